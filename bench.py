@@ -24,7 +24,9 @@ receives every trajectory (x, u, status, kkt by RCCL all-gather: of the last
 batch, or of every batch in asynchronous buckets) are reported beside it under
 `result_exchange`.
 
-Prints ONE JSON line on rank 0 (see README/DESIGN for the fields).
+Prints ONE JSON line on rank 0 (see README/DESIGN for the fields).  A plain run sets up, runs the W warm-up steps and
+times the K steps (`value`, `ms_per_step`); `--full` adds every other pass, check and baseline of the line;
+`--dump-outputs DIR` writes the results of the last timed step as .npy files.
 """
 from __future__ import annotations
 
@@ -93,7 +95,35 @@ def parse():
                          "plots a number that contains the collective; the other pass stays in the line beside it")
     ap.add_argument("--workload", choices=("planar", "whole_body"), default="planar",
                     help="planar = BASELINE configs[1] (the headline); whole_body = configs[2] (B2+Z1, one line with an MFMA roofline block)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the steady-state pass, contract repeats, in-order and converged passes, "
+                         "result exchange, parity checks against the oracle, extras and CPU baselines (the --no-* options select among "
+                         "them).  Off: set-up, W warm-up steps, the K timed steps, the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step, one DIR/<name>.npy per array (float32, "
+                         "other members as float64), at most 64 MB in all (a seeded sample of the problems beyond that)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 60 * 10**6   # below 64 MB with the .npy headers, in either unit
+
+
+def dump_outputs(d: str, arrays: dict) -> None:
+    """DIR/<name>.npy for every array (leading dimension = problem): float32 stays float32, everything else is written as
+    float64 (int32 members exactly).  Beyond DUMP_LIMIT_BYTES a fixed seeded sample of the problems is written, in order,
+    with its indices as problem_index.npy."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float32 if v.dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    n = next(iter(arrays.values())).shape[0]
+    per_problem = sum(v.nbytes // n for v in arrays.values())
+    if per_problem * n > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (per_problem + 8)
+        idx = np.sort(np.random.default_rng(20261016).choice(n, size=keep, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["problem_index"] = idx.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, f"{k}.npy"), v)
 
 
 def parity_spot_check(eng, batch, N, warmup, K, hooks, per_slot=32, tol=1e-4):
@@ -429,6 +459,9 @@ def whole_body_main(a, rank, world, local_rank, torch, dist):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt[0].item())
     dx, du = eng.last_step()
+    if rank == 0 and a.dump_outputs:
+        xw, uw = eng.get_iterate()
+        dump_outputs(a.dump_outputs, {"x": xw, "u": uw, "dx": dx, "du": du, "status": eng.status()})
     if rank == 0:
         lin /= steps; ric /= steps
         mfma_flops = N * ((15 + 15) * 12 + (6 * 3 + 6) * 8) * 2048.0 * B
@@ -446,7 +479,7 @@ def whole_body_main(a, rank, world, local_rank, torch, dist):
             "roofline_stage_kernel": stage_roofline(B * N, lin),
             "kernels_ms": {"wb::stage_kernel": lin, "wb::riccati_kernel": ric},
             "finite": bool(np.isfinite(dx).all() and np.isfinite(du).all()),
-            "cpu_baseline": None if a.no_cpu_baseline else wb_cpu_baseline(N, xi, ui, x0, xref, uref)}))
+            "cpu_baseline": wb_cpu_baseline(N, xi, ui, x0, xref, uref) if a.full and not a.no_cpu_baseline else None}))
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -479,10 +512,10 @@ def main():
         dist.init_process_group(backend="nccl", device_id=dev)
 
     B, N = a.batch, a.horizon
-    # a short run (the driver's --steps 20 is 0.4 ms of GPU work) also times LONG_STEPS back-to-back steps and reports
+    # a short --full run (the driver's --steps 20 is 0.4 ms of GPU work) also times LONG_STEPS back-to-back steps and reports
     # them beside the contract figure (`steady_state`)
     LONG_STEPS = 200
-    long_steps = LONG_STEPS if (world == 1 and a.steps < LONG_STEPS and a.steps > 0) else 0
+    long_steps = LONG_STEPS if (a.full and world == 1 and a.steps < LONG_STEPS and a.steps > 0) else 0
     slots = max(a.steps, long_steps) + a.warmup
     # rank r owns global problems [r*B, (r+1)*B): generated locally from the seeded stream
     batch = make_batch(B, N, offset=rank * B)
@@ -607,10 +640,13 @@ def main():
         time.sleep(float(os.environ["ALORE_BENCH_PRE_SLEEP_MS"]) * 1e-3)
     elapsed, dev_ms, used_graph = timed_pass(primary, a.steps)
     dev_ms, region_events_ms = grid_event_ms(dev_ms)
-    # The contract figure is ONE region of K steps measured once (one grid of ~0.13 ms).  `value` stays that first region; five further
-    # regions -- slots reloaded, the same W warm-up steps, the same barriers, the same K -- bracket it.
+    head_conv = a.headline == "converged_all_gather"
+    if a.dump_outputs and rank == 0 and not head_conv:   # the slot of the last timed step, before any other pass reloads it
+        dump_outputs(a.dump_outputs, eng.fetch(slot=a.warmup + a.steps - 1))
+    # The contract figure is ONE region of K steps measured once (one grid of ~0.13 ms).  `value` stays that first region; with --full
+    # five further regions -- slots reloaded, the same W warm-up steps, the same barriers, the same K -- bracket it.
     repeats = None
-    if world == 1 and a.steps > 0 and a.contract_repeats > 0:
+    if a.full and world == 1 and a.steps > 0 and a.contract_repeats > 0:
         r_ms, r_k = [], []
         for _ in range(a.contract_repeats):
             el_r, dms_r, _g = timed_pass(primary, a.steps)
@@ -637,7 +673,7 @@ def main():
     # the same K steps strictly one after the other (one launch in flight): what a single launch costs, and the figure the
     # rounds before the overlap quoted
     in_order = None
-    if world == 1 and a.overlap > 1 and a.steps > 0:
+    if a.full and world == 1 and a.overlap > 1 and a.steps > 0:
         eng.set_launch_overlap(1)
         hooks.single_grid = False
         el_o, dms_o, g_o = timed_pass("none", a.steps)
@@ -651,9 +687,8 @@ def main():
     # step i running under the solve of step i + 1.  Same pass at every world size (world = 1: the gather is a local copy),
     # so a scaling run compares like with like; `value` of the line keeps the sharded real-time-iteration unit at every N.
     conv = None
-    if a.steps > 0 and not a.no_converged:
+    if a.steps > 0 and not a.no_converged and (a.full or head_conv):
         try:
-            head_conv = a.headline == "converged_all_gather"
             Kc = a.steps if head_conv else min(a.steps, 50)   # as the headline: exactly K steps after W warm-up steps
             Wc = a.warmup if head_conv else min(a.warmup, 5)
             cg = ResultGatherer(dist, world, depth=2)
@@ -691,9 +726,11 @@ def main():
                 conv["in_flight"] = {"error": f"{type(e).__name__}: {e}"}
         except Exception as e:  # pragma: no cover
             conv = {"error": f"{type(e).__name__}: {e}"}
+        if a.dump_outputs and rank == 0 and head_conv:
+            dump_outputs(a.dump_outputs, eng.fetch(slot=Wc + Kc - 1))
 
     exchange = None
-    if world > 1 and a.gather != "none":
+    if a.full and world > 1 and a.gather != "none":
         # secondary figures: they must never cost the primary one (a rank that fails here would hang the others in the
         # collective, so the decision to run them is taken before, not inside, and errors are reported in the line)
         exchange = {}
@@ -714,7 +751,7 @@ def main():
     # parity of what was timed: the headline pass is run once more (untimed; the in_order / steady_state passes reloaded the
     # slots) and 32 seeded problems of each of 3 timed slots are compared with the CPU oracle at BASELINE.json's 1e-4
     spot = None
-    if rank == 0 and a.steps > 0:
+    if a.full and rank == 0 and a.steps > 0:
         spot = parity_spot_check(eng, batch, N, a.warmup, a.steps, hooks)
 
     # every timed step must have solved every problem
@@ -724,7 +761,7 @@ def main():
 
     # ... and the same timed configuration on the stress distribution (outside every timed region; the slots are reloaded after)
     stress = None
-    if rank == 0 and a.steps > 0 and world == 1 and not a.no_stress_check:
+    if a.full and rank == 0 and a.steps > 0 and world == 1 and not a.no_stress_check:
         try:
             stress = parity_stress_check(eng, N, a.warmup, a.steps, hooks)
         except Exception as e:  # pragma: no cover
@@ -851,7 +888,7 @@ def main():
             result["in_order"] = in_order
 
     # ---- extras on rank 0 of a single-GPU run: latency, converged solves, large batch, CPU baseline
-    if rank == 0 and world == 1 and not a.no_extras:
+    if a.full and rank == 0 and world == 1 and not a.no_extras:
         extras = {}
         # p50/p99 of one synchronous launch (what a caller of the C ABI sees): 1000 launches after 50 discarded,
         # B = 4096 and small batches
@@ -1418,7 +1455,7 @@ def main():
             extras["reference_horizon_n50"] = {"error": str(e)}
         result["extras"] = extras
 
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(N, batch, a.cpu_seconds)
 
     if rank == 0:

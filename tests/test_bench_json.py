@@ -64,12 +64,58 @@ def test_newest_committed_bench_json_is_clean():
 
 @pytest.mark.gpu
 def test_short_bench_run_has_no_errors():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--cpu-seconds", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "5", "--warmup", "2", "--cpu-seconds", "1"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     check_line(line)
     assert line["steady_state"]["steps"] >= 200 and "extras" in line
+
+
+def test_dump_outputs_keeps_dtypes_and_samples_beyond_the_limit(tmp_path):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    small = {"x": np.arange(4096 * 6, dtype=np.float32).reshape(4096, 2, 3), "status": np.arange(4096, dtype=np.int32)}
+    bench.dump_outputs(str(tmp_path / "s"), small)
+    assert sorted(os.listdir(tmp_path / "s")) == ["status.npy", "x.npy"]
+    x, st = np.load(tmp_path / "s" / "x.npy"), np.load(tmp_path / "s" / "status.npy")
+    assert x.dtype == np.float32 and np.array_equal(x, small["x"])
+    assert st.dtype == np.float64 and np.array_equal(st, small["status"])
+    n = 3 * bench.DUMP_LIMIT_BYTES // (21 * 48 * 8)
+    big = {"x": np.arange(n, dtype=np.float64)[:, None, None] * np.ones((1, 21, 48))}
+    for d in ("b1", "b2"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    total = sum(os.path.getsize(tmp_path / "b1" / f) for f in os.listdir(tmp_path / "b1"))
+    assert bench.DUMP_LIMIT_BYTES // 2 < total <= 64 * 10**6
+    idx = np.load(tmp_path / "b1" / "problem_index.npy")
+    assert np.all(np.diff(idx) > 0) and np.array_equal(idx, np.load(tmp_path / "b2" / "problem_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "b1" / "x.npy")[:, 0, 0], idx)
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_k_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run is the headline alone: exactly --steps timed steps, no secondary pass in the line; --dump-outputs writes the
+    last timed step's results, and a second run with the same arguments writes the same ones."""
+    import numpy as np
+    dumps = []
+    for rep in range(2):
+        d = tmp_path / f"out{rep}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+        check_line(line)
+        assert line["steps"] == 7 and line["warmup"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+        for k in ("steady_state", "contract_repeats", "in_order", "converged_all_gather", "parity_spot_check", "extras", "cpu_baseline"):
+            assert k not in line, k
+        files = sorted(os.listdir(d))
+        assert files == sorted(f"{k}.npy" for k in ("x", "u", "dual", "status", "n_iter", "kkt", "obj")), files
+        dumps.append({f[:-len(".npy")]: np.load(d / f) for f in files})
+    assert dumps[0]["x"].shape == (4096, 21, 3) and dumps[0]["x"].dtype == np.float32
+    assert (dumps[0]["status"] == 0).all()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
 
 
 def test_the_traffic_record_the_bench_line_quotes_is_valid_json():
