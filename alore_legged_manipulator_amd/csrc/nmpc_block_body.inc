@@ -482,151 +482,313 @@ next_item:
 #pragma unroll
             for (int s = 0; s < S; ++s) nonfree |= (j * S + s < N) ? (st0[s] | st1[s]) : 0;
             const bool cold = !gany<L>(nonfree != 0, gbase);
-            // gradient H du + g of the condensed QP at du
-            float g0[S], g1[S];
-            auto apply = [&](const float (&v0)[S], const float (&v1)[S], float (&g0)[S], float (&g1)[S]) {
-                float X0[S], X1[S], X2[S], in2[S];
-                float acc = 0.0f;
+            // Diagonal weights (the bench's and the reference controller's path): the packed form.  General weights: the scalar form, which
+            // keeps that body within the registers it had (pairs there cost it spills; the data decides the path, so every build that is
+            // compared bit for bit takes the same one)
+            if constexpr (DIAGW) {
+                // gradient H du + g of the condensed QP at du.  Iterate and gradient are PAIRS over the two inputs, (du0, du1) -> (g0, g1),
+                // like the rows of B and the weights: the state recursion (X0, X1), its adjoint (Lx, Ly) and the gradient run as packed
+                // multiply-adds, the input map's columns (B00, B10), (B01, B11) by one v_pk_mov_b32 each; X2, the term of node k + 2 and
+                // the DPP scans over the lanes stay scalar
+                v2f grad[S];
+                auto apply = [&](const v2f (&v)[S], v2f (&gr)[S]) {
+                    float X2[S], in2[S];
+                    v2f X01[S];
+                    float acc = 0.0f;
 #pragma unroll
-                for (int s = 0; s < S; ++s) { acc += BP2[s].x * (v0[s] - v1[s]) + d2[s]; X2[s] = acc; }
-                const float ex2 = gprefix<L>(acc, j) - acc + Dx2; // psi entering the block
+                    for (int s = 0; s < S; ++s) { acc += BP2[s].x * (v[s].x - v[s].y) + d2[s]; X2[s] = acc; }
+                    const float ex2 = gprefix<L>(acc, j) - acc + Dx2; // psi entering the block
 #pragma unroll
-                for (int s = 0; s < S; ++s) { in2[s] = (s == 0) ? ex2 : X2[(s > 0) ? s - 1 : 0] + ex2; }
+                    for (int s = 0; s < S; ++s) { in2[s] = (s == 0) ? ex2 : X2[(s > 0) ? s - 1 : 0] + ex2; }
 #pragma unroll
-                for (int s = 0; s < S; ++s) X2[s] += ex2;
-                float a0 = 0.0f, a1 = 0.0f;
-#pragma unroll
-                for (int s = 0; s < S; ++s) {
-                    a0 += sa[s] * in2[s] + BP0[s].x * v0[s] + BP0[s].y * v1[s] + d0[s]; X0[s] = a0;
-                    a1 += sb[s] * in2[s] + BP1[s].x * v0[s] + BP1[s].y * v1[s] + d1[s]; X1[s] = a1;
-                }
-                const float ex0 = gprefix<L>(a0, j) - a0 + Dx0, ex1 = gprefix<L>(a1, j) - a1 + Dx1;
-                float y0[S], y1[S], y2[S];
-#pragma unroll
-                for (int s = 0; s < S; ++s) {
-                    const float X0s = X0[s] + ex0, X1s = X1[s] + ex1;
-                    y0[s] = QA[s + 1].x * X0s + QA[s + 1].y * X1s + QB[s + 1].x * X2[s] + qA[s + 1].x;
-                    y1[s] = QA[s + 1].y * X0s + QC[s + 1].x * X1s + QB[s + 1].y * X2[s] + qA[s + 1].y;
-                    y2[s] = QB[s + 1].x * X0s + QB[s + 1].y * X1s + QC[s + 1].y * X2[s] + q2[s + 1];
-                }
-                // adjoint at node k + 1: suffix sums
-                float Lx[S], Ly[S], Lp[S];
-                float b0 = 0.0f, b1 = 0.0f;
-#pragma unroll
-                for (int s = S - 1; s >= 0; --s) { b0 += y0[s]; Lx[s] = b0; b1 += y1[s]; Ly[s] = b1; }
-                const float pr0 = gprefix<L>(b0, j), pr1 = gprefix<L>(b1, j);
-                const float es0 = glast<L>(pr0, lane) - pr0, es1 = glast<L>(pr1, lane) - pr1; // sum over the lanes above
-#pragma unroll
-                for (int s = 0; s < S; ++s) { Lx[s] += es0; Ly[s] += es1; }
-                // adjoint at node k + 2: the next slot's, the next lane's first, zero past the end of the group
-                const float nx_edge = (j == L - 1) ? 0.0f : lane_next<L>(Lx[0]);
-                const float ny_edge = (j == L - 1) ? 0.0f : lane_next<L>(Ly[0]);
-                float b2 = 0.0f;
-#pragma unroll
-                for (int s = S - 1; s >= 0; --s) {
-                    const float nxs = (s + 1 < S) ? Lx[(s + 1 < S) ? s + 1 : s] : nx_edge;
-                    const float nys = (s + 1 < S) ? Ly[(s + 1 < S) ? s + 1 : s] : ny_edge;
-                    b2 += y2[s] + sa[s + 1] * nxs + sb[s + 1] * nys;
-                    Lp[s] = b2;
-                }
-                const float pr2 = gprefix<L>(b2, j);
-                const float es2 = glast<L>(pr2, lane) - pr2;
-#pragma unroll
-                for (int s = 0; s < S; ++s) {
-                    const float Lps = Lp[s] + es2;
-                    g0[s] = RD[s].x * v0[s] + R01[s] * v1[s] + RP[s].x + BP0[s].x * Lx[s] + BP1[s].x * Ly[s] + BP2[s].x * Lps;
-                    g1[s] = R01[s] * v0[s] + RD[s].y * v1[s] + RP[s].y + BP0[s].y * Lx[s] + BP1[s].y * Ly[s] - BP2[s].x * Lps;
-                }
-            };
-            float is0[S], is1[S], w0[S], w1[S];
-            int hits = 0, badw = 0;
-#pragma unroll
-            for (int s = 0; s < S; ++s) { w0[s] = 0.0f; w1[s] = 0.0f; }
-            apply(w0, w1, g0, g1);
-#pragma unroll
-            for (int s = 0; s < S; ++s) {
-                const bool in = j * S + s < N;
-                is0[s] = in ? rcp_f(fmaxf(RD[s].x, 1e-20f)) : 0.0f;
-                is1[s] = in ? rcp_f(fmaxf(RD[s].y, 1e-20f)) : 0.0f;
-                const float j0 = -is0[s] * g0[s], j1 = -is1[s] * g1[s];
-                hits |= (j0 < lb0[s]) | (j0 > ub0[s]) | (j1 < lb1[s]) | (j1 > ub1[s]);
-                badw |= in ? ((!(RD[s].x > 0.0f)) | (!(RD[s].y > 0.0f))) : 0;
-                w0[s] = clampf(j0, lb0[s], ub0[s]); w1[s] = clampf(j1, lb1[s], ub1[s]);
-            }
-            const bool run = cold && gany<L>(hits != 0, gbase) && !gany<L>(badw != 0, gbase);
-            if (__any(run)) {
-                // Two buffers take turns as (iterate, gradient) of the current and of the previous step: a step reads both and writes the
-                // next iterate over the previous one, so nothing is copied from step to step.
-                // FULLN (the grid build, 3 .. 4 steps): plain steps, no bookkeeping.  Elsewhere a problem whose predicted set has
-                // not moved for two steps stops updating and the loop ends when all have (the fewest sweeps for a launch on its own).
-                float v0[S], v1[S], h0[S], h1[S]; // second buffer: starts as the previous point (0, gradient at 0)
-                int bits[S];
-                auto at_bounds = [&](float a0, float a1, int s) {
-                    return (a0 <= lb0[s] ? 1 : 0) | (a0 >= ub0[s] ? 2 : 0) | (a1 <= lb1[s] ? 4 : 0) | (a1 >= ub1[s] ? 8 : 0);
-                };
-#pragma unroll
-                for (int s = 0; s < S; ++s) { v0[s] = 0.0f; v1[s] = 0.0f; h0[s] = g0[s]; h1[s] = g1[s]; bits[s] = FULLN ? 0 : at_bounds(w0[s], w1[s], s); }
-                float alpha = 1.0f;
-                const int max_steps = FULLN ? p.pg_steps + 1 : p.pg_steps + p.pg_steps / 2; // FULLN: exactly pg_steps steps
-                int still = 0;
-                bool frozen = !run;
-                // one step: gradient at the current iterate (c*) into cg*, Barzilai-Borwein length from the differences to the previous point
-                // (q*, qg*), next iterate over q*; returns true when every problem of the wavefront has stopped
-                auto bb_step = [&](int t, const float (&c0)[S], const float (&c1)[S], float (&cg0)[S], float (&cg1)[S], float (&q0)[S], float (&q1)[S],
-                                   const float (&qg0)[S], const float (&qg1)[S]) -> bool {
-                    apply(c0, c1, cg0, cg1);
-                    float num = 0.0f, den = 0.0f;
+                    for (int s = 0; s < S; ++s) X2[s] += ex2;
+                    v2f a = bc2(0.0f); // (a0, a1)
 #pragma unroll
                     for (int s = 0; s < S; ++s) {
-                        const float e0 = c0[s] - q0[s], e1 = c1[s] - q1[s];
-                        num += RD[s].x * e0 * e0 + RD[s].y * e1 * e1;
-                        den += e0 * (cg0[s] - qg0[s]) + e1 * (cg1[s] - qg1[s]);
+                        const v2f Bc0 = lo_lo_u(BP0[s], BP1[s]), Bc1 = hi_hi_u(BP0[s], BP1[s]);
+                        const v2f t = mk2(sa[s] * in2[s] + d0[s], sb[s] * in2[s] + d1[s]);
+                        a += pfma(Bc0, bc2(v[s].x), pfma(Bc1, bc2(v[s].y), t));
+                        X01[s] = a;
                     }
-                    num = gtotal<L>(num, j, lane);
-                    den = gtotal<L>(den, j, lane);
-                    alpha = (den > 1e-30f) ? fminf(fmaxf(num * __builtin_amdgcn_rcpf(den), 1e-3f), 1.0f) : alpha;
-                    int moved = 0;
+                    const v2f ex01 = mk2(gprefix<L>(a.x, j) - a.x + Dx0, gprefix<L>(a.y, j) - a.y + Dx1);
+                    v2f y01[S];
+                    float y2[S];
 #pragma unroll
                     for (int s = 0; s < S; ++s) {
-                        const float n0 = __builtin_amdgcn_fmed3f(c0[s] - alpha * is0[s] * cg0[s], lb0[s], ub0[s]);
-                        const float n1 = __builtin_amdgcn_fmed3f(c1[s] - alpha * is1[s] * cg1[s], lb1[s], ub1[s]);
-                        if constexpr (FULLN) { // a problem that does not take the prediction runs along: its result is not used
-                            q0[s] = n0; q1[s] = n1;
-                        } else {
-                            q0[s] = frozen ? c0[s] : n0;
-                            q1[s] = frozen ? c1[s] : n1;
-                            const int nb = at_bounds(q0[s], q1[s], s);
-                            moved |= (j * S + s < N && nb != bits[s]) ? 1 : 0;
-                            bits[s] = nb;
+                        const v2f Xs = X01[s] + ex01;
+                        // (Q00 X0 + q0, Q11 X1 + q1): the off-diagonal entries are zeros
+                        y01[s] = pfma(lo_lo_u(QA[s + 1], QC[s + 1]), Xs, qA[s + 1]);
+                        y2[s] = QC[s + 1].y * X2[s] + q2[s + 1];
+                    }
+                    // adjoint at node k + 1: suffix sums
+                    v2f Lxy[S];
+                    float Lp[S];
+                    v2f b = bc2(0.0f); // (b0, b1)
+#pragma unroll
+                    for (int s = S - 1; s >= 0; --s) { b += y01[s]; Lxy[s] = b; }
+                    const float pr0 = gprefix<L>(b.x, j), pr1 = gprefix<L>(b.y, j);
+                    const v2f es01 = mk2(glast<L>(pr0, lane) - pr0, glast<L>(pr1, lane) - pr1); // sum over the lanes above
+#pragma unroll
+                    for (int s = 0; s < S; ++s) Lxy[s] += es01;
+                    // adjoint at node k + 2: the next slot's, the next lane's first, zero past the end of the group
+                    const float nx_edge = (j == L - 1) ? 0.0f : lane_next<L>(Lxy[0].x);
+                    const float ny_edge = (j == L - 1) ? 0.0f : lane_next<L>(Lxy[0].y);
+                    float b2 = 0.0f;
+#pragma unroll
+                    for (int s = S - 1; s >= 0; --s) {
+                        const float nxs = (s + 1 < S) ? Lxy[(s + 1 < S) ? s + 1 : s].x : nx_edge;
+                        const float nys = (s + 1 < S) ? Lxy[(s + 1 < S) ? s + 1 : s].y : ny_edge;
+                        b2 += y2[s] + sa[s + 1] * nxs + sb[s + 1] * nys;
+                        Lp[s] = b2;
+                    }
+                    const float pr2 = gprefix<L>(b2, j);
+                    const float es2 = glast<L>(pr2, lane) - pr2;
+#pragma unroll
+                    for (int s = 0; s < S; ++s) {
+                        const float Lps = Lp[s] + es2;
+                        // R v + r + B' (Lx, Ly, Lps): the rows of B are the pairs already
+                        gr[s] = pfma(BP0[s], bc2(Lxy[s].x), pfma(BP1[s], bc2(Lxy[s].y), pfma(BP2[s], bc2(Lps), pfma(RD[s], v[s], RP[s])))); // (R01 = 0)
+                    }
+                };
+                v2f is[S], w[S];
+                int hits = 0, badw = 0;
+#pragma unroll
+                for (int s = 0; s < S; ++s) w[s] = bc2(0.0f);
+                apply(w, grad);
+#pragma unroll
+                for (int s = 0; s < S; ++s) {
+                    const bool in = j * S + s < N;
+                    is[s].x = in ? rcp_f(fmaxf(RD[s].x, 1e-20f)) : 0.0f;
+                    is[s].y = in ? rcp_f(fmaxf(RD[s].y, 1e-20f)) : 0.0f;
+                    const v2f jp = -is[s] * grad[s];
+                    hits |= (jp.x < lb0[s]) | (jp.x > ub0[s]) | (jp.y < lb1[s]) | (jp.y > ub1[s]);
+                    badw |= in ? ((!(RD[s].x > 0.0f)) | (!(RD[s].y > 0.0f))) : 0;
+                    w[s].x = clampf(jp.x, lb0[s], ub0[s]); w[s].y = clampf(jp.y, lb1[s], ub1[s]);
+                }
+                const bool run = cold && gany<L>(hits != 0, gbase) && !gany<L>(badw != 0, gbase);
+                if (__any(run)) {
+                    // Two buffers take turns as (iterate, gradient) of the current and of the previous step: a step reads both and writes the
+                    // next iterate over the previous one, so nothing is copied from step to step.
+                    // FULLN (the grid build, 3 .. 4 steps): plain steps, no bookkeeping.  Elsewhere a problem whose predicted set has
+                    // not moved for two steps stops updating and the loop ends when all have (the fewest sweeps for a launch on its own).
+                    v2f v[S], h[S]; // second buffer: starts as the previous point (0, gradient at 0)
+                    int bits[S];
+                    auto at_bounds = [&](float a0, float a1, int s) {
+                        return (a0 <= lb0[s] ? 1 : 0) | (a0 >= ub0[s] ? 2 : 0) | (a1 <= lb1[s] ? 4 : 0) | (a1 >= ub1[s] ? 8 : 0);
+                    };
+#pragma unroll
+                    for (int s = 0; s < S; ++s) { v[s] = bc2(0.0f); h[s] = grad[s]; bits[s] = FULLN ? 0 : at_bounds(w[s].x, w[s].y, s); }
+                    float alpha = 1.0f;
+                    const int max_steps = FULLN ? p.pg_steps + 1 : p.pg_steps + p.pg_steps / 2; // FULLN: exactly pg_steps steps
+                    int still = 0;
+                    bool frozen = !run;
+                    // one step: gradient at the current iterate (c) into cg, Barzilai-Borwein length from the differences to the previous point
+                    // (q, qg), next iterate over q; returns true when every problem of the wavefront has stopped.  Differences, dot products
+                    // (one partial sum per input) and the step on pairs, the projection scalar
+                    auto bb_step = [&](int t, const v2f (&c)[S], v2f (&cg)[S], v2f (&q)[S], const v2f (&qg)[S]) -> bool {
+                        apply(c, cg);
+                        v2f nd = bc2(0.0f), dd = bc2(0.0f);
+#pragma unroll
+                        for (int s = 0; s < S; ++s) {
+                            const v2f e = c[s] - q[s];
+                            nd = pfma(RD[s] * e, e, nd);
+                            dd = pfma(e, cg[s] - qg[s], dd);
                         }
+                        const float num = gtotal<L>(nd.x + nd.y, j, lane);
+                        const float den = gtotal<L>(dd.x + dd.y, j, lane);
+                        alpha = (den > 1e-30f) ? fminf(fmaxf(num * __builtin_amdgcn_rcpf(den), 1e-3f), 1.0f) : alpha;
+                        const v2f na = bc2(-alpha);
+                        int moved = 0;
+#pragma unroll
+                        for (int s = 0; s < S; ++s) {
+                            const v2f st = pfma(na * is[s], cg[s], c[s]);
+                            const float n0 = __builtin_amdgcn_fmed3f(st.x, lb0[s], ub0[s]);
+                            const float n1 = __builtin_amdgcn_fmed3f(st.y, lb1[s], ub1[s]);
+                            if constexpr (FULLN) { // a problem that does not take the prediction runs along: its result is not used
+                                q[s].x = n0; q[s].y = n1;
+                            } else {
+                                q[s].x = frozen ? c[s].x : n0;
+                                q[s].y = frozen ? c[s].y : n1;
+                                const int nb = at_bounds(q[s].x, q[s].y, s);
+                                moved |= (j * S + s < N && nb != bits[s]) ? 1 : 0;
+                                bits[s] = nb;
+                            }
+                        }
+                        if constexpr (FULLN) return false;
+                        still = gany<L>(moved != 0, gbase) ? 0 : still + 1;
+                        frozen = frozen || (still >= 2 && t + 1 >= p.pg_steps);
+                        return __all(frozen);
+                    };
+                    auto take_set = [&](const v2f (&a)[S]) {
+#pragma unroll
+                        for (int s = 0; s < S; ++s) {
+                            const bool set = run && (j * S + s < N);
+                            const int n0 = (ub0[s] - lb0[s] > BOUNDTOL) ? ((a[s].x <= lb0[s]) ? ST_LOWER : ((a[s].x >= ub0[s]) ? ST_UPPER : ST_FREE)) : ST_LOWER;
+                            const int n1 = (ub1[s] - lb1[s] > BOUNDTOL) ? ((a[s].y <= lb1[s]) ? ST_LOWER : ((a[s].y >= ub1[s]) ? ST_UPPER : ST_FREE)) : ST_LOWER;
+                            st0[s] = set ? n0 : st0[s];
+                            st1[s] = set ? n1 : st1[s];
+                        }
+                    };
+                    bool in_w = true; // the latest iterate is in w, else in v
+#pragma unroll 1
+                    for (int t = 1; t < max_steps; t += 2) {
+                        const bool done = bb_step(t, w, grad, v, h);
+                        in_w = false;
+                        if (done || t + 1 >= max_steps) break;
+                        const bool done2 = bb_step(t + 1, v, h, w, grad);
+                        in_w = true;
+                        if (done2) break;
                     }
-                    if constexpr (FULLN) return false;
-                    still = gany<L>(moved != 0, gbase) ? 0 : still + 1;
-                    frozen = frozen || (still >= 2 && t + 1 >= p.pg_steps);
-                    return __all(frozen);
-                };
-                auto take_set = [&](const float (&a0)[S], const float (&a1)[S]) {
+                    if (in_w) take_set(w);
+                    else take_set(v);
+                }
+            } else {
+                // gradient H du + g of the condensed QP at du
+                float g0[S], g1[S];
+                auto apply = [&](const float (&v0)[S], const float (&v1)[S], float (&g0)[S], float (&g1)[S]) {
+                    float X0[S], X1[S], X2[S], in2[S];
+                    float acc = 0.0f;
+#pragma unroll
+                    for (int s = 0; s < S; ++s) { acc += BP2[s].x * (v0[s] - v1[s]) + d2[s]; X2[s] = acc; }
+                    const float ex2 = gprefix<L>(acc, j) - acc + Dx2; // psi entering the block
+#pragma unroll
+                    for (int s = 0; s < S; ++s) { in2[s] = (s == 0) ? ex2 : X2[(s > 0) ? s - 1 : 0] + ex2; }
+#pragma unroll
+                    for (int s = 0; s < S; ++s) X2[s] += ex2;
+                    float a0 = 0.0f, a1 = 0.0f;
 #pragma unroll
                     for (int s = 0; s < S; ++s) {
-                        const bool set = run && (j * S + s < N);
-                        const int n0 = (ub0[s] - lb0[s] > BOUNDTOL) ? ((a0[s] <= lb0[s]) ? ST_LOWER : ((a0[s] >= ub0[s]) ? ST_UPPER : ST_FREE)) : ST_LOWER;
-                        const int n1 = (ub1[s] - lb1[s] > BOUNDTOL) ? ((a1[s] <= lb1[s]) ? ST_LOWER : ((a1[s] >= ub1[s]) ? ST_UPPER : ST_FREE)) : ST_LOWER;
-                        st0[s] = set ? n0 : st0[s];
-                        st1[s] = set ? n1 : st1[s];
+                        a0 += sa[s] * in2[s] + BP0[s].x * v0[s] + BP0[s].y * v1[s] + d0[s]; X0[s] = a0;
+                        a1 += sb[s] * in2[s] + BP1[s].x * v0[s] + BP1[s].y * v1[s] + d1[s]; X1[s] = a1;
+                    }
+                    const float ex0 = gprefix<L>(a0, j) - a0 + Dx0, ex1 = gprefix<L>(a1, j) - a1 + Dx1;
+                    float y0[S], y1[S], y2[S];
+#pragma unroll
+                    for (int s = 0; s < S; ++s) {
+                        const float X0s = X0[s] + ex0, X1s = X1[s] + ex1;
+                        y0[s] = QA[s + 1].x * X0s + QA[s + 1].y * X1s + QB[s + 1].x * X2[s] + qA[s + 1].x;
+                        y1[s] = QA[s + 1].y * X0s + QC[s + 1].x * X1s + QB[s + 1].y * X2[s] + qA[s + 1].y;
+                        y2[s] = QB[s + 1].x * X0s + QB[s + 1].y * X1s + QC[s + 1].y * X2[s] + q2[s + 1];
+                    }
+                    // adjoint at node k + 1: suffix sums
+                    float Lx[S], Ly[S], Lp[S];
+                    float b0 = 0.0f, b1 = 0.0f;
+#pragma unroll
+                    for (int s = S - 1; s >= 0; --s) { b0 += y0[s]; Lx[s] = b0; b1 += y1[s]; Ly[s] = b1; }
+                    const float pr0 = gprefix<L>(b0, j), pr1 = gprefix<L>(b1, j);
+                    const float es0 = glast<L>(pr0, lane) - pr0, es1 = glast<L>(pr1, lane) - pr1; // sum over the lanes above
+#pragma unroll
+                    for (int s = 0; s < S; ++s) { Lx[s] += es0; Ly[s] += es1; }
+                    // adjoint at node k + 2: the next slot's, the next lane's first, zero past the end of the group
+                    const float nx_edge = (j == L - 1) ? 0.0f : lane_next<L>(Lx[0]);
+                    const float ny_edge = (j == L - 1) ? 0.0f : lane_next<L>(Ly[0]);
+                    float b2 = 0.0f;
+#pragma unroll
+                    for (int s = S - 1; s >= 0; --s) {
+                        const float nxs = (s + 1 < S) ? Lx[(s + 1 < S) ? s + 1 : s] : nx_edge;
+                        const float nys = (s + 1 < S) ? Ly[(s + 1 < S) ? s + 1 : s] : ny_edge;
+                        b2 += y2[s] + sa[s + 1] * nxs + sb[s + 1] * nys;
+                        Lp[s] = b2;
+                    }
+                    const float pr2 = gprefix<L>(b2, j);
+                    const float es2 = glast<L>(pr2, lane) - pr2;
+#pragma unroll
+                    for (int s = 0; s < S; ++s) {
+                        const float Lps = Lp[s] + es2;
+                        g0[s] = RD[s].x * v0[s] + R01[s] * v1[s] + RP[s].x + BP0[s].x * Lx[s] + BP1[s].x * Ly[s] + BP2[s].x * Lps;
+                        g1[s] = R01[s] * v0[s] + RD[s].y * v1[s] + RP[s].y + BP0[s].y * Lx[s] + BP1[s].y * Ly[s] - BP2[s].x * Lps;
                     }
                 };
-                bool in_w = true; // the latest iterate is in (w0, w1), else in (v0, v1)
-#pragma unroll 1
-                for (int t = 1; t < max_steps; t += 2) {
-                    const bool done = bb_step(t, w0, w1, g0, g1, v0, v1, h0, h1);
-                    in_w = false;
-                    if (done || t + 1 >= max_steps) break;
-                    const bool done2 = bb_step(t + 1, v0, v1, h0, h1, w0, w1, g0, g1);
-                    in_w = true;
-                    if (done2) break;
+                float is0[S], is1[S], w0[S], w1[S];
+                int hits = 0, badw = 0;
+#pragma unroll
+                for (int s = 0; s < S; ++s) { w0[s] = 0.0f; w1[s] = 0.0f; }
+                apply(w0, w1, g0, g1);
+#pragma unroll
+                for (int s = 0; s < S; ++s) {
+                    const bool in = j * S + s < N;
+                    is0[s] = in ? rcp_f(fmaxf(RD[s].x, 1e-20f)) : 0.0f;
+                    is1[s] = in ? rcp_f(fmaxf(RD[s].y, 1e-20f)) : 0.0f;
+                    const float j0 = -is0[s] * g0[s], j1 = -is1[s] * g1[s];
+                    hits |= (j0 < lb0[s]) | (j0 > ub0[s]) | (j1 < lb1[s]) | (j1 > ub1[s]);
+                    badw |= in ? ((!(RD[s].x > 0.0f)) | (!(RD[s].y > 0.0f))) : 0;
+                    w0[s] = clampf(j0, lb0[s], ub0[s]); w1[s] = clampf(j1, lb1[s], ub1[s]);
                 }
-                if (in_w) take_set(w0, w1);
-                else take_set(v0, v1);
+                const bool run = cold && gany<L>(hits != 0, gbase) && !gany<L>(badw != 0, gbase);
+                if (__any(run)) {
+                    // Two buffers take turns as (iterate, gradient) of the current and of the previous step: a step reads both and writes the
+                    // next iterate over the previous one, so nothing is copied from step to step.
+                    // FULLN (the grid build, 3 .. 4 steps): plain steps, no bookkeeping.  Elsewhere a problem whose predicted set has
+                    // not moved for two steps stops updating and the loop ends when all have (the fewest sweeps for a launch on its own).
+                    float v0[S], v1[S], h0[S], h1[S]; // second buffer: starts as the previous point (0, gradient at 0)
+                    int bits[S];
+                    auto at_bounds = [&](float a0, float a1, int s) {
+                        return (a0 <= lb0[s] ? 1 : 0) | (a0 >= ub0[s] ? 2 : 0) | (a1 <= lb1[s] ? 4 : 0) | (a1 >= ub1[s] ? 8 : 0);
+                    };
+#pragma unroll
+                    for (int s = 0; s < S; ++s) { v0[s] = 0.0f; v1[s] = 0.0f; h0[s] = g0[s]; h1[s] = g1[s]; bits[s] = FULLN ? 0 : at_bounds(w0[s], w1[s], s); }
+                    float alpha = 1.0f;
+                    const int max_steps = FULLN ? p.pg_steps + 1 : p.pg_steps + p.pg_steps / 2; // FULLN: exactly pg_steps steps
+                    int still = 0;
+                    bool frozen = !run;
+                    // one step: gradient at the current iterate (c*) into cg*, Barzilai-Borwein length from the differences to the previous point
+                    // (q*, qg*), next iterate over q*; returns true when every problem of the wavefront has stopped
+                    auto bb_step = [&](int t, const float (&c0)[S], const float (&c1)[S], float (&cg0)[S], float (&cg1)[S], float (&q0)[S], float (&q1)[S],
+                                       const float (&qg0)[S], const float (&qg1)[S]) -> bool {
+                        apply(c0, c1, cg0, cg1);
+                        float num = 0.0f, den = 0.0f;
+#pragma unroll
+                        for (int s = 0; s < S; ++s) {
+                            const float e0 = c0[s] - q0[s], e1 = c1[s] - q1[s];
+                            num += RD[s].x * e0 * e0 + RD[s].y * e1 * e1;
+                            den += e0 * (cg0[s] - qg0[s]) + e1 * (cg1[s] - qg1[s]);
+                        }
+                        num = gtotal<L>(num, j, lane);
+                        den = gtotal<L>(den, j, lane);
+                        alpha = (den > 1e-30f) ? fminf(fmaxf(num * __builtin_amdgcn_rcpf(den), 1e-3f), 1.0f) : alpha;
+                        int moved = 0;
+#pragma unroll
+                        for (int s = 0; s < S; ++s) {
+                            const float n0 = __builtin_amdgcn_fmed3f(c0[s] - alpha * is0[s] * cg0[s], lb0[s], ub0[s]);
+                            const float n1 = __builtin_amdgcn_fmed3f(c1[s] - alpha * is1[s] * cg1[s], lb1[s], ub1[s]);
+                            if constexpr (FULLN) { // a problem that does not take the prediction runs along: its result is not used
+                                q0[s] = n0; q1[s] = n1;
+                            } else {
+                                q0[s] = frozen ? c0[s] : n0;
+                                q1[s] = frozen ? c1[s] : n1;
+                                const int nb = at_bounds(q0[s], q1[s], s);
+                                moved |= (j * S + s < N && nb != bits[s]) ? 1 : 0;
+                                bits[s] = nb;
+                            }
+                        }
+                        if constexpr (FULLN) return false;
+                        still = gany<L>(moved != 0, gbase) ? 0 : still + 1;
+                        frozen = frozen || (still >= 2 && t + 1 >= p.pg_steps);
+                        return __all(frozen);
+                    };
+                    auto take_set = [&](const float (&a0)[S], const float (&a1)[S]) {
+#pragma unroll
+                        for (int s = 0; s < S; ++s) {
+                            const bool set = run && (j * S + s < N);
+                            const int n0 = (ub0[s] - lb0[s] > BOUNDTOL) ? ((a0[s] <= lb0[s]) ? ST_LOWER : ((a0[s] >= ub0[s]) ? ST_UPPER : ST_FREE)) : ST_LOWER;
+                            const int n1 = (ub1[s] - lb1[s] > BOUNDTOL) ? ((a1[s] <= lb1[s]) ? ST_LOWER : ((a1[s] >= ub1[s]) ? ST_UPPER : ST_FREE)) : ST_LOWER;
+                            st0[s] = set ? n0 : st0[s];
+                            st1[s] = set ? n1 : st1[s];
+                        }
+                    };
+                    bool in_w = true; // the latest iterate is in (w0, w1), else in (v0, v1)
+#pragma unroll 1
+                    for (int t = 1; t < max_steps; t += 2) {
+                        const bool done = bb_step(t, w0, w1, g0, g1, v0, v1, h0, h1);
+                        in_w = false;
+                        if (done || t + 1 >= max_steps) break;
+                        const bool done2 = bb_step(t + 1, v0, v1, h0, h1, w0, w1, g0, g1);
+                        in_w = true;
+                        if (done2) break;
+                    }
+                    if (in_w) take_set(w0, w1);
+                    else take_set(v0, v1);
+                }
             }
             if (STAMP) t_pg = __builtin_amdgcn_s_memtime() - tp0;
         }

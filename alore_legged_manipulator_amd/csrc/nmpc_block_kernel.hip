@@ -231,6 +231,11 @@ __device__ __forceinline__ v2f pfma(v2f a, v2f b, v2f c) { return __builtin_elem
 __device__ __forceinline__ v2f hi_hi(v2f a, v2f b) { v2f r; asm("v_pk_mov_b32 %0, %1, %2 op_sel:[1,1]" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ v2f lo_lo(v2f a, v2f b) { v2f r; asm("v_pk_mov_b32 %0, %1, %2 op_sel:[0,0]" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ v2f hi_lo(v2f a, v2f b) { v2f r; asm("v_pk_mov_b32 %0, %1, %2 op_sel:[1,0]" : "=v"(r) : "v"(a), "v"(b)); return r; }
+// the same, redone at every use (volatile: never merged with another use nor hoisted out of the prediction's step loop): the column
+// pairs of the input map and the diagonal of Q that the prediction's Hessian application takes, kept in registers from one step to
+// the next, would take registers that are not there
+__device__ __forceinline__ v2f lo_lo_u(v2f a, v2f b) { v2f r; asm volatile("v_pk_mov_b32 %0, %1, %2 op_sel:[0,0]" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ v2f hi_hi_u(v2f a, v2f b) { v2f r; asm volatile("v_pk_mov_b32 %0, %1, %2 op_sel:[1,1]" : "=v"(r) : "v"(a), "v"(b)); return r; }
 
 // nmpc_core.h: riccati_step on register pairs.  The cost-to-go travels as Pa = (P00, P01), Pb = (P02, P12), Pc = (P11, P22),
 // pa = (p0, p1), p2; the stage as B0 = (B00, B01), B1 = (B10, B11), B2 = (B20, -B20), Rd = (R00, R11), r = (r0, r1),
