@@ -87,6 +87,8 @@ SYMBOLS = (
     ("alore_nmpc_batch_default_bounds", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_void_p]),
     ("alore_nmpc_rti", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_int, C.c_void_p]),
     ("alore_nmpc_rti_many", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    ("alore_nmpc_rti_converge", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    ("alore_nmpc_rti_many_converge", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     ("alore_nmpc_set_launch_overlap", C.c_int, [C.c_void_p, C.c_int]),
     ("alore_nmpc_rti_many_prepare", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_int]),
     ("alore_nmpc_synchronize", C.c_int, [C.c_void_p, C.c_void_p]),

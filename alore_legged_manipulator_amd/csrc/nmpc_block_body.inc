@@ -1,6 +1,6 @@
-// nmpc_block_body.inc -- the body of nmpc::rti_block_kernel, included where L, S, DIAG, STAMP, ONCE, FULLN, TRACE, PERSIST (compile-time
-// constants) and the kernel arguments p_arg, grp_arg (RtiParams, RtiGroup: the first two of the kernel, read through the
-// kernel-argument segment) are in scope: nmpc_block_kernel.hip includes it in rti_block_kernel and in rti_block_sampler_kernel.
+// nmpc_block_body.inc -- the body of nmpc::rti_block_kernel, included where L, S, DIAG, STAMP, ONCE, FULLN, TRACE, PERSIST, TWOPH, CONV
+// (compile-time constants), KParams (the type of the first kernel argument: RtiParams for CONV, else RtiParamsCore) and the kernel
+// arguments p_arg, grp_arg (KParams, RtiGroup: the first two of the kernel, read through the kernel-argument segment) are in scope: nmpc_block_kernel.hip includes it in rti_block_kernel and in rti_block_sampler_kernel.
 // Kept as text, not as a device function: the kernels of the first kind compile to the instructions they had before the second existed.
     extern __shared__ float4 lds_raw[];
     float* lds = reinterpret_cast<float*>(lds_raw);
@@ -30,7 +30,7 @@
     int role = 1, tail_c = 0, bi_role = 0;
     if constexpr (TWOPH) {
         const auto& g0 = *reinterpret_cast<const __attribute__((address_space(4))) RtiGroup*>(
-            (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + ((sizeof(RtiParams) + 7) & ~(size_t)7));
+            (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + ((sizeof(KParams) + 7) & ~(size_t)7));
         const int unit = g0.blocks_per_batch + g0.tp_tail;
         const int u = (int)blockIdx.x / unit, r = (int)blockIdx.x - u * unit;
         if (r < g0.blocks_per_batch) {
@@ -49,7 +49,7 @@
     }
     if constexpr (TWOPH) {
         const auto& g0 = *reinterpret_cast<const __attribute__((address_space(4))) RtiGroup*>(
-            (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + ((sizeof(RtiParams) + 7) & ~(size_t)7));
+            (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + ((sizeof(KParams) + 7) & ~(size_t)7));
         if (g0.tp_trace != nullptr && threadIdx.x == 0) {
             g0.tp_trace[(size_t)blockIdx.x * 4] = (long long)__builtin_amdgcn_s_memrealtime();
             g0.tp_trace[(size_t)blockIdx.x * 4 + 3] = (long long)role | ((long long)bi_role << 8);
@@ -57,7 +57,7 @@
     }
     if constexpr (FULLN && !PERSIST && !TWOPH) {
         const auto& g0 = *reinterpret_cast<const __attribute__((address_space(4))) RtiGroup*>(
-            (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + ((sizeof(RtiParams) + 7) & ~(size_t)7));
+            (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + ((sizeof(KParams) + 7) & ~(size_t)7));
         if (g0.xcd_on) {
             const int x = (int)blockIdx.x & 7, xcd_k = (int)blockIdx.x >> 3;
             if (blockIdx.x == 0 && threadIdx.x == 0 && g0.xcd_end != nullptr) g0.xcd_end[32] = (unsigned long long)__builtin_amdgcn_s_memrealtime(); // the grid's start
@@ -77,8 +77,8 @@ next_item:
         asm volatile("" : "+v"(lane));
         asm volatile("" : "+s"(ka));
     }
-    const auto& p = *reinterpret_cast<const __attribute__((address_space(4))) RtiParams*>(ka);
-    const auto& grp = *reinterpret_cast<const __attribute__((address_space(4))) RtiGroup*>(ka + ((sizeof(RtiParams) + 7) & ~(size_t)7));
+    const auto& p = *reinterpret_cast<const __attribute__((address_space(4))) KParams*>(ka);
+    const auto& grp = *reinterpret_cast<const __attribute__((address_space(4))) RtiGroup*>(ka + ((sizeof(KParams) + 7) & ~(size_t)7));
     (void)p_arg; (void)grp_arg;
     const int g = lane / L, j = lane % L;
     const int gbase = lane - j;
@@ -392,6 +392,13 @@ next_item:
     int status = RET_OK, n_iter = 0;
     float kkt = 0.0f;
     bool defer = false;                       // first pass of a two-phase grid: this problem is left to the tail
+    // CONV: `done` -- the problem has met the tolerance (at iteration conv_k) or takes no part (padding group, masked out: done from the
+    // start).  From there on its x, u, xN and dual stay as they are (selects; its group sits out the sweeps, which alone write the dual)
+    // and status, n_iter, kkt keep the values of that iteration (status_c, n_iter_c, kkt_c).  Group-uniform, like everything it is made of.
+    bool done = false;
+    int conv_k = 0, status_c = RET_OK, n_iter_c = 0;
+    float kkt_c = 0.0f;
+    if constexpr (CONV) done = !valid || (p.mask != nullptr && p.mask[prob] == 0);
     unsigned long long defer_mask = 0;
 
     // ONCE: one real-time iteration per launch (the control tick): no loop, so the members that only feed the linearisation
@@ -802,7 +809,7 @@ next_item:
 #pragma unroll
         for (int i = 0; i < 3; ++i) { V[6 + i] = qN[i]; Vin[6 + i] = qN[i]; }
         int pd_fail = 0;
-        bool changed = true;
+        bool changed = CONV ? !done : true; // CONV: a finished problem keeps its dual and its steps (only the sweeps of a `changed` group write them)
         int khi = N - 1;
         int it = 0;
         n_iter = 0;
@@ -1295,11 +1302,20 @@ next_item:
                 comp += (mu0[s] > 1e-12f) ? fabsf(lb0[s] * mu0[s]) : ((mu0[s] < -1e-12f) ? fabsf(ub0[s] * mu0[s]) : 0.0f);
                 comp += (mu1[s] > 1e-12f) ? fabsf(lb1[s] * mu1[s]) : ((mu1[s] < -1e-12f) ? fabsf(ub1[s] * mu1[s]) : 0.0f);
             }
-            x[s][0] += dxs[s][0]; x[s][1] += dxs[s][1]; x[s][2] += dxs[s][2];
+            if constexpr (CONV) { // a finished problem keeps its iterate
+#pragma unroll
+                for (int c = 0; c < 3; ++c) x[s][c] = done ? x[s][c] : x[s][c] + dxs[s][c];
+            } else {
+                x[s][0] += dxs[s][0]; x[s][1] += dxs[s][1]; x[s][2] += dxs[s][2];
+            }
             // a free control may sit up to TOL_PRIMAL outside its box: keep the iterate feasible
             const float e0 = (lb0[s] <= ub0[s]) ? clampf(du0[s], lb0[s], ub0[s]) : du0[s];
             const float e1 = (lb1[s] <= ub1[s]) ? clampf(du1[s], lb1[s], ub1[s]) : du1[s];
-            u[s][0] += e0; u[s][1] += e1;
+            if constexpr (CONV) {
+                u[s][0] = done ? u[s][0] : u[s][0] + e0; u[s][1] = done ? u[s][1] : u[s][1] + e1;
+            } else {
+                u[s][0] += e0; u[s][1] += e1;
+            }
         }
         if (j == top) { // terminal node
             if (DIAG) {
@@ -1308,7 +1324,12 @@ next_item:
                 gd += (QN[0] * b0 + QN[1] * b1 + QN[2] * b2 + qN[0]) * e0 + (QN[1] * b0 + QN[3] * b1 + QN[4] * b2 + qN[1]) * e1 +
                       (QN[2] * b0 + QN[4] * b1 + QN[5] * b2 + qN[2]) * e2;
             }
-            xN[0] += dxo[0]; xN[1] += dxo[1]; xN[2] += dxo[2];
+            if constexpr (CONV) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) xN[c] = done ? xN[c] : xN[c] + dxo[c];
+            } else {
+                xN[0] += dxo[0]; xN[1] += dxo[1]; xN[2] += dxo[2];
+            }
         }
         if constexpr (!ONCE) {
             // further iterations: EVERY lane linearises the terminal cost at the new terminal node -- the slot of node N, whose weights and
@@ -1318,6 +1339,14 @@ next_item:
             for (int c = 0; c < 3; ++c) xN[c] = __int_as_float(__builtin_amdgcn_ds_bpermute((gbase + top) * 4, __float_as_int(xN[c])));
         }
         if (DIAG) kkt = fabsf(gtotal<L>(gd, j, lane)) + gtotal<L>(comp, j, lane);
+        if constexpr (CONV) {
+            // the results of the iteration that met the tolerance stay
+            status_c = done ? status_c : status; n_iter_c = done ? n_iter_c : n_iter; kkt_c = done ? kkt_c : kkt;
+            const bool met = !done && kkt < p.kkt_tol; // false for a NaN
+            conv_k = met ? sqp + 1 : conv_k;
+            done = done || met;
+            if (__all(done)) break; // wavefront-uniform: every problem of the wavefront has finished
+        }
     }
     if (STAMP) t5 = __builtin_amdgcn_s_memtime();
 
@@ -1438,9 +1467,16 @@ next_item:
     }
     }
     if (valid && !skip && !defer && j == 0) {
-        pb.status[prob] = status;
-        pb.n_iter[prob] = n_iter;
-        if (DIAG && pb.kkt) pb.kkt[prob] = kkt;
+        if constexpr (CONV) { // the iteration that met the tolerance, or the last one (-n_sqp: the tolerance was never met)
+            pb.status[prob] = status_c;
+            pb.n_iter[prob] = n_iter_c;
+            if (pb.kkt) pb.kkt[prob] = kkt_c;
+            if (p.sqp_iters) p.sqp_iters[(size_t)bi * p.B + prob] = done ? conv_k : -n_sqp;
+        } else {
+            pb.status[prob] = status;
+            pb.n_iter[prob] = n_iter;
+            if (DIAG && pb.kkt) pb.kkt[prob] = kkt;
+        }
         if (DIAG && pb.obj) pb.obj[prob] = obj;
     }
     if constexpr (CLEAN) { // the queue: this block's entries, then its report (stores only; nothing here waits)

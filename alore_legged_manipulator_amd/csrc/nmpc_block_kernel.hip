@@ -348,15 +348,23 @@ int block_lds_floats(int N, int L)
 // load: profiles/r05_a_timeline_*.txt); with tickets a faster XCD takes more items.  The ticket of the next item is requested
 // when the current one starts, so its latency is never waited for.
 // TWOPH (grid builds): the batches of the grid are solved in two passes -- see the top of nmpc_block_body.inc.
+// CONV (converged solves, alore_nmpc_rti_converge; built with DIAG, without ONCE / STAMP / PERSIST / TWOPH / TRACE): a problem stops
+// after the first iteration whose KKT value is below RtiParams::kkt_tol -- its iterate, dual and results are frozen from there on by
+// selects, its group sits out the sweeps -- and the wavefront leaves the iteration loop when all of its problems have (a scalar branch).
+// Its kernel argument is the whole RtiParams; every other build takes RtiParamsCore (nmpc_kernels.h).
 // -DALORE_EXP_WPE=n (experiments, never the shipped build): at least n wavefronts per SIMD, i.e. at most 512 / n registers
 #ifdef ALORE_EXP_WPE
 #define ALORE_KERNEL_ATTR __attribute__((amdgpu_waves_per_eu(ALORE_EXP_WPE, ALORE_EXP_WPE)))
 #else
 #define ALORE_KERNEL_ATTR
 #endif
-template <int L, int S, bool DIAG, bool STAMP, bool ONCE, bool FULLN = false, bool TRACE = false, bool PERSIST = false, bool TWOPH = false>
-__global__ __launch_bounds__(64) ALORE_KERNEL_ATTR void rti_block_kernel(const RtiParams p_arg, const RtiGroup grp_arg)
+template <int L, int S, bool DIAG, bool STAMP, bool ONCE, bool FULLN = false, bool TRACE = false, bool PERSIST = false, bool TWOPH = false,
+          bool CONV = false>
+__global__ __launch_bounds__(64) ALORE_KERNEL_ATTR void rti_block_kernel(const std::conditional_t<CONV, RtiParams, RtiParamsCore> p_arg,
+                                                                         const RtiGroup grp_arg)
 {
+    static_assert(!CONV || (DIAG && !STAMP && !ONCE && !TRACE && !PERSIST && !TWOPH), "CONV: the multi-iteration builds with the KKT value");
+    using KParams = std::conditional_t<CONV, RtiParams, RtiParamsCore>;
     constexpr bool SCAN_BUILD = true;
 #include "nmpc_block_body.inc"
 }
@@ -371,7 +379,7 @@ __global__ __launch_bounds__(64) ALORE_KERNEL_ATTR void rti_block_kernel(const R
 // pose the solve starts from: x0, and the turns its references are shifted by) -- as a kernel of its own it cost 4.7 us of the
 // tick's chain for three memory round trips and a microsecond of arithmetic.
 template <int L, int S, bool DIAG>
-__global__ __launch_bounds__(64) void rti_block_sampler_kernel(const RtiParams p_arg, const RtiGroup grp_arg, const AheadSampler sa, const PlantAhead pl)
+__global__ __launch_bounds__(64) void rti_block_sampler_kernel(const RtiParamsCore p_arg, const RtiGroup grp_arg, const AheadSampler sa, const PlantAhead pl)
 {
     if ((int)blockIdx.x < sa.first_block && pl.on) {
         const int r = (int)blockIdx.x * (64 / L) + (int)threadIdx.x / L;
@@ -389,7 +397,8 @@ __global__ __launch_bounds__(64) void rti_block_sampler_kernel(const RtiParams p
                                          (int)threadIdx.x, 64);
         return;
     }
-    constexpr bool STAMP = false, ONCE = true, FULLN = false, TRACE = false, PERSIST = false, TWOPH = false;
+    constexpr bool STAMP = false, ONCE = true, FULLN = false, TRACE = false, PERSIST = false, TWOPH = false, CONV = false;
+    using KParams = std::conditional_t<(L < 0), RtiParams, RtiParamsCore>; // = RtiParamsCore, spelt dependent: the body's CONV statements stay unchecked
     // the (16, 2) build keeps the sequential backward sweep here: with the scan over the lanes (nmpc_scan.h) it takes 284 registers, and
     // the sampler's wavefronts run beside the solver's only while a SIMD holds one of each (256): the tick of 4096 robots went from 19
     // to 27 us; capped at 256 registers (16 - 22 spilled) 21.0 against 19.5 us.  (32, 1) has room: 256 robots 14.3 -> 11.9 us per tick.
@@ -465,7 +474,9 @@ hipError_t launch_rti_block_group(const RtiParams& p, const RtiGroup& grp, const
     if ((long long)g.grid * grp.count > 0x7fffffffLL) return hipErrorInvalidValue;
     const bool stamp = p.stamps != nullptr;
     const bool diag = stamp || grp.b[0].kkt != nullptr || grp.b[0].obj != nullptr;
-    const bool once = p.n_sqp == 1;
+    const bool conv = p.kkt_tol >= 0.0f; // converged solve: the CONV builds (a launch of one iteration too)
+    if (conv && (stamp || grp.counter != nullptr || grp.tp_count2 > 0 || grp.trace)) return hipErrorInvalidValue;
+    const bool once = p.n_sqp == 1 && !conv;
     const void* fn = nullptr;
     int v = -1;
 #define PICK(LL, SS, idx)                                                                                 \
@@ -483,13 +494,28 @@ hipError_t launch_rti_block_group(const RtiParams& p, const RtiGroup& grp, const
     PICK(16, 4, 3)
     PICK(32, 1, 4)
 #undef PICK
+#define PICK_CONV(LL, SS, idx)                                                                            \
+    if (g.L == LL && g.RS == SS) {                                                                        \
+        v = 35 + idx;                                                                                     \
+        fn = (const void*)rti_block_kernel<LL, SS, true, false, false, false, false, false, false, true>; \
+    }
+    if (conv) {
+        fn = nullptr;
+        PICK_CONV(4, 5, 0)
+        PICK_CONV(8, 3, 1)
+        PICK_CONV(16, 2, 2)
+        PICK_CONV(16, 4, 3)
+        PICK_CONV(32, 1, 4)
+    }
+#undef PICK_CONV
     if (g.L == 4 && g.RS == 5 && p.N == 20 && once && !stamp) { // the control tick at the horizon that fills the (4, 5) mapping
         v = 25 + (diag ? 0 : 1);
         fn = diag ? (const void*)rti_block_kernel<4, 5, true, false, true, true> : (const void*)rti_block_kernel<4, 5, false, false, true, true>;
     }
     if (g.L == 4 && g.RS == 5 && p.N == 20 && !once && !stamp) { // several iterations per launch (converged solves) at the horizon that fills the mapping
-        v = 33 + (diag ? 0 : 1);
-        fn = diag ? (const void*)rti_block_kernel<4, 5, true, false, false, true> : (const void*)rti_block_kernel<4, 5, false, false, false, true>;
+        v = conv ? 40 : 33 + (diag ? 0 : 1);
+        fn = conv   ? (const void*)rti_block_kernel<4, 5, true, false, false, true, false, false, false, true>
+             : diag ? (const void*)rti_block_kernel<4, 5, true, false, false, true> : (const void*)rti_block_kernel<4, 5, false, false, false, true>;
     }
     const bool persist = grp.counter != nullptr;
     if (persist) {
@@ -513,11 +539,12 @@ hipError_t launch_rti_block_group(const RtiParams& p, const RtiGroup& grp, const
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     dev &= 15;
-    static size_t configured[16][35] = {{0}};
-    if (g.lds_bytes > configured[dev][v]) {
-        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds_bytes);
+    const size_t lds_bytes = g.lds_bytes;
+    static size_t configured[16][41] = {{0}};
+    if (lds_bytes > configured[dev][v]) {
+        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return e;
-        configured[dev][v] = g.lds_bytes;
+        configured[dev][v] = lds_bytes;
     }
     void* args[] = {const_cast<RtiParams*>(&p), const_cast<RtiGroup*>(&grp)};
     unsigned blocks = (unsigned)g.grid * (unsigned)grp.count;
@@ -533,7 +560,7 @@ hipError_t launch_rti_block_group(const RtiParams& p, const RtiGroup& grp, const
         if (nb > 0x7fffffffLL) return hipErrorInvalidValue;
         blocks = (unsigned)nb;
     }
-    e = hipLaunchKernel(fn, dim3(blocks), dim3(64), args, g.lds_bytes, s);
+    e = hipLaunchKernel(fn, dim3(blocks), dim3(64), args, lds_bytes, s);
     if (e != hipSuccess) return e;
     return hipGetLastError();
 }

@@ -58,6 +58,11 @@ struct alore_nmpc_solver {
     const unsigned char* mask = nullptr; // see alore_nmpc_set_problem_mask
     const float* lin_x = nullptr; // see alore_nmpc_set_linearization_point
     const float* lin_u = nullptr;
+    // alore_nmpc_rti_converge / alore_nmpc_rti_many_converge: the request of the call in progress (conv_tol < 0: none), and the row of
+    // conv_iters ([count][B]) that belongs to the first batch of the launch being enqueued
+    float conv_tol = -1.0f;
+    int* conv_iters = nullptr;
+    int conv_row = 0;
     // pinned staging for alore_nmpc_batch_upload / _download from pageable host memory
     char* stage_up = nullptr;
     char* stage_down = nullptr;
@@ -540,6 +545,8 @@ void fill_params(alore_nmpc_handle h, const alore_nmpc_batch* dev, int B, int n_
     p->lin_x = h->lin_x;
     p->lin_u = h->lin_u;
     p->mask = nullptr;
+    p->kkt_tol = h->conv_tol;
+    p->sqp_iters = (h->conv_tol >= 0.0f && h->conv_iters) ? h->conv_iters + (size_t)h->conv_row * B : nullptr;
 }
 
 // one launch for one batch; B_in_flight = problems of all launches that run concurrently with it (0: only this one)
@@ -567,7 +574,8 @@ int rti_one(alore_nmpc_handle h, const alore_nmpc_batch* dev, int B, int n_sqp, 
     // would avoid it -- B = 1, N = 20, cold start, synchronous launch p50: 3 / 4 / 6 / 8 steps 22.7 / 23.6 / 23.8 / 24.8 us (round 6)
     if (h->auto_pg && B <= 64 && h->cfg.N <= 32) p.pg_steps = 3;
     hipStream_t s = (hipStream_t)stream;
-    if (h->stamps) {
+    const bool stamps = h->stamps && p.kkt_tol < 0.0f; // converged solves have no stamped build
+    if (stamps) {
         const size_t need = (size_t)g.grid * g.wpb * 8; // one record per wavefront
         if (need > h->stamps_cap) {
             if (h->d_stamps) (void)hipFree(h->d_stamps);
@@ -582,7 +590,7 @@ int rti_one(alore_nmpc_handle h, const alore_nmpc_batch* dev, int B, int n_sqp, 
     // one batch that is a grid of several residencies by itself (B >= 32768 on the packed mapping): what alore_nmpc_rti_many gives the
     // batches of a call -- staggered first residency, XCD shares, the prediction length of a full chip -- applies to it as it stands
     static const bool big_as_group = !(getenv("ALORE_NMPC_BIG_AS_GROUP") && atoi(getenv("ALORE_NMPC_BIG_AS_GROUP")) == 0);
-    if (big_as_group && use_block && g.L == 4 && g.RS == 5 && !h->stamps && !co && !plant && (long)g.grid >= 2L * 4 * h->n_cu) {
+    if (big_as_group && use_block && g.L == 4 && g.RS == 5 && !stamps && !co && !plant && (long)g.grid >= 2L * 4 * h->n_cu) {
         const int rc = rti_group(h, dev, 1, B, n_sqp, stream, B, nullptr);
         if (rc != ALORE_NMPC_OK) return rc;
         if (h->timing) {
@@ -609,7 +617,7 @@ int rti_one(alore_nmpc_handle h, const alore_nmpc_batch* dev, int B, int n_sqp, 
     }
     h->last_geom = g;
     h->have_geom = true;
-    if (h->stamps) { // diagnostic mode: synchronous, never used for timing
+    if (stamps) { // diagnostic mode: synchronous, never used for timing
         const int n_waves = g.grid * g.wpb;
         std::vector<long long> host((size_t)n_waves * 8);
         HIP_TRY(h, hipStreamSynchronize(s));
@@ -703,6 +711,23 @@ void remember_independent(alore_nmpc_handle h, const alore_nmpc_batch* batches, 
     h->indep_used[k] = ++h->indep_clock;
 }
 
+// Converged solves: does the iteration-count array of the call ([count][B] ints) stay clear of every array of every batch?  (Its rows
+// are disjoint by construction; one pass over the 15 x count ranges.)
+bool iters_independent(alore_nmpc_handle h, const alore_nmpc_batch* batches, int count, int B)
+{
+    const size_t lo = reinterpret_cast<size_t>(h->conv_iters), hi = lo + (size_t)count * B * sizeof(int);
+    const int N = h->cfg.N;
+    for (int i = 0; i < count; ++i) {
+        for (int m = 0; m < kNumMembers; ++m) {
+            const void* q = member_ptr(batches + i, kMembers[m]);
+            if (!q) continue;
+            const size_t a = reinterpret_cast<size_t>(q), b = a + (size_t)B * kMembers[m].per_problem(N) * 4; // (a shared member's one copy lies inside)
+            if (a < hi && lo < b) return false;
+        }
+    }
+    return true;
+}
+
 // `count` independent batches on the stage-block kernel as ONE grid (nmpc_block_kernel.hip: RtiGroup): by table
 // (count <= GROUP_MAX) or, with `stride`, by constant member strides (any count)
 int rti_group(alore_nmpc_handle h, const alore_nmpc_batch* batches, int count, int B, int n_sqp, void* stream, int B_in_flight,
@@ -752,7 +777,8 @@ int rti_group(alore_nmpc_handle h, const alore_nmpc_batch* batches, int count, i
     static const bool persist_on = getenv("ALORE_NMPC_PERSIST") && atoi(getenv("ALORE_NMPC_PERSIST")) == 1;
     grp.counter = nullptr;
     grp.persist_blocks = 0;
-    if (persist_on && g.L == 4 && g.RS == 5 && h->cfg.N == 20 && n_sqp == 1 && (long)g.grid * count >= 2L * 4 * h->n_cu) {
+    const bool conv = p.kkt_tol >= 0.0f; // converged solve: none of the persistent, two-phase or traced builds exists for it
+    if (persist_on && !conv && g.L == 4 && g.RS == 5 && h->cfg.N == 20 && n_sqp == 1 && (long)g.grid * count >= 2L * 4 * h->n_cu) {
         grp.counter = h->d_tickets + 2 * (h->ticket_turn++ % alore_nmpc_solver::kTicketRing);
         grp.persist_blocks = 4 * h->n_cu;
     }
@@ -788,7 +814,7 @@ int rti_group(alore_nmpc_handle h, const alore_nmpc_batch* batches, int count, i
             for (int i = 0; i < 32; ++i) mx = h->tp_rec[i] > mx ? h->tp_rec[i] : mx;
             if (mx > 0) h->tp_share = (double)mx / (double)B; // the fullest queue of the last grid
         }
-        bool on = want != 0 && !grp.counter && nmpc::rti_block_two_phase_supported(p, g) && (long)g.grid * count >= 2 * resident;
+        bool on = want != 0 && !conv && !grp.counter && nmpc::rti_block_two_phase_supported(p, g) && (long)g.grid * count >= 2 * resident;
         int tail = 0, lag = 0, count2 = 0;
         if (on) {
             tail = (int)std::ceil(h->tp_share * 1.08 * g.grid) + 3;
@@ -926,7 +952,7 @@ int rti_group(alore_nmpc_handle h, const alore_nmpc_batch* batches, int count, i
     }
     static const char* trace_path = getenv("ALORE_NMPC_TRACE");
     grp.trace = nullptr;
-    if (trace_path && grp.tp_count2 == 0 && g.L == 4 && g.RS == 5 && h->cfg.N == 20 && n_sqp == 1 && batches[0].kkt && batches[0].obj) {
+    if (trace_path && !conv && grp.tp_count2 == 0 && g.L == 4 && g.RS == 5 && h->cfg.N == 20 && n_sqp == 1 && batches[0].kkt && batches[0].obj) {
         const size_t words = (size_t)g.grid * count * 8;
         long long* d_trace = nullptr;
         HIP_TRY(h, hipMalloc((void**)&d_trace, words * sizeof(long long)));
@@ -1056,9 +1082,12 @@ int alore_nmpc_rti_many(alore_nmpc_handle h, const alore_nmpc_batch* batches, in
             if (batches_independent(h, batches, count, B)) remember_independent(h, batches, count, B);
             else ways = 1;
         }
+        // a converged solve also writes its iteration counts: they must not overlap any array of the call either
+        if (ways > 1 && h->conv_tol >= 0.0f && h->conv_iters && !iters_independent(h, batches, count, B)) ways = 1;
     }
     if (ways == 1) {
         for (int i = 0; i < count; ++i) {
+            h->conv_row = i;
             const int rc = rti_one(h, batches + i, B, n_sqp, stream, 0);
             if (rc != ALORE_NMPC_OK) return rc;
         }
@@ -1089,6 +1118,7 @@ int alore_nmpc_rti_many(alore_nmpc_handle h, const alore_nmpc_batch* batches, in
             // alore_nmpc_set_timing: HIP events on the launch stream directly around the grid (alore_nmpc_get_launch_info: last_kernel_ms is
             // then the duration of the ONE grid that served the `count` batches)
             if (h->timing) HIP_TRY(h, hipEventRecord(h->ev0, main_s));
+            h->conv_row = 0;
             const int rc = rti_group(h, batches, count, B, n_sqp, stream, (int)(inflight > clampB ? clampB : inflight), stride);
             if (h->timing && rc == ALORE_NMPC_OK) {
                 HIP_TRY(h, hipEventRecord(h->ev1, main_s));
@@ -1111,6 +1141,7 @@ int alore_nmpc_rti_many(alore_nmpc_handle h, const alore_nmpc_batch* batches, in
         int rc = ALORE_NMPC_OK;
         for (int gi = 0, first = 0; first < count && rc == ALORE_NMPC_OK; ++gi, first += per) {
             const int n = (count - first < per) ? count - first : per;
+            h->conv_row = first;
             rc = rti_group(h, batches + first, n, B, n_sqp, (two && (gi & 1)) ? (void*)h->side[0] : (void*)main_s, Bf, nullptr);
         }
         if (two) { // join even after a failed launch: the side stream must not stay forked (an open capture would be lost)
@@ -1129,6 +1160,7 @@ int alore_nmpc_rti_many(alore_nmpc_handle h, const alore_nmpc_batch* batches, in
     // different streams would pair events of different launches): in order on the caller's stream.
     if (h->timing) {
         for (int i = 0; i < count; ++i) {
+            h->conv_row = i;
             const int rc1 = rti_one(h, batches + i, B, n_sqp, stream, 0);
             if (rc1 != ALORE_NMPC_OK) return rc1;
         }
@@ -1146,6 +1178,7 @@ int alore_nmpc_rti_many(alore_nmpc_handle h, const alore_nmpc_batch* batches, in
     const int Bf = (int)(inflight > clampB ? clampB : inflight); // the automatic lane mapping packs for all of them
     for (int i = 0; i < count && rc == ALORE_NMPC_OK; ++i) {
         const int w = i % ways;
+        h->conv_row = i;
         rc = rti_one(h, batches + i, B, n_sqp, w == 0 ? (void*)main_s : (void*)h->side[w - 1], Bf);
     }
     for (int w = 1; w <= forked; ++w) { // join every forked stream, whatever happened above
@@ -1155,6 +1188,32 @@ int alore_nmpc_rti_many(alore_nmpc_handle h, const alore_nmpc_batch* batches, in
         if (rc == ALORE_NMPC_OK && e2 != hipSuccess) rc = fail(h, ALORE_NMPC_E_HIP, "rti_many: join", e2);
     }
     return rc;
+}
+
+namespace {
+// the converge request of one call: on the handle while the launches are enqueued (fill_params reads it), gone when the call returns
+struct ConvScope {
+    alore_nmpc_handle h;
+    ConvScope(alore_nmpc_handle h_, float tol, int* iters) : h(h_) { h->conv_tol = tol; h->conv_iters = iters; h->conv_row = 0; }
+    ~ConvScope() { h->conv_tol = -1.0f; h->conv_iters = nullptr; h->conv_row = 0; }
+};
+} // namespace
+
+int alore_nmpc_rti_converge(alore_nmpc_handle h, const alore_nmpc_batch* dev, int B, int max_sqp, float kkt_tol, int* sqp_iters, void* stream)
+{
+    if (!h || !dev || B <= 0 || max_sqp < 1 || !(kkt_tol >= 0.0f)) return fail(h, ALORE_NMPC_E_INVALID, "rti_converge: bad argument");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    ConvScope cs(h, kkt_tol, sqp_iters);
+    return rti_one(h, dev, B, max_sqp, stream, 0);
+}
+
+int alore_nmpc_rti_many_converge(alore_nmpc_handle h, const alore_nmpc_batch* batches, int count, int B, int max_sqp, float kkt_tol,
+                                 int* sqp_iters, void* stream)
+{
+    if (!h || !batches || count < 1 || B <= 0 || max_sqp < 1 || !(kkt_tol >= 0.0f))
+        return fail(h, ALORE_NMPC_E_INVALID, "rti_many_converge: bad argument");
+    ConvScope cs(h, kkt_tol, sqp_iters);
+    return alore_nmpc_rti_many(h, batches, count, B, max_sqp, stream);
 }
 
 int alore_nmpc_synchronize(alore_nmpc_handle h, void* stream)

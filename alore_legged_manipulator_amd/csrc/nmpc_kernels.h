@@ -8,8 +8,10 @@
 
 namespace nmpc {
 
-// kernel parameters, passed by value
-struct RtiParams {
+// kernel parameters, passed by value.  RtiParamsCore is what every build takes as its kernel argument except the converged-solve
+// builds (CONV, alore_nmpc_rti_converge), which take the whole RtiParams: the parameters of the early exit are appended behind the
+// core, so the kernel-argument layout -- and the instructions -- of every other build are those they had before the CONV builds existed
+struct RtiParamsCore {
     alore_nmpc_batch b;
     int B;
     int N;
@@ -24,6 +26,13 @@ struct RtiParams {
     unsigned shared; // ALORE_NMPC_SHARED_* bits: members that are ONE copy for the whole batch (problem stride 0)
     const unsigned char* mask; // optional [B]: 0 = the problem is left exactly as it is (alore_nmpc_set_problem_mask), else null
 };
+struct RtiParams : RtiParamsCore {
+    // converged solves (alore_nmpc_rti_converge): a problem stops after the first iteration whose KKT value is below kkt_tol, n_sqp is the
+    // cap.  kkt_tol < 0: a plain launch of n_sqp iterations (the other builds; never a caller's value, the C ABI refuses it)
+    float kkt_tol;
+    int* sqp_iters; // optional [count][B], row = batch of the grid: the iteration a problem met the tolerance at, -n_sqp if it never did
+};
+static_assert(sizeof(RtiParams) == sizeof(RtiParamsCore) + 16, "RtiParams: the early-exit parameters follow the core");
 
 // up to GROUP_MAX independent batches served by one grid of the stage-block kernel (by value in the kernel arguments: 24 x 120 B of the 4 KB they hold)
 constexpr int GROUP_MAX = 24;

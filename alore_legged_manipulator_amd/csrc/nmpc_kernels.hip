@@ -608,9 +608,15 @@ __device__ __forceinline__ int active_set_rescue(float* row, int N, int j, bool 
 }
 
 // one wavefront per workgroup, G = 64 / L problems per wavefront
-template <int L, bool STAMP, int WPB, bool WREG, bool DIAG>
-__global__ __launch_bounds__(64 * WPB) void rti_kernel(const RtiParams p)
+// CONV (converged solves, alore_nmpc_rti_converge; built with DIAG, without STAMP): a problem stops after the first iteration whose KKT
+// value is below p.kkt_tol -- its records of x, u and the dual are no longer written, its group sits out the sweeps, status / n_iter / kkt
+// keep the values of that iteration -- and the wavefront leaves the iteration loop when all of its problems have (wavefront-uniform: the
+// loop synchronises only the wavefront, so a wavefront may leave while the others of its workgroup go on).  Its kernel argument is the
+// whole RtiParams; the other builds take RtiParamsCore (nmpc_kernels.h).
+template <int L, bool STAMP, int WPB, bool WREG, bool DIAG, bool CONV = false>
+__global__ __launch_bounds__(64 * WPB) void rti_kernel(const std::conditional_t<CONV, RtiParams, RtiParamsCore> p)
 {
+    static_assert(!CONV || (DIAG && !STAMP), "CONV: the builds with the KKT value");
     extern __shared__ float4 lds_raw[];
     float* lds = reinterpret_cast<float*>(lds_raw);
     const int N = p.N;
@@ -752,8 +758,14 @@ __global__ __launch_bounds__(64 * WPB) void rti_kernel(const RtiParams p)
     constexpr bool want_kkt = DIAG, want_obj = DIAG;
     int status = RET_OK, n_iter = 0;
     float kkt = 0.0f;
+    // CONV: `done` -- met the tolerance (at iteration conv_k; status_c, n_iter_c, kkt_c are its results) or takes no part (padding group,
+    // masked out: done from the start).  Group-uniform.
+    bool done = false, all_done = false;
+    int conv_k = 0, status_c = RET_OK, n_iter_c = 0;
+    float kkt_c = 0.0f;
+    if constexpr (CONV) done = !keep;
 
-    for (int sqp = 0; sqp < p.n_sqp; ++sqp) {
+    for (int sqp = 0; sqp < p.n_sqp && !(CONV && all_done); ++sqp) {
         // ---- phase A (stage-parallel): linearise, Gauss-Newton cost, bounds, working-set guess
         int infeasible = 0;
         for (int k = j; k <= N; k += L) {
@@ -931,7 +943,7 @@ __global__ __launch_bounds__(64 * WPB) void rti_kernel(const RtiParams p)
 
         // ---- phase B: working-set iterations
         int pd_fail = 0;
-        bool changed = true; // "this problem still needs a sweep"
+        bool changed = CONV ? !done : true; // "this problem still needs a sweep" (CONV: a finished problem keeps its records)
         int khi = N - 1;     // highest stage whose cost-to-go is stale
         int it = 0;
         n_iter = 0;
@@ -1130,7 +1142,7 @@ __global__ __launch_bounds__(64 * WPB) void rti_kernel(const RtiParams p)
                       (q1.x * sb.x + q1.y * sb.y + q1.z * sb.z + q1.w) * t1 +
                       (q2.x * sb.x + q2.y * sb.y + q2.z * sb.z + q2.w) * t2;
             }
-            st4(rec, S_X, xk.x + dxp.x, xk.y + dxp.y, xk.z + dxp.z, 0.0f);
+            if (!(CONV && done)) st4(rec, S_X, xk.x + dxp.x, xk.y + dxp.y, xk.z + dxp.z, 0.0f);
             if (k < N) {
                 const float4 dd = lds4(rec, S_D), R = lds4(rec, S_R), bnd = lds4(rec, S_BND), sd = lds4(rec, S_STDU),
                              mu = lds4(rec, S_MU), uy = lds4(rec, S_UY);
@@ -1142,10 +1154,17 @@ __global__ __launch_bounds__(64 * WPB) void rti_kernel(const RtiParams p)
                 // a free control may sit up to TOL_PRIMAL outside its box: keep the iterate feasible
                 const float du0 = (bnd.x <= bnd.y) ? clampf(sd.z, bnd.x, bnd.y) : sd.z;
                 const float du1 = (bnd.z <= bnd.w) ? clampf(sd.w, bnd.z, bnd.w) : sd.w;
-                st4(rec, S_UY, uy.x + du0, uy.y + du1, mu.x, mu.y);
+                if (!(CONV && done)) st4(rec, S_UY, uy.x + du0, uy.y + du1, mu.x, mu.y);
             }
         }
         if (want_kkt) kkt = fabsf(group_total<L>(gd, j)) + group_total<L>(comp, j);
+        if constexpr (CONV) {
+            status_c = done ? status_c : status; n_iter_c = done ? n_iter_c : n_iter; kkt_c = done ? kkt_c : kkt;
+            const bool met = !done && kkt < p.kkt_tol; // false for a NaN
+            conv_k = met ? sqp + 1 : conv_k;
+            done = done || met;
+            all_done = __all(done);
+        }
         wave_sync();
     }
     if (STAMP) t_stamp[5] = __builtin_amdgcn_s_memtime();
@@ -1193,9 +1212,16 @@ __global__ __launch_bounds__(64 * WPB) void rti_kernel(const RtiParams p)
     float obj = 0.0f;
     if (want_obj) obj = 0.5f * group_total<L>(part, j);
     if (keep && writer) {
-        p.b.status[prob] = status;
-        p.b.n_iter[prob] = n_iter;
-        if (want_kkt && p.b.kkt) p.b.kkt[prob] = kkt;
+        if constexpr (CONV) {
+            p.b.status[prob] = status_c;
+            p.b.n_iter[prob] = n_iter_c;
+            if (p.b.kkt) p.b.kkt[prob] = kkt_c;
+            if (p.sqp_iters) p.sqp_iters[prob] = done ? conv_k : -p.n_sqp;
+        } else {
+            p.b.status[prob] = status;
+            p.b.n_iter[prob] = n_iter;
+            if (want_kkt && p.b.kkt) p.b.kkt[prob] = kkt;
+        }
         if (want_obj && p.b.obj) p.b.obj[prob] = obj;
     }
     if (STAMP && lane == 0 && p.stamps) {
@@ -1215,6 +1241,8 @@ hipError_t launch_rti(const RtiParams& p, const LaunchGeom& g, hipStream_t s)
     dim3 grid(g.grid), block(g.threads);
     hipError_t e = hipSuccess;
     const bool stamp = p.stamps != nullptr;
+    const bool conv = p.kkt_tol >= 0.0f; // converged solve: the CONV builds (with the KKT value, without stamps)
+    if (conv && stamp) return hipErrorInvalidValue;
     int dev = 0; // hipFuncSetAttribute applies to the current device: the cache is per device
     e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
@@ -1222,12 +1250,17 @@ hipError_t launch_rti(const RtiParams& p, const LaunchGeom& g, hipStream_t s)
     switch (g.L) {
 #define CASE(LL)                                                                                              \
     case LL: {                                                                                                \
-        static size_t configured[16][16] = {{0}}; /* raise the dynamic-LDS cap once per (device, variant) */  \
+        static size_t configured[16][32] = {{0}}; /* raise the dynamic-LDS cap once per (device, variant) */  \
         constexpr bool WR = (LL >= 32);                                                                       \
-        const bool diag = stamp || p.b.kkt != nullptr || p.b.obj != nullptr;                                  \
-        const int v = (stamp ? 1 : 0) + (g.wpb == 4 ? 2 : 0) + ((g.wreg && WR) ? 4 : 0) + (diag ? 0 : 8);    \
+        const bool diag = conv || stamp || p.b.kkt != nullptr || p.b.obj != nullptr;                          \
+        const int v = (stamp ? 1 : 0) + (g.wpb == 4 ? 2 : 0) + ((g.wreg && WR) ? 4 : 0) + (diag ? 0 : 8) +  \
+                      (conv ? 16 : 0);                                                                        \
         const void* fn = nullptr;                                                                             \
         switch (v) {                                                                                          \
+        case 16: fn = (const void*)rti_kernel<LL, false, 1, false, true, true>; break;                        \
+        case 18: fn = (const void*)rti_kernel<LL, false, 4, false, true, true>; break;                        \
+        case 20: fn = (const void*)rti_kernel<LL, false, 1, WR, true, true>; break;                           \
+        case 22: fn = (const void*)rti_kernel<LL, false, 4, WR, true, true>; break;                                                                                                                     \
         case 0: fn = (const void*)rti_kernel<LL, false, 1, false, true>; break;                               \
         case 1: fn = (const void*)rti_kernel<LL, true, 1, false, true>; break;                                \
         case 2: fn = (const void*)rti_kernel<LL, false, 4, false, true>; break;                               \

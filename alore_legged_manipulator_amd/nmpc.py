@@ -64,6 +64,8 @@ class BatchedNmpc:
             dt_ = torch.int32 if k in ("status", "n_iter") else torch.float32
             self.ts[k] = torch.zeros((self.slots,) + shp, dtype=dt_, device=self.device)
         self.t = {k: v[0] for k, v in self.ts.items()}
+        # iterations of the last converged solve of every slot (rti_converge / rti_range_converge): k, or -max_sqp if never met
+        self.sqp_iters = torch.zeros((self.slots, self.B), dtype=torch.int32, device=self.device)
         # diagnostics=False: kkt / obj are not asked for (NULL pointers) and the kernel skips them, like the
         # reference's tick, which never calls acado_getKKT / acado_getObjective
         skip = () if diagnostics else ("kkt", "obj")
@@ -208,6 +210,25 @@ class BatchedNmpc:
         rc = self.lib.alore_nmpc_rti_many(self.h, args[0], args[1], args[2], n_sqp, self._stream())
         if rc != 0:
             self._check(rc)
+
+    def rti_converge(self, max_sqp: int, kkt_tol: float, slot: int = 0) -> None:
+        """at most max_sqp iterations per problem, stopping after the first whose KKT value is below kkt_tol
+        (alore_nmpc_rti_converge); the iteration counts go to self.sqp_iters[slot]"""
+        self._check(self.lib.alore_nmpc_rti_converge(self.h, C.byref(self._batches[slot]), self.B, int(max_sqp), float(kkt_tol),
+                                                     C.c_void_p(self.sqp_iters[slot].data_ptr()), self._stream()))
+
+    def rti_range_converge(self, first: int, count: int, max_sqp: int, kkt_tol: float) -> None:
+        """rti_converge for slots first .. first + count - 1 by ONE call (alore_nmpc_rti_many_converge); counts in
+        self.sqp_iters[first : first + count]"""
+        if first < 0 or count < 1 or first + count > self.slots:
+            raise ValueError(f"rti_range_converge: slots {first} .. {first + count - 1} outside 0 .. {self.slots - 1}")
+        args = getattr(self, "_range_args", {}).get((first, count))
+        if args is None:
+            if not hasattr(self, "_batch_array"):
+                self._batch_array = (Batch * self.slots)(*self._batches)
+            args = (C.cast(C.byref(self._batch_array, first * C.sizeof(Batch)), C.POINTER(Batch)), C.c_int(count), C.c_int(self.B))
+        self._check(self.lib.alore_nmpc_rti_many_converge(self.h, args[0], args[1], args[2], int(max_sqp), float(kkt_tol),
+                                                          C.c_void_p(self.sqp_iters[first].data_ptr()), self._stream()))
 
     def prepare_range(self, first: int, count: int) -> None:
         """the independence check of rti_range(first, count) ahead of time (alore_nmpc_rti_many_prepare): later calls on these

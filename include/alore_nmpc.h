@@ -172,6 +172,31 @@ int alore_nmpc_rti(alore_nmpc_handle h, const alore_nmpc_batch *dev, int B, int 
  * of B): results of different mappings agree to float32 rounding; pin lanes_per_problem where the bits of a single
  * alore_nmpc_rti launch are wanted. */
 int alore_nmpc_rti_many(alore_nmpc_handle h, const alore_nmpc_batch *batches, int count, int B, int n_sqp, void *stream);
+/* Converged solves: ACADO's `for (...) { feedbackStep(); if (getKKT() < tol) break; }` per problem.  Every problem runs at most
+ * max_sqp real-time iterations and stops after the first iteration k whose KKT value (alore_nmpc_batch.kkt, acado_getKKT) satisfies
+ * kkt_k < kkt_tol; its x, u, dual, status, n_iter and kkt are then those after iteration k (k ticks of the reference), and obj is
+ * evaluated at that iterate.  A problem that never meets the tolerance -- a NaN KKT value never does, nor does kkt_tol = 0 -- gets the
+ * results of alore_nmpc_rti(max_sqp).  sqp_iters: DEVICE [B] ints (alore_nmpc_rti_many_converge: [count][B], row i = batches[i]) or
+ * NULL; sqp_iters[b] = k, or -max_sqp when problem b never met the tolerance.  kkt_tol < 0 or NaN, max_sqp < 1: ALORE_NMPC_E_INVALID.
+ * Everything else is that of alore_nmpc_rti / alore_nmpc_rti_many: mappings, groups and streams modes, strided runs, descriptor tables,
+ * prepared sets, shared members, the linearisation point, timing, launch info, stream capture (no host synchronisation).
+ * Automatic choices:
+ *  - the KKT value is computed whether or not batch.kkt is NULL (it is stored only where it is not);
+ *  - the problems of a wavefront share its control flow (16 of them on the packed mapping), so a wavefront runs until its slowest
+ *    problem has met the tolerance; a problem that has met it is frozen -- the further iterations of its mates leave it exactly as it
+ *    was -- and the wavefront leaves the iteration loop when all of its problems have.  The time of a call follows the slowest problem
+ *    of each wavefront, not the mean;
+ *  - the launches run their own builds of the kernels, also at max_sqp = 1 and kkt_tol = 0 (results agree with alore_nmpc_rti to
+ *    float32 rounding); none of them runs in two phases, persistently or traced, whatever alore_nmpc_set_two_phase and the diagnostic
+ *    environment ask for;
+ *  - in alore_nmpc_rti_many_converge the iteration counts are an array the call writes: if they overlap any array of the batches, the
+ *    batches run one after the other, as overlapping batches do;
+ *  - masked problems (alore_nmpc_set_problem_mask) write nothing, sqp_iters included, and count as converged from the start: a
+ *    wavefront of masked problems leaves after its first iteration. */
+int alore_nmpc_rti_converge(alore_nmpc_handle h, const alore_nmpc_batch *dev, int B, int max_sqp, float kkt_tol,
+                            int *sqp_iters /* DEVICE [B] or NULL */, void *stream);
+int alore_nmpc_rti_many_converge(alore_nmpc_handle h, const alore_nmpc_batch *batches, int count, int B, int max_sqp,
+                                 float kkt_tol, int *sqp_iters /* DEVICE [count][B] or NULL */, void *stream);
 /* Wait for the work enqueued on `stream` (hipStreamSynchronize on the solver's device): what a synchronous control tick does after
  * alore_nmpc_rti, for callers that do not link the HIP runtime themselves.  One robot, cold start, through this pair from a C++
  * host: 22 us p50 (tools/micro/rti_latency.cpp), of which 2.4 us is the enqueue. */
