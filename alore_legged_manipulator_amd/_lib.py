@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ALORE_NMPC_LIB") or os.path.join(HERE, "libalore_nmpc.so")
 
 FP = C.POINTER(C.c_float)
+DP = C.POINTER(C.c_double)
 IP = C.POINTER(C.c_int)
 
 
@@ -122,6 +123,10 @@ SYMBOLS = (
     ("alore_nmpc_set_linearization_point", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("alore_nmpc_get_launch_info", C.c_int, [C.c_void_p, C.POINTER(LaunchInfo)]),
     ("alore_nmpc_set_timing", C.c_int, [C.c_void_p, C.c_int]),
+    # include/alore_ltv_mpc.h: the converged LTV-MPC calls (the rest of that header is bound in ltv_mpc._bind)
+    ("alore_ltv_get_cmd_converge", C.c_int, [C.c_void_p, C.c_int, DP, C.c_int, C.c_double, C.c_int, C.c_void_p]),
+    ("alore_ltv_tick_converge", C.c_int, [C.c_void_p, C.c_int, DP, C.c_int, C.c_double, C.c_int, DP, IP, IP, C.c_void_p]),
+    ("alore_ltv_relin_info", C.c_int, [C.c_void_p, C.c_int, IP, DP, C.c_void_p]),
 )
 
 _lib = None

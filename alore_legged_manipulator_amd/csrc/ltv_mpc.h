@@ -37,6 +37,15 @@ struct Dev {
     long long* stamps;   // diagnostic (ALORE_LTV_STAMPS=1): cycles of robot 0 in rollout / backward / forward / rest
 };
 
+// The converged build of the lanes kernel (alore_ltv_get_cmd_converge / _tick_converge) takes this instead; the plain builds
+// keep taking a Dev and never see the extra fields.  n_relin is the cap on the passes (max_relin) here.
+struct DevConv : Dev {
+    double du_th;        // a robot stops after the first pass whose du <= du_th (validated on the host: finite, >= 0)
+    int* relin_iters;    // [B] passes taken; -max_relin: threshold never met; 0: non-finite input
+    double* du;          // [B] du of the robot's last executed pass
+    int* iters_host;     // optional, with cmd_host: relin_iters straight into pinned host memory
+};
+
 // status of a robot (alore_ltv_results / _commands / _tick): 0 solved, 1 sweep cap reached, 2 a measured state, reference or
 // stored previous output of the robot is NaN or Inf -- nothing is solved for it, its command is zero, its stored state stays
 constexpr int STATUS_OK = 0, STATUS_SWEEP_CAP = 1, STATUS_NON_FINITE = 2;
@@ -52,6 +61,8 @@ __host__ __device__ inline bool non_finite_at(const double* p)
 
 // enqueue getCmd for d.B robots (lanes kernel unless thread_kernel); raises the LDS limit of the long-horizon build once
 hipError_t launch_get_cmd(const Dev& d, bool thread_kernel, hipStream_t s);
+// the same for the converged build (always the lanes kernel)
+hipError_t launch_get_cmd_converge(const DevConv& d, hipStream_t s);
 
 } // namespace ltv
 #endif

@@ -439,8 +439,18 @@ __device__ __forceinline__ double pivot_rcp_d(double x)
         d.stamps[i] += now_ - d.stamps[7];                                                   \
         d.stamps[7] = now_;                                                                  \
     }
-template <int S>
-__global__ __launch_bounds__(64) void get_cmd_lanes_kernel(Dev d)
+//
+// CONV (alore_ltv_get_cmd_converge): the reference's own stopping rule, P:581-584 -- after every pass
+// du = sum over the T output columns of |change of v| + |change of omega|, stop once du <= du_threshold (P:584, commented out
+// there in favour of the wall clock; du_threshold / max_iter are still read from mpc3ms.yaml).  Per robot: the output a pass
+// starts from is parked in the two spare doubles per robot that pad every stage record in LDS, du is summed over the 16 lanes
+// after the pass, and a robot whose du met the threshold is FINISHED: it takes no further part in `act`, the predicate that
+// already guards every update of ua / uw / st / the records / sweeps while a robot waits for the sweeps of its wavefront
+// mates, so its state is frozen by the same selects.  Its lanes keep running the sweeps of the others (no heavy code under a
+// partial EXEC mask, see below) -- what is saved is whole passes: the wavefront leaves the loop once its four robots are
+// finished, so its time follows the slowest of the four.
+template <int S, bool CONV = false>
+__global__ __launch_bounds__(64) void get_cmd_lanes_kernel(std::conditional_t<CONV, DevConv, Dev> d)
 {
     constexpr int L = 16, G = 4;
     (void)L;
@@ -512,6 +522,12 @@ __global__ __launch_bounds__(64) void get_cmd_lanes_kernel(Dev d)
     auto REC = [&](int k_, int f) -> double& { return lds_rec[(size_t)k_ * REC_STRIDE + f * 4 + g]; };
     int sweeps = 0, status = 0;
     double pos0[3] = {0.0, 0.0, 0.0};
+    // CONV: finished (uniform over the robot's 16 lanes; a non-finite robot from the start), passes taken, the sweeps of the last
+    // pass it took part in, du of that pass.  Dead in the plain builds.
+    static_assert(REC_STRIDE >= (NF + 2) * 4, "the output a pass starts from is parked in the padding of the stage records");
+    [[maybe_unused]] bool fin = poisoned;
+    [[maybe_unused]] int iters = poisoned ? 0 : -d.n_relin, sweeps_kept = 0;
+    [[maybe_unused]] double du_last = 0.0;
     if (d.stamps && blockIdx.x == 0 && lane == 0) d.stamps[7] = (long long)__builtin_readcyclecounter();
 
     for (int relin = 0; relin < d.n_relin; ++relin) {
@@ -528,6 +544,11 @@ __global__ __launch_bounds__(64) void get_cmd_lanes_kernel(Dev d)
             px += a * cs * dt; py += a * sn * dt; pth += yd * dt; pv = a;
         }
         pos0[0] = px; pos0[1] = py; pos0[2] = pth;
+        if constexpr (CONV) { // the output this pass starts from, for du: each lane parks and later re-reads its own stages
+#pragma unroll
+            for (int s = 0; s < S; ++s)
+                if (j * S + s < K) { REC(j * S + s, NF) = ua[s]; REC(j * S + s, NF + 1) = uw[s]; }
+        }
         {
             // heading entering stage k: exclusive prefix of the clamped yaw rates
             double inc[S], acc = 0.0, hd[S];
@@ -550,7 +571,7 @@ __global__ __launch_bounds__(64) void get_cmd_lanes_kernel(Dev d)
                 const double v_in = (k == 0) ? pv : ((s == 0) ? a_prev_lane : ua[(s > 0) ? s - 1 : 0]);
                 const double B00 = cs[s] * dt, B10 = sn[s] * dt;
                 const double A02 = -B10 * v_in, A12 = B00 * v_in;
-                if (vs) {
+                if (vs && !(CONV && fin)) { // a finished robot keeps the records of its last pass
                     REC(k, 0) = A02; REC(k, 1) = A12; REC(k, 2) = B00; REC(k, 3) = B10; REC(k, 4) = -A02 * hd[s]; REC(k, 5) = -A12 * hd[s];
                 }
             }
@@ -559,8 +580,8 @@ __global__ __launch_bounds__(64) void get_cmd_lanes_kernel(Dev d)
         // ---- working-set iterations
         bool settled = false;
         sweeps = 0;
-        while (__any(!settled && sweeps < c.max_sweeps)) {
-            const bool act = !settled && sweeps < c.max_sweeps;
+        while (__any(!settled && sweeps < c.max_sweeps && !(CONV && fin))) { // a finished robot sits out: frozen by `act`
+            const bool act = !settled && sweeps < c.max_sweeps && !(CONV && fin);
             // backward sweep: cost-to-go V(xi) = 1/2 xi' P xi + p' xi, P symmetric 5 x 5, handed from lane to lane
             double P[5][5], p[5];
 #pragma unroll
@@ -988,7 +1009,27 @@ __global__ __launch_bounds__(64) void get_cmd_lanes_kernel(Dev d)
                 ++sweeps;
             }
         }
-        status = settled ? 0 : 1;
+        status = (CONV && fin) ? status : (settled ? 0 : 1);
+        if constexpr (CONV) {
+            // du of this pass (P:581-583): the lane's stages, plus on the first pass the delayed columns, which change from the
+            // stored output to the delay buffer (both read as zeros after a reset); later passes leave them alone
+            double part = 0.0;
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                const int kc = min(j * S + s, K - 1);
+                const double da = fabs(ua[s] - REC(kc, NF)) + fabs(uw[s] - REC(kc, NF + 1));
+                part += (j * S + s < K) ? da : 0.0;
+            }
+            if (relin == 0 && !zero_hist)
+                for (int i = j; i < 2 * dl; i += 16) part += fabs(bf[i] - out[i]);
+            const double tot = __shfl(rowprefix_d(part), lane | 15); // the row's total, the same bits in its 16 lanes
+            const bool ran = !fin, met = ran && tot <= d.du_th;
+            du_last = ran ? tot : du_last;
+            sweeps_kept = ran ? sweeps : sweeps_kept;
+            iters = met ? relin + 1 : iters;
+            fin = fin || met;
+            if (!__any(!fin)) break; // wavefront-uniform: all four robots (padding groups shadow the last one) are finished
+        }
     }
     // ---- predictMotion(xopt): the linear prediction about the rollout of the final output (see the kernel above for
     //      which rollout the reference uses), by prefix sums; column m of the output drives step m -> m + 1
@@ -1027,8 +1068,17 @@ __global__ __launch_bounds__(64) void get_cmd_lanes_kernel(Dev d)
             double sb_, cb_;
             sincos(bth_k, &sb_, &cb_);
             const double B00 = cb_ * dt, B10 = sb_ * dt, A02 = -B10 * bv_k, A12 = B00 * bv_k;
-            sx += vs ? (A02 * tth_k + B00 * ua[s] - A02 * bth_k) : 0.0;
-            sy += vs ? (A12 * tth_k + B10 * ua[s] - A12 * bth_k) : 0.0;
+            if constexpr (CONV) {
+                // A finished robot must publish the bits the plain build publishes for the same output (tests/test_ltv_converge.py), and
+                // this sum of two products minus a third is the one place of the kernel where the compiler has a choice of which
+                // product to fuse (it chose differently in the two S = 2 builds, 1 ulp in x / y): here the order of the plain builds
+                // is written out -- the input term as a product, then the two heading terms fused onto it
+                sx += vs ? fma(-A02, bth_k, fma(A02, tth_k, B00 * ua[s])) : 0.0;
+                sy += vs ? fma(-A12, bth_k, fma(A12, tth_k, B10 * ua[s])) : 0.0;
+            } else {
+                sx += vs ? (A02 * tth_k + B00 * ua[s] - A02 * bth_k) : 0.0;
+                sy += vs ? (A12 * tth_k + B10 * ua[s] - A12 * bth_k) : 0.0;
+            }
             ix[s] = sx; iy[s] = sy;
             ht[s] = tth_k + dt * uw[s]; // heading after the step
         }
@@ -1053,6 +1103,10 @@ __global__ __launch_bounds__(64) void get_cmd_lanes_kernel(Dev d)
             d.status[b] = STATUS_NON_FINITE;
             d.cmd[2 * b] = 0.0; d.cmd[2 * b + 1] = 0.0;
             if (d.cmd_host) { d.cmd_host[2 * b] = 0.0; d.cmd_host[2 * b + 1] = 0.0; d.status_host[b] = STATUS_NON_FINITE; }
+            if constexpr (CONV) {
+                d.relin_iters[b] = 0; d.du[b] = 0.0;
+                if (d.iters_host) d.iters_host[b] = 0;
+            }
         }
     } else if (valid) {
 #pragma unroll
@@ -1070,10 +1124,14 @@ __global__ __launch_bounds__(64) void get_cmd_lanes_kernel(Dev d)
                 for (int i = 0; i + 1 < dl; ++i) { bf[2 * i] = d.reset ? 0.0 : bf[2 * (i + 1)]; bf[2 * i + 1] = d.reset ? 0.0 : bf[2 * (i + 1) + 1]; }
                 bf[2 * (dl - 1)] = c0; bf[2 * (dl - 1) + 1] = c1;
             }
-            d.sweeps[b] = sweeps;
+            d.sweeps[b] = CONV ? sweeps_kept : sweeps;
             d.status[b] = status;
             d.cmd[2 * b] = c0; d.cmd[2 * b + 1] = c1;
             if (d.cmd_host) { d.cmd_host[2 * b] = c0; d.cmd_host[2 * b + 1] = c1; d.status_host[b] = status; }
+            if constexpr (CONV) {
+                d.relin_iters[b] = iters; d.du[b] = du_last;
+                if (d.iters_host) d.iters_host[b] = iters;
+            }
         }
     }
 }
@@ -1094,6 +1152,24 @@ hipError_t launch_get_cmd(const Dev& d, bool thread_kernel, hipStream_t s)
             raised = true;
         }
         hipLaunchKernelGGL(get_cmd_lanes_kernel<4>, dim3((B + 3) / 4), dim3(64), lds, s, d);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_get_cmd_converge(const DevConv& d, hipStream_t s)
+{
+    const int B = d.B, K = d.c.predict_steps - d.c.delay_num;
+    const size_t lds = ((size_t)K * REC_STRIDE + 16) * sizeof(double);
+    if (K <= 32)
+        hipLaunchKernelGGL((get_cmd_lanes_kernel<2, true>), dim3((B + 3) / 4), dim3(64), lds, s, d);
+    else {
+        static bool raised = false;
+        if (!raised) {
+            const hipError_t e = hipFuncSetAttribute((const void*)get_cmd_lanes_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (64 * REC_STRIDE + 16) * 8);
+            if (e != hipSuccess) return e;
+            raised = true;
+        }
+        hipLaunchKernelGGL((get_cmd_lanes_kernel<4, true>), dim3((B + 3) / 4), dim3(64), lds, s, d);
     }
     return hipGetLastError();
 }

@@ -97,7 +97,8 @@ struct alore_ltv_solver {
     std::string err;
     double *d_now = nullptr, *d_xref = nullptr, *d_dref = nullptr, *d_out = nullptr, *d_buff = nullptr, *d_xopt = nullptr, *d_ws = nullptr,
            *d_est = nullptr, *d_cmd = nullptr;
-    int *d_st = nullptr, *d_sweeps = nullptr, *d_status = nullptr, *d_goal = nullptr;
+    int *d_st = nullptr, *d_sweeps = nullptr, *d_status = nullptr, *d_goal = nullptr, *d_relin = nullptr;
+    double* d_du = nullptr;
     long long* d_stamps = nullptr;
     char* h_stage = nullptr; // pinned
     size_t stage_bytes = 0;
@@ -123,7 +124,7 @@ hipError_t zalloc(T** p, size_t n)
 }
 void lfree(alore_ltv_handle h)
 {
-    void* ptrs[] = {h->d_now, h->d_xref, h->d_dref, h->d_out, h->d_buff, h->d_xopt, h->d_ws, h->d_est, h->d_st, h->d_sweeps, h->d_status, h->d_goal, h->d_cmd};
+    void* ptrs[] = {h->d_now, h->d_xref, h->d_dref, h->d_out, h->d_buff, h->d_xopt, h->d_ws, h->d_est, h->d_st, h->d_sweeps, h->d_status, h->d_goal, h->d_cmd, h->d_relin, h->d_du};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
 }
@@ -172,6 +173,7 @@ int alore_ltv_create(const alore_ltv_config* cfg, int device, int max_robots, al
     A(zalloc(&h->d_buff, B * dl * 2)); A(zalloc(&h->d_xopt, B * (T + 1) * 3)); A(zalloc(&h->d_ws, T * ltv::NF * B)); A(zalloc(&h->d_est, B * 3));
     if (std::getenv("ALORE_LTV_STAMPS")) A(zalloc(&h->d_stamps, (size_t)8));
     A(zalloc(&h->d_st, T * 2 * B)); A(zalloc(&h->d_sweeps, B)); A(zalloc(&h->d_status, B)); A(zalloc(&h->d_goal, B)); A(zalloc(&h->d_cmd, B * 2));
+    A(zalloc(&h->d_relin, B)); A(zalloc(&h->d_du, B));
     h->stage_bytes = sizeof(double) * B * ((T + 1) * 3 + T * 5 + 8) + sizeof(int) * B * 4 + 1024;
     if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_stage, h->stage_bytes, hipHostMallocDefault);
     if (e != hipSuccess) { lfree(h); delete h; return e == hipErrorOutOfMemory ? ALORE_LTV_E_NOMEM : ALORE_LTV_E_HIP; }
@@ -234,15 +236,16 @@ int alore_ltv_refs_from_store(alore_ltv_handle h, void* nmpc, int B, double now,
     return ALORE_LTV_OK;
 }
 
+// du_th: null for the fixed count; else the converged build (n_relin is its cap), which is always the lanes kernel
 static int ltv_enqueue(alore_ltv_handle h, int B, const double* now_state, int n_relin, int reset, hipStream_t s,
-                       double* cmd_host = nullptr, int* status_host = nullptr)
+                       double* cmd_host = nullptr, int* status_host = nullptr, const double* du_th = nullptr, int* iters_host = nullptr)
 {
     double* hn = (double*)h->h_stage;
     std::memcpy(hn, now_state, sizeof(double) * B * 3);
-    ltv::Dev d{};
+    ltv::DevConv d{};
     d.c = h->cfg; d.B = B; d.stride = h->B;
     static const char* which = std::getenv("ALORE_LTV_KERNEL");
-    const bool thread_kernel = which && which[0] == 't';
+    const bool thread_kernel = !du_th && which && which[0] == 't';
     if (cmd_host && !thread_kernel) { // tick path: the lanes kernel reads the states once, straight from the pinned slab
         void* dn = nullptr;
         LTV_TRY(h, hipHostGetDevicePointer(&dn, hn, 0));
@@ -258,6 +261,11 @@ static int ltv_enqueue(alore_ltv_handle h, int B, const double* now_state, int n
     d.stamps = h->d_stamps;
     // 16 lanes per robot (stages in registers, sweeps lane by lane) unless ALORE_LTV_KERNEL=thread asks for the
     // one-thread-per-robot kernel (diagnostic A/B)
+    if (du_th) {
+        d.du_th = *du_th; d.relin_iters = h->d_relin; d.du = h->d_du; d.iters_host = iters_host;
+        LTV_TRY(h, ltv::launch_get_cmd_converge(d, s));
+        return ALORE_LTV_OK;
+    }
     LTV_TRY(h, ltv::launch_get_cmd(d, thread_kernel, s));
     return ALORE_LTV_OK;
 }
@@ -291,6 +299,68 @@ int alore_ltv_tick(alore_ltv_handle h, int B, const double* now_state, int n_rel
     LTV_TRY(h, hipStreamSynchronize(s));
     std::memcpy(cmd, sc, sizeof(double) * B * 2);
     if (status) std::memcpy(status, st, sizeof(int) * B);
+    return ALORE_LTV_OK;
+}
+
+// The stopping rule's arguments.  Here, not in the kernel: ltv_mpc.hip is built without NaN / Inf semantics.
+static const char* converge_args_bad(int max_relin, double du_th)
+{
+    if (max_relin < 1) return "max_relin must be at least 1";
+    if (std::isnan(du_th)) return "du_th is NaN";
+    if (du_th < 0.0) return "du_th must not be negative";
+    return nullptr;
+}
+
+int alore_ltv_get_cmd_converge(alore_ltv_handle h, int B, const double* now_state, int max_relin, double du_th, int reset, void* stream)
+{
+    if (!h || B < 1 || B > h->B || !now_state) return lfail(h, ALORE_LTV_E_INVALID, "get_cmd_converge: bad argument");
+    if (const char* why = converge_args_bad(max_relin, du_th)) return lfail(h, ALORE_LTV_E_INVALID, (std::string("get_cmd_converge: ") + why).c_str());
+    LTV_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (std::isinf(du_th)) du_th = 1.7976931348623157e308; // "always met": the kernel compares finite numbers only
+    const int rc = ltv_enqueue(h, B, now_state, max_relin, reset, s, nullptr, nullptr, &du_th);
+    if (rc != ALORE_LTV_OK) return rc;
+    LTV_TRY(h, hipStreamSynchronize(s)); // the staging slab is reused by the next call
+    return ALORE_LTV_OK;
+}
+
+int alore_ltv_tick_converge(alore_ltv_handle h, int B, const double* now_state, int max_relin, double du_th, int reset, double* cmd, int* status,
+                            int* relin_iters, void* stream)
+{
+    if (!h || B < 1 || B > h->B || !now_state || !cmd) return lfail(h, ALORE_LTV_E_INVALID, "tick_converge: bad argument");
+    if (const char* why = converge_args_bad(max_relin, du_th)) return lfail(h, ALORE_LTV_E_INVALID, (std::string("tick_converge: ") + why).c_str());
+    LTV_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (std::isinf(du_th)) du_th = 1.7976931348623157e308;
+    // as alore_ltv_tick: commands, status and the pass counts land in the pinned slab, behind the states
+    double* sc = (double*)h->h_stage + (size_t)B * 3;
+    int* st = (int*)(sc + (size_t)B * 2);
+    int* it = st + B;
+    void *dsc = nullptr, *dst = nullptr, *dit = nullptr;
+    LTV_TRY(h, hipHostGetDevicePointer(&dsc, sc, 0));
+    LTV_TRY(h, hipHostGetDevicePointer(&dst, st, 0));
+    LTV_TRY(h, hipHostGetDevicePointer(&dit, it, 0));
+    const int rc = ltv_enqueue(h, B, now_state, max_relin, reset, s, (double*)dsc, (int*)dst, &du_th, (int*)dit);
+    if (rc != ALORE_LTV_OK) return rc;
+    LTV_TRY(h, hipStreamSynchronize(s));
+    std::memcpy(cmd, sc, sizeof(double) * B * 2);
+    if (status) std::memcpy(status, st, sizeof(int) * B);
+    if (relin_iters) std::memcpy(relin_iters, it, sizeof(int) * B);
+    return ALORE_LTV_OK;
+}
+
+int alore_ltv_relin_info(alore_ltv_handle h, int B, int* relin_iters, double* du, void* stream)
+{
+    if (!h || B < 1 || B > h->B) return lfail(h, ALORE_LTV_E_INVALID, "relin_info: bad argument");
+    LTV_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    double* sd = (double*)h->h_stage;
+    int* si = (int*)(sd + (size_t)B);
+    if (du) LTV_TRY(h, hipMemcpyAsync(sd, h->d_du, sizeof(double) * B, hipMemcpyDeviceToHost, s));
+    if (relin_iters) LTV_TRY(h, hipMemcpyAsync(si, h->d_relin, sizeof(int) * B, hipMemcpyDeviceToHost, s));
+    LTV_TRY(h, hipStreamSynchronize(s));
+    if (du) std::memcpy(du, sd, sizeof(double) * B);
+    if (relin_iters) std::memcpy(relin_iters, si, sizeof(int) * B);
     return ALORE_LTV_OK;
 }
 

@@ -120,3 +120,31 @@ class BatchedLtvMpc:
         sw = np.zeros(n, np.int32); st = np.zeros(n, np.int32)
         self._check(self.L.alore_ltv_results(self.h, n, _dp(out), _dp(xopt), sw.ctypes.data_as(IP), st.ctypes.data_as(IP), None))
         return {"output": out, "cmd": out[:, self.d].copy(), "xopt": xopt, "sweeps": sw, "status": st}
+
+    def _relin_info(self, n):
+        self.relin_iters = np.zeros(n, np.int32); self.du = np.zeros(n)
+        self._check(self.L.alore_ltv_relin_info(self.h, n, self.relin_iters.ctypes.data_as(IP), _dp(self.du), None))
+
+    def get_cmd_converge(self, now_state, max_relin=150, du_th=0.01, reset=False):
+        """get_cmd with the reference's stopping rule (mpc.cpp:581-584; defaults: max_iter, du_threshold of mpc3ms.yaml): every
+        robot stops after the first pass whose du = sum |change of the output| <= du_th.  Fills self.relin_iters (passes taken,
+        -max_relin: never met, 0: non-finite input) and self.du (du of the last pass); both are in the returned dict too."""
+        now_state = np.ascontiguousarray(now_state, np.float64)
+        n = now_state.shape[0]
+        self._check(self.L.alore_ltv_get_cmd_converge(self.h, n, _dp(now_state), int(max_relin), float(du_th), 1 if reset else 0, None))
+        out = np.zeros((n, self.T, 2)); xopt = np.zeros((n, self.T + 1, 3))
+        sw = np.zeros(n, np.int32); st = np.zeros(n, np.int32)
+        self._check(self.L.alore_ltv_results(self.h, n, _dp(out), _dp(xopt), sw.ctypes.data_as(IP), st.ctypes.data_as(IP), None))
+        self._relin_info(n)
+        return {"output": out, "cmd": out[:, self.d].copy(), "xopt": xopt, "sweeps": sw, "status": st,
+                "relin_iters": self.relin_iters, "du": self.du}
+
+    def tick_converge(self, now_state, max_relin=150, du_th=0.01, reset=False):
+        """tick with the stopping rule of get_cmd_converge: cmd (n, 2), status, relin_iters; self.du is fetched as well"""
+        now_state = np.ascontiguousarray(now_state, np.float64)
+        n = now_state.shape[0]
+        cmd = np.zeros((n, 2)); st = np.zeros(n, np.int32); it = np.zeros(n, np.int32)
+        self._check(self.L.alore_ltv_tick_converge(self.h, n, _dp(now_state), int(max_relin), float(du_th), 1 if reset else 0, _dp(cmd),
+                                                   st.ctypes.data_as(IP), it.ctypes.data_as(IP), None))
+        self._relin_info(n)
+        return cmd, st, it

@@ -12,7 +12,8 @@
  * equality-constrained problem is one backward / forward sweep over the stages (state augmented by the previous
  * input, so that rate terms and rate limits are stage-local); multipliers and violations update the guess until
  * it reproduces itself (4 - 25 sweeps cold, 1 - 3 warm).  The reference stops its relinearisation loop on a 9.7 ms
- * wall clock, i.e. after a machine-dependent number of passes; here the count is an argument.
+ * wall clock, i.e. after a machine-dependent number of passes; here the count is an argument (alore_ltv_get_cmd), or the
+ * loop stops per robot on the reference's du_threshold rule (alore_ltv_get_cmd_converge).
  * Parity: the QP arithmetic of the reference lives in OSQP (external, un-vendored, version unpinned): PARITY
  * UNPINNED; checked against an independent dense solve of the same matrices (oracle/ltv_mpc_oracle.py).
  */
@@ -72,6 +73,27 @@ int alore_ltv_commands(alore_ltv_handle h, int B, double *cmd, int *status, void
  * out -- one upload, one launch, one download, one wait on the stream */
 int alore_ltv_tick(alore_ltv_handle h, int B, const double *now_state, int n_relin, int reset, double *cmd, int *status,
                    void *stream);
+
+/* getCmd with the reference's own stopping rule instead of a fixed count.  After every pass of its loop the reference forms
+ *   du = sum_i |output(0,i) - last_output(0,i)| + |output(1,i) - last_output(1,i)|     (mpc.cpp:581-583, all T columns)
+ * and the rule `du <= du_th` stands next to it, commented out in favour of the 9.7 ms wall clock (mpc.cpp:584); its two
+ * parameters are still read: du_threshold 0.01 and max_iter 150 (mpc_controller/config/mpc3ms.yaml:2,4).  Here every robot
+ * runs at most max_relin passes and is finished after the first pass k (counted from 1) with du_k <= du_th: its output,
+ * working set, sweeps and status are frozen there, and everything a call leaves behind (the stored output, xopt, the delay
+ * buffer, the command) is what alore_ltv_get_cmd with n_relin = k leaves for that robot.  The first delay_num columns count
+ * in du: on the first pass they change from the stored output to the delay buffer (both zero after reset = 1), later not.
+ * Four robots share a wavefront, which leaves the loop when all four are finished: the time of a call follows the slowest
+ * robot of each wavefront, not the mean.  A robot with a non-finite input (status 2) is not solved: relin_iters 0, du 0.
+ * max_relin < 1, du_th < 0 or du_th NaN: ALORE_LTV_E_INVALID.  du_th = 0 is allowed and stops only on an exactly repeated
+ * output.  Always the 16-lanes-per-robot kernel.  Asynchrony as alore_ltv_get_cmd / alore_ltv_tick. */
+int alore_ltv_get_cmd_converge(alore_ltv_handle h, int B, const double *now_state, int max_relin, double du_th, int reset, void *stream);
+/* one control tick with that rule: as alore_ltv_tick, plus relin_iters HOST [B] or NULL.  Synchronises the stream. */
+int alore_ltv_tick_converge(alore_ltv_handle h, int B, const double *now_state, int max_relin, double du_th, int reset,
+                            double *cmd, int *status, int *relin_iters, void *stream);
+/* what the last converged call took, HOST pointers, either may be NULL: relin_iters [B] = k, or -max_relin when the threshold
+ * was never met (the robot ran all max_relin passes); du [B] = du of the robot's last executed pass.  Synchronises the stream. */
+int alore_ltv_relin_info(alore_ltv_handle h, int B, int *relin_iters, double *du, void *stream);
+
 /* overwrite the stored previous output / delay buffer (tests): output [B][T][2], buff [B][d][2] */
 int alore_ltv_set_state(alore_ltv_handle h, int B, const double *output, const double *buff, void *stream);
 
