@@ -65,6 +65,17 @@ class DeviceView(C.Structure):
                 ("ok", C.c_void_p)]
 
 
+class CheckC(C.Structure):
+    """alore_backend_check (include/alore_backend.h)"""
+    _fields_ = [("collision", C.c_int), ("first_panel", C.c_int), ("n_checked", C.c_int), ("pad", C.c_int),
+                ("first_time", C.c_double), ("first_xy", C.c_double * 2), ("min_dist", C.c_double)]
+
+
+# the same record as a numpy dtype (what check_plans unpacks, and what a copy of the device slab holds)
+CHECK_DTYPE = np.dtype([("collision", np.int32), ("first_panel", np.int32), ("n_checked", np.int32), ("pad", np.int32),
+                        ("first_time", np.float64), ("first_xy", np.float64, 2), ("min_dist", np.float64)])
+
+
 def _bind(L):
     if getattr(L, "_backend_bound", False):
         return
@@ -87,6 +98,8 @@ def _bind(L):
     L.alore_backend_lbfgs.argtypes = [C.c_void_p, C.c_int, C.c_int, DP, DP, DP, C.c_double, C.c_double, C.c_int, DP,
                                       C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), DP, C.c_void_p]
     L.alore_backend_last_plan_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.alore_backend_check_plans.argtypes = [C.c_void_p, C.c_int, DP, DP, C.c_double, C.c_int, C.POINTER(CheckC), C.c_void_p]
+    L.alore_backend_device_check.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L._backend_bound = True
 
 
@@ -169,6 +182,26 @@ class BatchedMSPlanner:
         xy = np.zeros((n, per, 2)); yaw = np.zeros((n, self.P * panels_per_piece)); npts = np.zeros(n, np.int32)
         self._check(self.L.alore_backend_path_points(self.h, n, int(panels_per_piece), _dp(xy), _dp(yaw), npts.ctypes.data_as(C.POINTER(C.c_int))))
         return [(xy[b, :npts[b]].copy(), yaw[b, :(npts[b] // (panels_per_piece + 1)) * panels_per_piece].copy()) for b in range(n)]
+
+    def check_plans(self, t_from=None, t_to=None, min_safe_dis=None, body=False, count=None) -> dict:
+        """The final collision check of the plans of the last launch against the map as it is NOW (set_map / build_esdf since
+        then): per plan, over the panels whose time interval overlaps (t_from[b], t_to[b]) (None: from 0 / to the end), whether
+        one is closer than min_safe_dis (None: the configured final_min_safe_dis) and where the first one is.  body: the
+        minimum over the reference point and the configured body check points instead of the reference point alone."""
+        n = self.count if count is None else int(count)
+        m = max(n, 0)
+        tf = None if t_from is None else np.ascontiguousarray(np.broadcast_to(np.asarray(t_from, np.float64), (m,)))
+        tt = None if t_to is None else np.ascontiguousarray(np.broadcast_to(np.asarray(t_to, np.float64), (m,)))
+        rec = np.zeros(m, CHECK_DTYPE)
+        self._check(self.L.alore_backend_check_plans(self.h, n, _dp(tf), _dp(tt), 0.0 if min_safe_dis is None else float(min_safe_dis),
+                                                     int(bool(body)), rec.ctypes.data_as(C.POINTER(CheckC)), None))
+        return {k: rec[k].copy() for k in ("collision", "first_panel", "n_checked", "first_time", "first_xy", "min_dist")}
+
+    def device_check(self) -> int:
+        """device address of the records of the last check_plans (alore_backend_check[max_problems], CHECK_DTYPE)"""
+        p = C.c_void_p()
+        self._check(self.L.alore_backend_device_check(self.h, C.byref(p)))
+        return p.value
 
     def set_free_map(self, half: float = 40.0, res: float = 0.1, value: float = 100.0):
         n = int(round(2 * half / res))

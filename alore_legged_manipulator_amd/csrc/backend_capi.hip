@@ -1,6 +1,7 @@
 // backend_capi.hip -- implementation of include/alore_backend.h: argument checks, device storage, staging
 // through pinned host memory, launches.  No CPU path: alore_backend_create fails without a GPU.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <string>
@@ -34,6 +35,12 @@ struct alore_backend_planner {
     size_t stage_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
+    // alore_backend_check_plans: the argument block followed by the windows [t_from[count], t_to[count]], pinned and on the
+    // device (one upload per call), and the records of the last check
+    char *h_check = nullptr, *d_check_in = nullptr;
+    alore_backend_check* d_check = nullptr;
+    hipEvent_t ev_check = nullptr, ev_check_done = nullptr; // the upload of the previous call has left h_check; its kernel has ended
+    bool check_pending = false;
 };
 
 namespace {
@@ -73,10 +80,13 @@ void free_all(alore_backend_handle h)
     }
     void* ptrs[] = {h->d_map, h->d_M, h->d_cut, h->d_inner, h->d_initT, h->d_pos, h->d_head, h->d_tail, h->d_sxy, h->d_fxy, h->d_sxyt,
                     h->r_inner, h->r_T, h->r_coef, h->r_tail, h->r_ok, h->r_status, h->d_hist, h->d_gram, h->d_pcr, h->d_x, h->d_g, h->d_lam, h->d_rho,
-                    h->d_cost, h->d_err, h->d_ret, h->d_params, h->d_order};
+                    h->d_cost, h->d_err, h->d_ret, h->d_params, h->d_order, h->d_check_in, h->d_check};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
+    if (h->h_check) (void)hipHostFree(h->h_check);
+    if (h->ev_check) (void)hipEventDestroy(h->ev_check);
+    if (h->ev_check_done) (void)hipEventDestroy(h->ev_check_done);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
 }
@@ -101,6 +111,9 @@ backend::Params base_params(alore_backend_handle h, int count, int mode)
     p.stamps = h->d_stamps;
     return p;
 }
+
+constexpr size_t CHECK_ARGS_BYTES = (sizeof(backend::CheckArgs) + 15) & ~size_t(15);
+size_t check_in_bytes(size_t B) { return CHECK_ARGS_BYTES + sizeof(double) * 2 * B; }
 
 } // namespace
 
@@ -173,6 +186,10 @@ int alore_backend_create(const alore_backend_config* cfg, int device, int max_pi
     if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_stage, h->stage_bytes, hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreate(&h->ev0);
     if (e == hipSuccess) e = hipEventCreate(&h->ev1);
+    A(dalloc(&h->d_check, B)); A(dalloc(&h->d_check_in, check_in_bytes(B)));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_check, check_in_bytes(B), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_check, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_check_done, hipEventDisableTiming);
     if (e != hipSuccess) {
         free_all(h);
         delete h;
@@ -413,6 +430,61 @@ int alore_backend_device_results(alore_backend_handle h, alore_backend_device_vi
     out->tail = h->r_tail;
     out->start_xytheta = h->d_sxyt;
     out->ok = h->r_ok;
+    return ALORE_BE_OK;
+}
+
+int alore_backend_check_plans(alore_backend_handle h, int count, const double* t_from, const double* t_to, double min_safe_dis, int body,
+                              alore_backend_check* out, void* stream)
+{
+    if (!h) return ALORE_BE_E_INVALID;
+    if (count < 1 || count > h->B) return fail(h, ALORE_BE_E_INVALID, "check_plans: count out of range");
+    if (!std::isfinite(min_safe_dis)) return fail(h, ALORE_BE_E_INVALID, "check_plans: min_safe_dis is not finite");
+    if (body && h->cfg.n_check == 0) return fail(h, ALORE_BE_E_INVALID, "check_plans: body check asked for, but the configuration has no check points");
+    if (!h->d_map) return fail(h, ALORE_BE_E_INVALID, "check_plans: no map (alore_backend_set_map / alore_backend_build_esdf)");
+    if (!h->timed || count > h->count) return fail(h, ALORE_BE_E_INVALID, "check_plans: no finished plan for these slots (alore_backend_plan first)");
+    for (int b = 0; b < count; ++b) { // the caller's arrays last: only a call that can run reads them
+        if ((t_from && !std::isfinite(t_from[b])) || (t_to && !std::isfinite(t_to[b]))) return fail(h, ALORE_BE_E_INVALID, "check_plans: a window bound is not finite");
+        if (t_to && t_to[b] < (t_from ? t_from[b] : 0.0)) return fail(h, ALORE_BE_E_INVALID, "check_plans: a window ends before it begins");
+    }
+    BE_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (h->check_pending) {
+        BE_TRY(h, hipEventSynchronize(h->ev_check));         // the pinned block is free again
+        BE_TRY(h, hipStreamWaitEvent(s, h->ev_check_done, 0)); // the previous check (on whatever stream) has read its arguments and written its records
+    }
+    h->check_pending = false;
+    const size_t n = count;
+    double *h_win = (double*)(h->h_check + CHECK_ARGS_BYTES), *d_win = (double*)(h->d_check_in + CHECK_ARGS_BYTES);
+    backend::CheckArgs g{};
+    g.count = count; g.P = h->P; g.R = h->cfg.final_check_num; g.n_check = h->cfg.n_check; g.body = body != 0;
+    g.n_pieces = h->d_M; g.T = h->r_T; g.coef = h->r_coef; g.plan_start_xyt = h->d_sxyt;
+    g.map = h->map;
+    g.t_from = t_from ? d_win : nullptr;
+    g.t_to = t_to ? d_win + n : nullptr;
+    g.min_safe_dis = min_safe_dis > 0.0 ? min_safe_dis : h->cfg.final_min_safe_dis;
+    g.xv = h->cfg.standard_diff ? 0.0 : h->cfg.icr_xv;
+    std::memcpy(g.check_pts, h->cfg.check_pts, sizeof(g.check_pts));
+    g.out = h->d_check;
+    std::memcpy(h->h_check, &g, sizeof(g));
+    if (t_from) std::memcpy(h_win, t_from, sizeof(double) * n);
+    if (t_to) std::memcpy(h_win + n, t_to, sizeof(double) * n);
+    BE_TRY(h, hipMemcpyAsync(h->d_check_in, h->h_check, CHECK_ARGS_BYTES + sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
+    BE_TRY(h, hipEventRecord(h->ev_check, s));
+    h->check_pending = true;
+    BE_TRY(h, backend::check_plans((const backend::CheckArgs*)h->d_check_in, count, s));
+    BE_TRY(h, hipEventRecord(h->ev_check_done, s));
+    if (out) {
+        BE_TRY(h, hipMemcpyAsync(h->h_stage, h->d_check, sizeof(alore_backend_check) * n, hipMemcpyDeviceToHost, s));
+        BE_TRY(h, hipStreamSynchronize(s));
+        std::memcpy(out, h->h_stage, sizeof(alore_backend_check) * n);
+    }
+    return ALORE_BE_OK;
+}
+
+int alore_backend_device_check(alore_backend_handle h, const alore_backend_check** out)
+{
+    if (!h || !out) return fail(h, ALORE_BE_E_INVALID, "device_check: bad argument");
+    *out = h->d_check;
     return ALORE_BE_OK;
 }
 

@@ -79,6 +79,22 @@ size_t lds_bytes(int P);
 // `p` must stay alive until the copy has been issued from pinned memory or has completed (callers keep it in the handle)
 hipError_t launch(const Params& p, const Params* d_params, int P, hipStream_t s);
 
+// the final collision check again, on the stored plans of the last launch against the map of now (backend_kernels.hip:
+// check_plans_kernel): one wavefront per plan, a time window per plan, the threshold an argument, optionally the body points
+struct CheckArgs {
+    int count, P, R, n_check, body;
+    const int* n_pieces;          // [B]
+    const double *T, *coef;       // ResultStore
+    const double* plan_start_xyt; // [B][3]
+    MapView map;
+    const double *t_from, *t_to;  // [count] or null (0, +infinity)
+    double min_safe_dis, xv;      // xv: 0 for the standard differential model
+    double check_pts[8][2];
+    alore_backend_check* out;     // [count]
+};
+// the kernel reads its arguments from d_args (device memory, filled in stream order before the launch)
+hipError_t check_plans(const CheckArgs* d_args, int count, hipStream_t s);
+
 // MSPlanner::get_the_predicted_state[_and_path] on the plans of the last launch (esdf_build.hip)
 struct PredictArgs {
     int count, P;

@@ -1562,4 +1562,102 @@ hipError_t launch(const Params& p, const Params* d_params, int P, hipStream_t s)
     return hipGetLastError();
 }
 
+// The final collision check again (final_collision above: the same panels, nodes, weights and order of additions), on the plans
+// the last launch left in the result slabs and against the map of now.  One wavefront per plan, panels over the lanes in chunks
+// of 64, positions by wave_prefix and a carry from chunk to chunk.  What differs from the optimiser's own check: T and the
+// coefficients come from global memory (the result slabs), a panel counts only if its time interval overlaps the plan's window
+// (panels before the window are still integrated: the position needs them), the threshold is an argument, and a panel's
+// distance may include the body points, placed like the clearance penalty places them (eval_cost: pose-dependent terms).
+// No LDS, no barrier: every exchange is inside the wavefront; every branch around a cross-lane operation is on a ballot.
+__global__ __launch_bounds__(64) void check_plans_kernel(const CheckArgs* __restrict__ gp)
+{
+    typedef const CSTQ CheckArgs CArgs;
+    CArgs& a = *(CArgs*)gp;
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= a.count) return;
+    constexpr double BIG = 1.79769313486231570815e+308;
+    const int P = a.P, R = a.R, M = min(max(uni(a.n_pieces[b]), 0), P), NP = R * M;
+    const GLBQ double* Tg = (const GLBQ double*)a.T + (size_t)b * P;
+    const GLBQ double* cg = (const GLBQ double*)a.coef + (size_t)b * P * 12;
+    const double xvI = a.xv, map_inv = 1.0 / a.map.res, thr = a.min_safe_dis;
+    const double t_from = a.t_from ? a.t_from[b] : 0.0, t_to = a.t_to ? a.t_to[b] : __builtin_inf();
+    const int nq = a.body ? a.n_check : 0;
+    double carry_x = a.plan_start_xyt[(size_t)b * 3], carry_y = a.plan_start_xyt[(size_t)b * 3 + 1], mind = BIG;
+    int first = -1, n_checked = 0;
+    double first_t = -1.0, first_x = 0.0, first_y = 0.0;
+    for (int base = 0; base < NP; base += 64) {
+        const int p = base + lane;
+        double ix = 0.0, iy = 0.0, tau = 0.0, step = 0.0, sy = 0.0, cy = 1.0;
+        if (p < NP) {
+            const int i = p / R, q = p - i * R;
+            const double T = Tg[i], half = T / R / 2.0, cint = T / R / 6.0;
+            const GLBQ double* ci = cg + 12 * i;
+            for (int s = 0; s < 3; ++s) {
+                const double t = (2 * q + s) * half;
+                double sg, d1[2];
+                sg = ((((ci[10] * t + ci[8]) * t + ci[6]) * t + ci[4]) * t + ci[2]) * t + ci[0];
+                for (int d = 0; d < 2; ++d)
+                    d1[d] = (((5.0 * ci[10 + d] * t + 4.0 * ci[8 + d]) * t + 3.0 * ci[6 + d]) * t + 2.0 * ci[4 + d]) * t + ci[2 + d];
+                sincos(sg, &sy, &cy); // after the last node: the heading at the panel's end
+                const double w = (s == 1) ? 4.0 * cint : cint;
+                ix += w * (d1[1] * cy + d1[0] * xvI * sy);
+                iy += w * (d1[1] * sy - d1[0] * xvI * cy);
+            }
+            double t0 = 0.0; // start of piece i, summed in piece order
+            for (int k = 0; k < i; ++k) t0 += Tg[k];
+            step = T / R;
+            tau = t0 + (q + 1) * step;
+        }
+        ix = wave_prefix(ix); iy = wave_prefix(iy);
+        const double px = carry_x + ix, py = carry_y + iy;
+        const bool counted = p < NP && tau > t_from && tau - step < t_to;
+        double dist = BIG;
+        if (counted) {
+            double gx, gy;
+            dist = esdf(a.map, map_inv, px, py, false, 0.0, gx, gy);
+            for (int k = 0; k < nq; ++k) {
+                const double bx = a.check_pts[k][0], by = a.check_pts[k][1];
+                dist = fmin(dist, esdf(a.map, map_inv, px + cy * bx - sy * by, py + sy * bx + cy * by, false, 0.0, gx, gy));
+            }
+        }
+        // the reference stops at its first hit: the minimum and the count cover the counted panels up to and including it
+        const unsigned long long hits = __ballot(counted && dist < thr);
+        const int hit_lane = hits ? __ffsll((long long)hits) - 1 : 64;
+        const bool taken = counted && lane <= hit_lane;
+        n_checked += __popcll(__ballot(taken));
+        double local = taken ? dist : BIG;
+#pragma unroll
+        for (int mm = 32; mm >= 1; mm >>= 1) local = fmin(local, __shfl_xor(local, mm));
+        mind = fmin(mind, local);
+        if (hit_lane < 64) {
+            first = base + hit_lane;
+            first_t = __shfl(tau, hit_lane);
+            first_x = __shfl(px, hit_lane);
+            first_y = __shfl(py, hit_lane);
+            break;
+        }
+        carry_x += __shfl(ix, 63);
+        carry_y += __shfl(iy, 63);
+    }
+    if (lane == 0) {
+        alore_backend_check& o = a.out[b];
+        o.collision = first >= 0 ? 1 : 0;
+        o.first_panel = first;
+        o.n_checked = n_checked;
+        o.pad = 0;
+        o.first_time = first_t;
+        o.first_xy[0] = first_x;
+        o.first_xy[1] = first_y;
+        o.min_dist = mind;
+    }
+}
+
+hipError_t check_plans(const CheckArgs* d_args, int count, hipStream_t s)
+{
+    void* args[] = {&d_args};
+    hipError_t e = hipLaunchKernel((const void*)check_plans_kernel, dim3(count), dim3(64), args, 0, s);
+    if (e != hipSuccess) return e;
+    return hipGetLastError();
+}
+
 } // namespace backend

@@ -161,6 +161,34 @@ int alore_backend_predicted_state(alore_backend_handle h, int count, double reso
  * Synchronises. */
 int alore_backend_path_points(alore_backend_handle h, int count, int panels_per_piece, double *xy, double *yaw, int *n_points);
 
+/* ---- stored plans against the map of now ------------------------------------------------------------- */
+/* MSPlanner::check_final_collision (optimizer.cpp:474-571) again, on the plans of the last alore_backend_plan and the handle's
+ * CURRENT map (alore_backend_set_map / alore_backend_build_esdf since then), one wavefront per plan, nothing but the records below
+ * crosses the bus: what a replanner asks every cycle (plan_manager.hpp:714-727).  The path is integrated from the plan's start
+ * position in final_check_num Simpson panels per piece; panel p = i R + q ends at tau_p = sum_{k<i} T_k + (q + 1) T_i / R and
+ * COUNTS for robot b when its interval (tau_p - T_i / R, tau_p] overlaps the open window (t_from[b], t_to[b]) -- the part of the
+ * plan the robot has not driven yet.  The distance of a panel is the ESDF at the reference point at its end and, with body != 0,
+ * the minimum over that point and the n_check body points placed like the optimiser's clearance penalty places them. */
+typedef struct alore_backend_check {
+    int collision;    /* 1: a counted panel is closer than the threshold */
+    int first_panel;  /* the first such panel, or -1 */
+    int n_checked;    /* counted panels up to and including the first hit (all counted panels without one) */
+    int pad;
+    double first_time;  /* tau of first_panel, or -1 */
+    double first_xy[2]; /* reference point at the end of first_panel, or zeros */
+    double min_dist;    /* over the n_checked panels (the reference stops at its first hit); DBL_MAX when nothing counts */
+} alore_backend_check;
+/* t_from, t_to: HOST arrays [count] or NULL (0 and +infinity); min_safe_dis <= 0: the configured final_min_safe_dis.  The launch
+ * goes on `stream`; with out (HOST, [count]) the records are copied down and the stream is synchronised, with out == NULL nothing
+ * waits and a consumer on the same GPU reads the slab of alore_backend_device_check in stream order.  A slot whose plan the
+ * optimiser rejected is checked like any other (what is stored is its last pass).  A check on another stream than the one before it
+ * starts after that one has ended (the handle keeps one argument block and one slab of records); a consumer of the slab on another
+ * stream, and a map update or a new plan while a check is in flight on another stream, are the caller's to order. */
+int alore_backend_check_plans(alore_backend_handle h, int count, const double *t_from, const double *t_to, double min_safe_dis, int body,
+                              alore_backend_check *out, void *stream);
+/* device slab [max_problems] of the records of the last check; valid until the handle is destroyed */
+int alore_backend_device_check(alore_backend_handle h, const alore_backend_check **out);
+
 #ifdef __cplusplus
 }
 #endif
