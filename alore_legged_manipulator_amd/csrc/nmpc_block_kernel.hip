@@ -22,7 +22,7 @@
 // Builds: DIAG (KKT value and objective wanted), STAMP (phase stamps, diagnostic), ONCE (n_sqp = 1, the control tick: no
 // iteration loop, so od / the raw bounds die after the linearisation and the iterate, WN, yN are read again at the end
 // instead of held -- (4, 5) 435 registers instead of 512 + scratch, (16, 2) 252: two wavefronts per SIMD).
-// Which (L, S) runs: block_geometry() below -- the widest L whose wavefronts, over ALL launches in flight
+// Which (L, S) runs: block_geometry() (nmpc_launch_plan.h) -- the widest L whose wavefronts, over ALL launches in flight
 // (alore_nmpc_rti_many, nmpc_capi.hip), still fit one per SIMD.
 //
 // Numerics are those of nmpc_kernels.hip / nmpc_core.h (see there for the reference citations); per-problem results
@@ -35,6 +35,7 @@
 #include <cstdlib>
 
 #include <type_traits>
+#include <utility>
 
 #include "nmpc_core.h"
 #include "nmpc_scan.h"
@@ -327,13 +328,6 @@ __device__ __forceinline__ bool riccati_step_pk(const StagePk& s, ValuePk& V, Po
 
 } // namespace
 
-// LDS floats of one wavefront: W and y of its 64 / L problems, each area padded to whole 256-float DMA pieces
-int block_lds_floats(int N, int L)
-{
-    const int G = 64 / L;
-    return ((G * 25 * N + 255) & ~255) + ((G * 5 * N + 255) & ~255);
-}
-
 // One grid serves up to GROUP_MAX independent batches (alore_nmpc_rti_many): the descriptors travel by value in the kernel
 // arguments, block -> (batch, block of the batch) by one division.  The pointers of a workgroup's batch are
 // wavefront-uniform (scalar loads from the kernel-argument segment); a single batch is the group of one.
@@ -406,62 +400,44 @@ __global__ __launch_bounds__(64) void rti_block_sampler_kernel(const RtiParamsCo
 #include "nmpc_block_body.inc"
 }
 
-// (L, S) instantiated: (4, 5) (8, 3) (16, 2) (32, 1) for horizons up to 20 / 24 / 32 / 32, (16, 4) up to 64
-bool block_geometry(int B, int N, int forced_L, int lds_limit_bytes, int n_cu, LaunchGeom* g, int B_in_flight)
+// The kernels, in the order of kBlockBuilds / kSamplerBuilds (nmpc_launch_plan.h): made from those tables entry for entry, so the set of
+// instantiations is the tables' and a build's index there is its slot here.  No instantiation is named anywhere else.
+template <size_t... I>
+static const void* const* block_kernels(std::index_sequence<I...>)
 {
-    if (B <= 0 || N <= 0) return false;
-    const int cus = n_cu > 0 ? n_cu : 256;
-    int L = forced_L;
-    if (L == 0) {
-        // the sweeps cost N scalar stage steps per wavefront whatever L is: spread a small batch over all SIMDs
-        // (one wavefront each), pack a large one
-        // (measured, profiles/r03_c_block_kernel_experiments.txt: two wavefronts on a SIMD do not issue faster than one,
-        // so L = 32 only pays while every wavefront still has a CU to itself)
-        // B_in_flight: problems of all launches that run concurrently with this one (alore_nmpc_rti_many) -- what fills
-        // the chip is their sum
-        const long Bo = (B_in_flight > B) ? B_in_flight : B;
-        L = 16;
-        while (L > 4 && (Bo + 64 / L - 1) / (64 / L) > 4L * cus) L >>= 1;
-        while (L < 16 && N > L * (L == 4 ? 5 : 3)) L <<= 1;
-        if (L == 16 && N <= 32 && (Bo + 1) / 2 <= (long)cus) L = 32;
-        // (long horizons -- the reference's N = 50 -- stay on (16, 4): 8 lanes x 7 stages with W_k in registers instead of LDS was built in
-        // round 6 and spills 880 registers: 49.6 against 35 us per batch in flight; what took (16, 4) to 26 us is the scan of nmpc_scan.h)
+    static const void* const table[] = {(const void*)rti_block_kernel<kBlockBuilds[I].L, kBlockBuilds[I].S, kBlockBuilds[I].DIAG, kBlockBuilds[I].STAMP, kBlockBuilds[I].ONCE,
+                                                                      kBlockBuilds[I].FULLN, kBlockBuilds[I].TRACE, kBlockBuilds[I].PERSIST, kBlockBuilds[I].TWOPH,
+                                                                      kBlockBuilds[I].CONV>...};
+    return table;
+}
+template <size_t... I>
+static const void* const* sampler_kernels(std::index_sequence<I...>)
+{
+    static const void* const table[] = {(const void*)rti_block_sampler_kernel<kSamplerBuilds[I].L, kSamplerBuilds[I].S, kSamplerBuilds[I].DIAG>...};
+    return table;
+}
+
+// dynamic LDS of a build, raised once per (device, build) to the largest request seen
+template <int BUILDS>
+static hipError_t configure_lds(const void* fn, int build, size_t lds_bytes)
+{
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    dev &= 15;
+    static size_t configured[16][BUILDS] = {{0}};
+    if (lds_bytes > configured[dev][build]) {
+        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e != hipSuccess) return e;
+        configured[dev][build] = lds_bytes;
     }
-    int S = 0;
-    if (L == 4 && N <= 20) S = 5;
-    else if (L == 8 && N <= 24) S = 3;
-    else if (L == 16 && N <= 32) S = 2;
-    else if (L == 16 && N <= 64) S = 4;
-    else if (L == 32 && N <= 32) S = 1;
-    if (S == 0) return false;
-    const size_t lds = (size_t)block_lds_floats(N, L) * 4;
-    if ((long)lds > lds_limit_bytes) return false;
-    g->L = L;
-    g->G = 64 / L;
-    g->wpb = 1;
-    g->wreg = 0;
-    g->threads = 64;
-    g->grid = (B + g->G - 1) / g->G;
-    g->RS = S; // stages per lane
-    g->lds_bytes = lds;
-    g->block = 1;
-    return true;
+    return hipSuccess;
 }
 
 hipError_t launch_rti_block(const RtiParams& p, const LaunchGeom& g, hipStream_t s)
 {
     RtiGroup grp;
-    grp.count = 1;
     grp.blocks_per_batch = g.grid;
-    grp.strided = 0;
-    grp.stagger_blocks = 0;
-    grp.stagger_x1024 = 0;
-    grp.trace = nullptr;
-    grp.counter = nullptr;
-    grp.persist_blocks = 0;
-    grp.xcd_on = 0;
-    grp.xcd_end = nullptr;
-    grp.tp_count2 = 0; grp.tp_tail = 0; grp.tp_lag = 0; grp.tp_timeout = 0; grp.tp_exits = nullptr; grp.tp_cnt = nullptr; grp.tp_entries = nullptr; grp.tp_trace = nullptr; grp.tp_rec = nullptr;
     grp.b[0] = p.b;
     return launch_rti_block_group(p, grp, g, s);
 }
@@ -472,80 +448,21 @@ hipError_t launch_rti_block_group(const RtiParams& p, const RtiGroup& grp, const
 {
     if (grp.count < 1 || (!grp.strided && grp.count > GROUP_MAX) || grp.blocks_per_batch != g.grid) return hipErrorInvalidValue;
     if ((long long)g.grid * grp.count > 0x7fffffffLL) return hipErrorInvalidValue;
-    const bool stamp = p.stamps != nullptr;
-    const bool diag = stamp || grp.b[0].kkt != nullptr || grp.b[0].obj != nullptr;
-    const bool conv = p.kkt_tol >= 0.0f; // converged solve: the CONV builds (a launch of one iteration too)
-    if (conv && (stamp || grp.counter != nullptr || grp.tp_count2 > 0 || grp.trace)) return hipErrorInvalidValue;
-    const bool once = p.n_sqp == 1 && !conv;
-    const void* fn = nullptr;
-    int v = -1;
-#define PICK(LL, SS, idx)                                                                                 \
-    if (g.L == LL && g.RS == SS) {                                                                        \
-        v = idx * 5 + (stamp ? 4 : ((diag ? 0 : 1) + (once ? 2 : 0)));                                    \
-        fn = stamp ? (const void*)rti_block_kernel<LL, SS, true, true, false>                             \
-                   : (diag ? (once ? (const void*)rti_block_kernel<LL, SS, true, false, true>             \
-                                   : (const void*)rti_block_kernel<LL, SS, true, false, false>)           \
-                           : (once ? (const void*)rti_block_kernel<LL, SS, false, false, true>            \
-                                   : (const void*)rti_block_kernel<LL, SS, false, false, false>));        \
-    }
-    PICK(4, 5, 0)
-    PICK(8, 3, 1)
-    PICK(16, 2, 2)
-    PICK(16, 4, 3)
-    PICK(32, 1, 4)
-#undef PICK
-#define PICK_CONV(LL, SS, idx)                                                                            \
-    if (g.L == LL && g.RS == SS) {                                                                        \
-        v = 35 + idx;                                                                                     \
-        fn = (const void*)rti_block_kernel<LL, SS, true, false, false, false, false, false, false, true>; \
-    }
-    if (conv) {
-        fn = nullptr;
-        PICK_CONV(4, 5, 0)
-        PICK_CONV(8, 3, 1)
-        PICK_CONV(16, 2, 2)
-        PICK_CONV(16, 4, 3)
-        PICK_CONV(32, 1, 4)
-    }
-#undef PICK_CONV
-    if (g.L == 4 && g.RS == 5 && p.N == 20 && once && !stamp) { // the control tick at the horizon that fills the (4, 5) mapping
-        v = 25 + (diag ? 0 : 1);
-        fn = diag ? (const void*)rti_block_kernel<4, 5, true, false, true, true> : (const void*)rti_block_kernel<4, 5, false, false, true, true>;
-    }
-    if (g.L == 4 && g.RS == 5 && p.N == 20 && !once && !stamp) { // several iterations per launch (converged solves) at the horizon that fills the mapping
-        v = conv ? 40 : 33 + (diag ? 0 : 1);
-        fn = conv   ? (const void*)rti_block_kernel<4, 5, true, false, false, true, false, false, false, true>
-             : diag ? (const void*)rti_block_kernel<4, 5, true, false, false, true> : (const void*)rti_block_kernel<4, 5, false, false, false, true>;
-    }
-    const bool persist = grp.counter != nullptr;
-    if (persist) {
-        if (!(g.L == 4 && g.RS == 5 && p.N == 20 && once && !stamp)) return hipErrorInvalidValue;
-        v = 28 + (diag ? 0 : 1);
-        fn = diag ? (const void*)rti_block_kernel<4, 5, true, false, true, true, false, true> : (const void*)rti_block_kernel<4, 5, false, false, true, true, false, true>;
-    }
-    const bool twoph = grp.tp_count2 > 0;
-    if (twoph) {
-        if (!(g.L == 4 && g.RS == 5 && p.N == 20 && once && !stamp) || persist || grp.trace || grp.xcd_on) return hipErrorInvalidValue;
-        v = 31 + (diag ? 0 : 1);
-        fn = diag ? (const void*)rti_block_kernel<4, 5, true, false, true, true, false, false, true> : (const void*)rti_block_kernel<4, 5, false, false, true, true, false, false, true>;
-    }
-    if (grp.trace) { // diagnostic: only the grid builds have an instrumented twin
-        if (!(g.L == 4 && g.RS == 5 && p.N == 20 && once && !stamp && diag)) return hipErrorInvalidValue;
-        v = persist ? 30 : 27;
-        fn = persist ? (const void*)rti_block_kernel<4, 5, true, false, true, true, true, true> : (const void*)rti_block_kernel<4, 5, true, false, true, true, true>;
-    }
-    if (!fn) return hipErrorInvalidValue;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    dev &= 15;
+    const bool persist = grp.counter != nullptr, twoph = grp.tp_count2 > 0;
+    BlockBuildRequest want = {g.L, g.RS, p.N, p.n_sqp};
+    want.diag = grp.b[0].kkt != nullptr || grp.b[0].obj != nullptr;
+    want.stamp = p.stamps != nullptr;
+    want.conv = p.kkt_tol >= 0.0f;
+    want.persist = persist;
+    want.twoph = twoph;
+    want.trace = grp.trace != nullptr;
+    want.xcd_shares = grp.xcd_on != 0;
+    const int build = select_block_build(want);
+    if (build < 0) return hipErrorInvalidValue;
+    const void* fn = block_kernels(std::make_index_sequence<kNumBlockBuilds>())[build];
     const size_t lds_bytes = g.lds_bytes;
-    static size_t configured[16][41] = {{0}};
-    if (lds_bytes > configured[dev][v]) {
-        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        configured[dev][v] = lds_bytes;
-    }
+    hipError_t e = configure_lds<kNumBlockBuilds>(fn, build, lds_bytes);
+    if (e != hipSuccess) return e;
     void* args[] = {const_cast<RtiParams*>(&p), const_cast<RtiGroup*>(&grp)};
     unsigned blocks = (unsigned)g.grid * (unsigned)grp.count;
     if (persist && blocks > (unsigned)grp.persist_blocks) blocks = (unsigned)grp.persist_blocks;
@@ -554,9 +471,8 @@ hipError_t launch_rti_block_group(const RtiParams& p, const RtiGroup& grp, const
         for (int x = 0; x < 8; ++x) mx = grp.xcd_share[x] > mx ? grp.xcd_share[x] : mx;
         blocks = 8u * (unsigned)mx;
     }
-    if (twoph) { // units of (blocks of a batch, tail of the batch tp_lag units before): see nmpc_block_body.inc
-        const long long units = std::max((long long)grp.count, (long long)grp.tp_count2 + grp.tp_lag);
-        const long long nb = units * ((long long)g.grid + grp.tp_tail);
+    if (twoph) {
+        const long long nb = two_phase_blocks(grp.count, grp.tp_count2, grp.tp_lag, g.grid, grp.tp_tail);
         if (nb > 0x7fffffffLL) return hipErrorInvalidValue;
         blocks = (unsigned)nb;
     }
@@ -565,56 +481,20 @@ hipError_t launch_rti_block_group(const RtiParams& p, const RtiGroup& grp, const
     return hipGetLastError();
 }
 
-bool rti_block_two_phase_supported(const RtiParams& p, const LaunchGeom& g)
-{
-    return g.block && g.L == 4 && g.RS == 5 && p.N == 20 && p.n_sqp == 1 && p.stamps == nullptr && g.grid <= 64 * TP_KMAX;
-}
-
-// The solve of one batch with the sampler's workgroups behind it in the same grid; false when this (mapping, mode) has no such build
-// (the caller then launches the two kernels one after the other)
-// 2: the sampler's workgroups run beside the solver's (builds of at most 256 registers: a SIMD holds one wavefront of each); 1: the
-// grid carries the plant step only (the (8, 3) build takes 303 registers: the sampler's wavefronts would queue behind the solver's
-// with one slot per SIMD -- as a kernel of its own the sampler has eight); 0: neither
-int rti_block_sampler_supported(const RtiParams& p, const LaunchGeom& g)
-{
-    if (!(g.block && p.n_sqp == 1 && p.stamps == nullptr && p.N + 1 <= 32)) return 0;
-    if ((g.L == 16 && g.RS == 2) || (g.L == 32 && g.RS == 1)) return 2;
-    if (g.L == 8 && g.RS == 3) return 1;
-    return 0;
-}
+// The solve of one batch with the sampler's workgroups behind it in the same grid; hipErrorInvalidValue when this (mapping, mode) has no
+// such build (rti_block_sampler_supported: the caller then launches the two kernels one after the other)
 hipError_t launch_rti_block_sampler(const RtiParams& p, const LaunchGeom& g, const AheadSampler& sa_in, const PlantAhead* plant, hipStream_t s)
 {
     const int kind = rti_block_sampler_supported(p, g);
     if (kind == 0 || (kind == 1 && sa_in.B > 0)) return hipErrorInvalidValue;
     RtiGroup grp;
-    grp.count = 1;
     grp.blocks_per_batch = g.grid;
-    grp.strided = 0;
-    grp.stagger_blocks = 0;
-    grp.stagger_x1024 = 0;
-    grp.trace = nullptr;
-    grp.counter = nullptr;
-    grp.persist_blocks = 0;
-    grp.xcd_on = 0;
-    grp.xcd_end = nullptr;
-    grp.tp_count2 = 0; grp.tp_tail = 0; grp.tp_lag = 0; grp.tp_timeout = 0; grp.tp_exits = nullptr; grp.tp_cnt = nullptr; grp.tp_entries = nullptr; grp.tp_trace = nullptr; grp.tp_rec = nullptr;
-    for (int m = 0; m < 15; ++m) grp.stride[m] = 0;
     grp.b[0] = p.b;
-    const bool diag = p.b.kkt != nullptr || p.b.obj != nullptr;
-    const int v = (g.L == 16 ? 0 : (g.L == 32 ? 2 : 4)) + (diag ? 0 : 1);
-    const void* fn = g.L == 16 ? (diag ? (const void*)rti_block_sampler_kernel<16, 2, true> : (const void*)rti_block_sampler_kernel<16, 2, false>)
-                   : g.L == 32 ? (diag ? (const void*)rti_block_sampler_kernel<32, 1, true> : (const void*)rti_block_sampler_kernel<32, 1, false>)
-                               : (diag ? (const void*)rti_block_sampler_kernel<8, 3, true> : (const void*)rti_block_sampler_kernel<8, 3, false>);
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const int build = select_sampler_build(g, p.N, p.n_sqp, p.stamps != nullptr, p.b.kkt != nullptr || p.b.obj != nullptr);
+    if (build < 0) return hipErrorInvalidValue;
+    const void* fn = sampler_kernels(std::make_index_sequence<kNumSamplerBuilds>())[build];
+    hipError_t e = configure_lds<kNumSamplerBuilds>(fn, build, g.lds_bytes);
     if (e != hipSuccess) return e;
-    dev &= 15;
-    static size_t configured[16][6] = {{0}};
-    if (g.lds_bytes > configured[dev][v]) {
-        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds_bytes);
-        if (e != hipSuccess) return e;
-        configured[dev][v] = g.lds_bytes;
-    }
     AheadSampler sa = sa_in;
     sa.first_block = g.grid;
     PlantAhead pl{};

@@ -2,9 +2,13 @@
 #ifndef ALORE_NMPC_KERNELS_H
 #define ALORE_NMPC_KERNELS_H
 
+#include <cstddef>
+#include <type_traits>
+
 #include <hip/hip_runtime.h>
 
 #include "../../include/alore_nmpc.h"
+#include "nmpc_launch_plan.h" // LaunchGeom, block_lds_floats, block_geometry, TP_KMAX: everything of a launch that is decided without a GPU
 
 namespace nmpc {
 
@@ -36,52 +40,43 @@ static_assert(sizeof(RtiParams) == sizeof(RtiParamsCore) + 16, "RtiParams: the e
 
 // up to GROUP_MAX independent batches served by one grid of the stage-block kernel (by value in the kernel arguments: 24 x 120 B of the 4 KB they hold)
 constexpr int GROUP_MAX = 24;
-constexpr int TP_KMAX = 16; // two-phase grids: a tail workgroup reads the reports of its batch's blocks, up to 64 * TP_KMAX of them
 // Queue of a two-phase grid, per batch (all words 0 between launches): `cnt[block]` = 1 + problems the first-pass workgroup of that block
 // left to the tail (0: it has not reported yet), `entries[block * G + i]` = 1 + number of its i-th such problem (0: not written yet; the
 // tail workgroup that takes an entry puts it back to 0), `exits` = tail workgroups of the batch that have left (the last one puts
 // cnt[] and itself back to 0).  The first pass only stores -- no read-modify-write on a word that the other workgroups of the batch
 // hit as well (one returning add per workgroup on a per-batch counter made the whole grid wait for that word: 170 against 130 us).
+// A default-constructed RtiGroup is one batch in a plain grid: callers set only what they mean.
 struct RtiGroup {
-    int count;            // batches in this launch
-    int blocks_per_batch; // workgroups per batch: block -> batch by division
-    int stagger_blocks;   // the first stagger_blocks workgroups (one full residency of the chip) delay their start by
-    int stagger_x1024;    // blockIdx * stagger_x1024 / 1024 ticks of the 100 MHz real-time counter (0: no stagger), see the kernel
-    int strided;          // 1: batch i = b[0] with every member pointer advanced by i * stride[member] bytes (any count);
-                          // 0: batch i = b[i] (count <= GROUP_MAX)
-    long long* trace;     // diagnostic (ALORE_NMPC_TRACE): 8 words per workgroup, see the kernel; else null
-    int* counter;         // persistent grid: [0] tickets handed out, [1] workgroups that have left (both 0 between launches); else null
-    int persist_blocks;   // persistent grid: workgroups launched (one per SIMD slot); items beyond them are taken by ticket
-    int xcd_on;           // 1: XCD x (workgroups w = x mod 8) works on xcd_share[x] consecutive blocks from xcd_base[x] (see the kernel)
-    int xcd_share[8], xcd_base[8];
-    unsigned long long* xcd_end; // [8][4] host memory: finishing times (100 MHz counter) of the last four workgroups of every XCD, or null
+    int count = 1;            // batches in this launch
+    int blocks_per_batch = 0; // workgroups per batch: block -> batch by division
+    int stagger_blocks = 0;   // the first stagger_blocks workgroups (one full residency of the chip) delay their start by
+    int stagger_x1024 = 0;    // blockIdx * stagger_x1024 / 1024 ticks of the 100 MHz real-time counter (0: no stagger), see the kernel
+    int strided = 0;          // 1: batch i = b[0] with every member pointer advanced by i * stride[member] bytes (any count);
+                              // 0: batch i = b[i] (count <= GROUP_MAX)
+    long long* trace = nullptr; // diagnostic (ALORE_NMPC_TRACE): 8 words per workgroup, see the kernel; else null
+    int* counter = nullptr;   // persistent grid: [0] tickets handed out, [1] workgroups that have left (both 0 between launches); else null
+    int persist_blocks = 0;   // persistent grid: workgroups launched (one per SIMD slot); items beyond them are taken by ticket
+    int xcd_on = 0;           // 1: XCD x (workgroups w = x mod 8) works on xcd_share[x] consecutive blocks from xcd_base[x] (see the kernel)
+    int xcd_share[8] = {}, xcd_base[8] = {};
+    unsigned long long* xcd_end = nullptr; // [8][4] host memory: finishing times (100 MHz counter) of the last four workgroups of every XCD, or null
     // Two-phase grids (TWOPH builds of the kernel, see nmpc_block_kernel.hip).  The grid is dealt in UNITS of blocks_per_batch + tp_tail
     // workgroups: unit u = the blocks of batch u, then the tail workgroups of batch u - tp_lag.  Batches below tp_count2 run in two phases
     // (first pass: no working-set prediction, one sweep; problems whose working set moves are queued for the tail workgroups, which solve
     // them sixteen at a time with the full body); the rest in one pass.
-    int tp_count2, tp_tail, tp_lag;
-    int tp_timeout;              // ticks of the 100 MHz counter a tail workgroup waits for its chunk before it gives up (error record)
-    int* tp_exits;               // [tp_count2]
-    int* tp_cnt;                 // [tp_count2][blocks_per_batch]
-    int* tp_entries;             // [tp_count2][blocks_per_batch * 16]
-    long long* tp_trace;         // diagnostic (ALORE_NMPC_TP_TRACE): 4 words per workgroup -- real-time counter at its start, inputs landed, end; role | batch << 8 | turns << 40 -- or null
-    int* tp_rec;                 // host memory: [0 .. 31] deferred problems of batch (b mod 32), [32] != 0: a tail workgroup timed out; or null
-    long long stride[15]; // bytes, in the member order of alore_nmpc_batch
-    alore_nmpc_batch b[GROUP_MAX];
+    int tp_count2 = 0, tp_tail = 0, tp_lag = 0;
+    int tp_timeout = 0;              // ticks of the 100 MHz counter a tail workgroup waits for its chunk before it gives up (error record)
+    int* tp_exits = nullptr;         // [tp_count2]
+    int* tp_cnt = nullptr;           // [tp_count2][blocks_per_batch]
+    int* tp_entries = nullptr;       // [tp_count2][blocks_per_batch * 16]
+    long long* tp_trace = nullptr;   // diagnostic (ALORE_NMPC_TP_TRACE): 4 words per workgroup -- real-time counter at its start, inputs landed, end; role | batch << 8 | turns << 40 -- or null
+    int* tp_rec = nullptr;           // host memory: [0 .. 31] deferred problems of batch (b mod 32), [32] != 0: a tail workgroup timed out; or null
+    long long stride[15] = {}; // bytes, in the member order of alore_nmpc_batch
+    alore_nmpc_batch b[GROUP_MAX] = {};
 };
+// the kernel reads it from the kernel-argument segment by offset
+static_assert(std::is_trivially_copyable<RtiGroup>::value, "RtiGroup travels by value in the kernel arguments");
+static_assert(sizeof(RtiGroup) == 3176 && offsetof(RtiGroup, stride) == 176 && offsetof(RtiGroup, b) == 296, "RtiGroup: layout of the kernel arguments");
 static_assert(sizeof(alore_nmpc_batch) == 15 * sizeof(void*), "alore_nmpc_batch is 15 pointers");
-
-struct LaunchGeom {
-    int L;       // lanes per problem
-    int G;       // problems per wavefront
-    int wpb;     // wavefronts per workgroup (1 or 4)
-    int wreg;    // 1: W_k of a stage lives in the registers of its lane, not in the LDS staging area
-    int threads; // = L * G, multiple of 64
-    int grid;
-    int RS;      // wavefront kernel: LDS floats per problem; stage-block kernel: stages per lane (S)
-    size_t lds_bytes;
-    int block;   // 1: stage-block kernel (nmpc_block_kernel.hip), 0: wavefront kernel (nmpc_kernels.hip)
-};
 
 // number of LDS floats one problem needs (before padding) for horizon N
 int rti_row_floats(int N, bool wreg);
@@ -89,11 +84,10 @@ int rti_row_floats(int N, bool wreg);
 bool rti_geometry(int B, int N, int forced_L, int lds_limit_bytes, int n_cu, LaunchGeom* g, int forced_wpb = 0);
 hipError_t launch_rti(const RtiParams& p, const LaunchGeom& g, hipStream_t s);
 // stage-block kernel (nmpc_block_kernel.hip): L = 4, 8 or 16 lanes per problem, each lane owns ceil(N / L) stages
-int block_lds_floats(int N, int L);
-bool block_geometry(int B, int N, int forced_L, int lds_limit_bytes, int n_cu, LaunchGeom* g, int B_in_flight = 0);
+// (block_lds_floats, block_geometry: nmpc_launch_plan.h)
 hipError_t launch_rti_block(const RtiParams& p, const LaunchGeom& g, hipStream_t s);
 // may a grid of this geometry run in two phases (RtiGroup::tp_*)?
-bool rti_block_two_phase_supported(const RtiParams& p, const LaunchGeom& g);
+inline bool rti_block_two_phase_supported(const RtiParams& p, const LaunchGeom& g) { return two_phase_supported(g, p.N, p.n_sqp, p.stamps != nullptr); }
 hipError_t launch_rti_block_group(const RtiParams& p, const RtiGroup& grp, const LaunchGeom& g, hipStream_t s);
 
 // nmpc_dense.hip: the condensed QP of the reference's dense interface (acadoWorkspace.H / g / lb / ub, acado_solve)
@@ -183,7 +177,8 @@ struct AheadSampler {
     int B, N;
     int first_block;     // set by the launcher: workgroups from here on are the sampler's
 };
-int rti_block_sampler_supported(const RtiParams& p, const LaunchGeom& g); // 2: sampler + plant step in the solver's grid, 1: plant step only, 0: neither
+// 2: sampler + plant step in the solver's grid, 1: plant step only, 0: neither
+inline int rti_block_sampler_supported(const RtiParams& p, const LaunchGeom& g) { return sampler_supported(g, p.N, p.n_sqp, p.stamps != nullptr); }
 hipError_t launch_rti_block_sampler(const RtiParams& p, const LaunchGeom& g, const AheadSampler& sa, const PlantAhead* plant, hipStream_t s);
 // closed_loop_run: the pose-independent part of the sampling of a tick ahead of its pose, and the plant step that completes it
 bool ref_sample_ahead_supported(int N);
