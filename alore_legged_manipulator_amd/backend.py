@@ -71,6 +71,22 @@ class CheckC(C.Structure):
                 ("first_time", C.c_double), ("first_xy", C.c_double * 2), ("min_dist", C.c_double)]
 
 
+class FrontEndParamsC(C.Structure):
+    """alore_front_end_params (include/alore_backend.h); the fields of flat_traj.FrontEndParams"""
+    _fields_ = [("distance_weight", C.c_double), ("yaw_weight", C.c_double), ("traj_cut_length", C.c_double),
+                ("sample_time", C.c_double), ("min_traj_num", C.c_int), ("max_vel", C.c_double), ("max_acc", C.c_double)]
+
+
+class PathsC(C.Structure):
+    """alore_backend_paths: host or device addresses"""
+    _fields_ = [("max_points", C.c_int), ("n_points", C.c_void_p), ("xy", C.c_void_p), ("start_yaw", C.c_void_p),
+                ("end_yaw", C.c_void_p), ("start_vaj", C.c_void_p), ("start_oaj", C.c_void_p)]
+
+
+MAX_PATH_POINTS = 31
+BUILD_OK, BUILD_MASKED, BUILD_E_POINTS, BUILD_E_PIECES = 0, 1, -1, -2
+
+
 # the same record as a numpy dtype (what check_plans unpacks, and what a copy of the device slab holds)
 CHECK_DTYPE = np.dtype([("collision", np.int32), ("first_panel", np.int32), ("n_checked", np.int32), ("pad", np.int32),
                         ("first_time", np.float64), ("first_xy", np.float64, 2), ("min_dist", np.float64)])
@@ -100,6 +116,15 @@ def _bind(L):
     L.alore_backend_last_plan_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.alore_backend_check_plans.argtypes = [C.c_void_p, C.c_int, DP, DP, C.c_double, C.c_int, C.POINTER(CheckC), C.c_void_p]
     L.alore_backend_device_check.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.alore_front_end_default_params.argtypes = [C.POINTER(FrontEndParamsC)]
+    L.alore_front_end_default_params.restype = None
+    L.alore_backend_set_paths.argtypes = [C.c_void_p, C.c_int, C.POINTER(PathsC), C.POINTER(FrontEndParamsC), C.c_int, C.c_void_p, C.c_int,
+                                          C.c_void_p]
+    L.alore_backend_device_build_status.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.alore_backend_build_status.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.alore_backend_get_problems.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), DP, DP, DP, DP, DP, DP, DP, C.POINTER(C.c_int)]
+    L.alore_backend_predicted_state_device.argtypes = [C.c_void_p, C.c_int, C.c_double] + [C.c_void_p] * 8
+    L.alore_backend_plan_masked.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     L._backend_bound = True
 
 
@@ -117,6 +142,44 @@ def default_config() -> BackendConfig:
 
 def _dp(a):
     return a.ctypes.data_as(DP) if a is not None else None
+
+
+def _front_end_params(params) -> FrontEndParamsC:
+    """flat_traj.FrontEndParams (or anything with its fields; None: the defaults) as the C struct"""
+    c = FrontEndParamsC()
+    if params is None:
+        L = _lib.load()
+        _bind(L)
+        L.alore_front_end_default_params(C.byref(c))
+    else:
+        for name, _ in FrontEndParamsC._fields_:
+            setattr(c, name, getattr(params, name))
+    return c
+
+
+def _dev(a):
+    """device address of a torch tensor, or the address itself (int / None)"""
+    if a is None or isinstance(a, int):
+        return a
+    return int(a.data_ptr())
+
+
+def _stream(s):
+    """hipStream_t of a torch stream, or the handle itself (int / None = the default stream)"""
+    if s is None or isinstance(s, int):
+        return s
+    return int(s.cuda_stream)
+
+
+def _mask(mask, stride):
+    """(address, stride in bytes) of a device mask: a torch int32 tensor (its own stride), an address with `stride`, or a pair"""
+    if mask is None:
+        return None, 0
+    if isinstance(mask, tuple):
+        return int(mask[0]), int(mask[1])
+    if isinstance(mask, int):
+        return mask, int(stride)
+    return int(mask.data_ptr()), int(mask.stride(0) * mask.element_size()) if mask.dim() else 4
 
 
 class BatchedMSPlanner:
@@ -183,18 +246,21 @@ class BatchedMSPlanner:
         self._check(self.L.alore_backend_path_points(self.h, n, int(panels_per_piece), _dp(xy), _dp(yaw), npts.ctypes.data_as(C.POINTER(C.c_int))))
         return [(xy[b, :npts[b]].copy(), yaw[b, :(npts[b] // (panels_per_piece + 1)) * panels_per_piece].copy()) for b in range(n)]
 
-    def check_plans(self, t_from=None, t_to=None, min_safe_dis=None, body=False, count=None) -> dict:
+    def check_plans(self, t_from=None, t_to=None, min_safe_dis=None, body=False, count=None, stream=None, fetch=True) -> dict | None:
         """The final collision check of the plans of the last launch against the map as it is NOW (set_map / build_esdf since
         then): per plan, over the panels whose time interval overlaps (t_from[b], t_to[b]) (None: from 0 / to the end), whether
         one is closer than min_safe_dis (None: the configured final_min_safe_dis) and where the first one is.  body: the
-        minimum over the reference point and the configured body check points instead of the reference point alone."""
+        minimum over the reference point and the configured body check points instead of the reference point alone.
+        fetch=False: the records stay in the device slab (device_check / check_mask), nothing waits and nothing is returned."""
         n = self.count if count is None else int(count)
         m = max(n, 0)
         tf = None if t_from is None else np.ascontiguousarray(np.broadcast_to(np.asarray(t_from, np.float64), (m,)))
         tt = None if t_to is None else np.ascontiguousarray(np.broadcast_to(np.asarray(t_to, np.float64), (m,)))
         rec = np.zeros(m, CHECK_DTYPE)
         self._check(self.L.alore_backend_check_plans(self.h, n, _dp(tf), _dp(tt), 0.0 if min_safe_dis is None else float(min_safe_dis),
-                                                     int(bool(body)), rec.ctypes.data_as(C.POINTER(CheckC)), None))
+                                                     int(bool(body)), rec.ctypes.data_as(C.POINTER(CheckC)) if fetch else None, _stream(stream)))
+        if not fetch:
+            return None
         return {k: rec[k].copy() for k in ("collision", "first_panel", "n_checked", "first_time", "first_xy", "min_dist")}
 
     def device_check(self) -> int:
@@ -202,6 +268,80 @@ class BatchedMSPlanner:
         p = C.c_void_p()
         self._check(self.L.alore_backend_device_check(self.h, C.byref(p)))
         return p.value
+
+    def check_mask(self):
+        """(address, stride) of the `collision` words of the check slab: the mask of set_paths_device / plan that names the plans
+        the last check_plans flagged"""
+        return self.device_check(), C.sizeof(CheckC)
+
+    # ---- problems from way-point paths, built on the device (alore_backend_set_paths)
+    def set_paths(self, paths_xy, start_yaw, end_yaw, start_vaj=None, start_oaj=None, params=None, mask=None):
+        """FlatTrajData of way-point paths (a list of [n][2] arrays, or one [count][K][2] array with n_points given as a pair
+        (xy, n_points)) into slots 0..count-1, and the launch order; NumPy in, padded to the longest path.  mask: per slot, 0 leaves
+        the slot as it is.  Raises when a path does not build (build_status() says which)."""
+        if isinstance(paths_xy, tuple):
+            xy, npts = np.ascontiguousarray(paths_xy[0], np.float64), np.ascontiguousarray(paths_xy[1], np.int32)
+        else:
+            npts = np.array([len(p) for p in paths_xy], np.int32)
+            K = int(min(max(int(npts.max()), 2), MAX_PATH_POINTS))
+            xy = np.zeros((len(paths_xy), K, 2))
+            for b, p in enumerate(paths_xy):
+                q = np.asarray(p, np.float64).reshape(-1, 2)[:K]
+                xy[b, :len(q)] = q
+        n = len(npts)
+        sy = np.ascontiguousarray(np.broadcast_to(np.asarray(start_yaw, np.float64), (n,)))
+        ey = np.ascontiguousarray(np.broadcast_to(np.asarray(end_yaw, np.float64), (n,)))
+        vaj = None if start_vaj is None else np.ascontiguousarray(np.broadcast_to(np.asarray(start_vaj, np.float64), (n, 3)))
+        oaj = None if start_oaj is None else np.ascontiguousarray(np.broadcast_to(np.asarray(start_oaj, np.float64), (n, 3)))
+        mk = None if mask is None else np.ascontiguousarray(np.asarray(mask).astype(bool), np.int32)
+        pc = PathsC(xy.shape[1], npts.ctypes.data, xy.ctypes.data, sy.ctypes.data, ey.ctypes.data,
+                    None if vaj is None else vaj.ctypes.data, None if oaj is None else oaj.ctypes.data)
+        fe = _front_end_params(params)
+        self.count = n  # the handle's count changes whether or not every path builds
+        self._check(self.L.alore_backend_set_paths(self.h, n, C.byref(pc), C.byref(fe), 0, None if mk is None else mk.ctypes.data, 4, None))
+
+    def set_paths_device(self, count, max_points, n_points, xy, start_yaw, end_yaw, start_vaj=None, start_oaj=None, params=None, mask=None,
+                         mask_stride=4, stream=None):
+        """The same with everything resident: torch tensors (int32 n_points [count], float64 xy [count][max_points][2], start_yaw /
+        end_yaw [count], start_vaj / start_oaj [count][3]) or raw device addresses; mask as for plan().  Nothing is copied but the
+        argument block and nothing waits; build_status() has the outcome per slot."""
+        pc = PathsC(int(max_points), _dev(n_points), _dev(xy), _dev(start_yaw), _dev(end_yaw), _dev(start_vaj), _dev(start_oaj))
+        fe = _front_end_params(params)
+        mp, ms = _mask(mask, mask_stride)
+        self._check(self.L.alore_backend_set_paths(self.h, int(count), C.byref(pc), C.byref(fe), 1, mp, ms, _stream(stream)))
+        self.count = int(count)
+
+    def build_status(self, count: int | None = None) -> np.ndarray:
+        """per slot of the last set_paths[_device]: 0 built, 1 masked out, -1 bad point count, -2 too many pieces (waits)"""
+        n = int(count or self.count)
+        out = np.zeros(n, np.int32)
+        self._check(self.L.alore_backend_build_status(self.h, n, out.ctypes.data_as(C.POINTER(C.c_int))))
+        return out
+
+    def device_build_status(self) -> int:
+        p = C.c_void_p()
+        self._check(self.L.alore_backend_device_build_status(self.h, C.byref(p)))
+        return p.value
+
+    def problems(self, count: int | None = None) -> dict:
+        """the problem slots as they lie on the device (waits)"""
+        n, P = int(count or self.count), self.P
+        out = {"n_pieces": np.zeros(n, np.int32), "inner": np.zeros((n, P - 1, 2)), "init_T": np.zeros(n), "positions": np.zeros((n, P, 2)),
+               "head": np.zeros((n, 2, 3)), "tail": np.zeros((n, 2, 3)), "start_xytheta": np.zeros((n, 3)), "final_xy": np.zeros((n, 2)),
+               "if_cut": np.zeros(n, np.int32)}
+        ip = C.POINTER(C.c_int)
+        self._check(self.L.alore_backend_get_problems(self.h, n, out["n_pieces"].ctypes.data_as(ip), _dp(out["inner"]), _dp(out["init_T"]),
+                                                      _dp(out["positions"]), _dp(out["head"]), _dp(out["tail"]), _dp(out["start_xytheta"]),
+                                                      _dp(out["final_xy"]), out["if_cut"].ctypes.data_as(ip)))
+        return out
+
+    def predicted_state_device(self, count, times, xytheta, vaj, oaj, forward, resolution: float = 0.01, start_times=None, start_xytheta=None,
+                               stream=None):
+        """predicted_state with device inputs (times [count], start_times [count] or None, start_xytheta [count][3] or None) and
+        outputs (xytheta, vaj, oaj [count][3] float64, forward [count] int32): torch tensors or addresses; no copy, nothing waits"""
+        self._check(self.L.alore_backend_predicted_state_device(self.h, int(count), float(resolution), _dev(start_times), _dev(times),
+                                                                _dev(start_xytheta), _dev(xytheta), _dev(vaj), _dev(oaj), _dev(forward),
+                                                                _stream(stream)))
 
     def set_free_map(self, half: float = 40.0, res: float = 0.1, value: float = 100.0):
         n = int(round(2 * half / res))
@@ -233,21 +373,27 @@ class BatchedMSPlanner:
         self.count = n
         self._pieces = np.array([a.n_pieces for a in arr])
 
-    def plan(self, count: int | None = None):
-        self._check(self.L.alore_backend_plan(self.h, count or self.count, None))
+    def plan(self, count: int | None = None, mask=None, mask_stride: int = 4, stream=None):
+        """mask (device memory: a torch int32 tensor, an address with mask_stride bytes between the words, or check_mask()):
+        only the slots whose word is not 0 are planned, the others keep their stored plan bit for bit"""
+        if mask is None:
+            self._check(self.L.alore_backend_plan(self.h, count or self.count, _stream(stream)))
+            return
+        mp, ms = _mask(mask, mask_stride)
+        self._check(self.L.alore_backend_plan_masked(self.h, count or self.count, mp, ms, _stream(stream)))
 
     def last_plan_ms(self) -> float:
         ms = C.c_float()
         self._check(self.L.alore_backend_last_plan_ms(self.h, C.byref(ms)))
         return ms.value
 
-    def results(self, count: int | None = None) -> dict:
+    def results(self, count: int | None = None, stream=None) -> dict:
         n = count or self.count
         st = (StatusC * n)()
         inner = np.zeros((n, self.P - 1, 2))
         T = np.zeros((n, self.P))
         coef = np.zeros((n, self.P * 6, 2))
-        self._check(self.L.alore_backend_results(self.h, n, st, _dp(inner), _dp(T), _dp(coef), None))
+        self._check(self.L.alore_backend_results(self.h, n, st, _dp(inner), _dp(T), _dp(coef), _stream(stream)))
         out = {k: np.array([getattr(s, k) for s in st]) for k in
                ("ok", "attempts", "alm_rounds", "evals", "lbfgs_ret", "path_ret", "collision", "n_pieces", "cost", "min_dist", "tail_s")}
         out["xy_err"] = np.array([[s.xy_err[0], s.xy_err[1]] for s in st])

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "backend_kernels.h"
+#include "flat_traj_build.h"
 
 struct alore_backend_planner {
     alore_backend_config cfg;
@@ -41,6 +42,16 @@ struct alore_backend_planner {
     alore_backend_check* d_check = nullptr;
     hipEvent_t ev_check = nullptr, ev_check_done = nullptr; // the upload of the previous call has left h_check; its kernel has ended
     bool check_pending = false;
+    // alore_backend_set_paths: the argument block followed by the staged inputs of the host route, pinned and on the device, and
+    // the build status per slot
+    char *h_build = nullptr, *d_build_in = nullptr;
+    int* d_build_status = nullptr;
+    hipEvent_t ev_build = nullptr; // the upload of the previous call has left h_build
+    bool build_pending = false;
+    // alore_backend_plan_masked: its parameter block goes up from pinned memory
+    backend::Params* h_params = nullptr;
+    hipEvent_t ev_params = nullptr;
+    bool params_pending = false;
 };
 
 namespace {
@@ -80,11 +91,15 @@ void free_all(alore_backend_handle h)
     }
     void* ptrs[] = {h->d_map, h->d_M, h->d_cut, h->d_inner, h->d_initT, h->d_pos, h->d_head, h->d_tail, h->d_sxy, h->d_fxy, h->d_sxyt,
                     h->r_inner, h->r_T, h->r_coef, h->r_tail, h->r_ok, h->r_status, h->d_hist, h->d_gram, h->d_pcr, h->d_x, h->d_g, h->d_lam, h->d_rho,
-                    h->d_cost, h->d_err, h->d_ret, h->d_params, h->d_order, h->d_check_in, h->d_check};
+                    h->d_cost, h->d_err, h->d_ret, h->d_params, h->d_order, h->d_check_in, h->d_check, h->d_build_in, h->d_build_status};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->h_check) (void)hipHostFree(h->h_check);
+    if (h->h_build) (void)hipHostFree(h->h_build);
+    if (h->h_params) (void)hipHostFree(h->h_params);
+    if (h->ev_build) (void)hipEventDestroy(h->ev_build);
+    if (h->ev_params) (void)hipEventDestroy(h->ev_params);
     if (h->ev_check) (void)hipEventDestroy(h->ev_check);
     if (h->ev_check_done) (void)hipEventDestroy(h->ev_check_done);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -114,6 +129,27 @@ backend::Params base_params(alore_backend_handle h, int count, int mode)
 
 constexpr size_t CHECK_ARGS_BYTES = (sizeof(backend::CheckArgs) + 15) & ~size_t(15);
 size_t check_in_bytes(size_t B) { return CHECK_ARGS_BYTES + sizeof(double) * 2 * B; }
+
+// the block of alore_backend_set_paths: arguments, then (host route) the inputs of up to B paths of flat_traj::MAX_POINTS points
+constexpr size_t BUILD_ARGS_BYTES = (sizeof(backend::BuildArgs) + 15) & ~size_t(15);
+struct BuildLayout {
+    size_t n_points, xy, start_yaw, end_yaw, vaj, oaj, mask, bytes;
+};
+BuildLayout build_layout(size_t n, size_t K)
+{
+    BuildLayout l{};
+    size_t at = BUILD_ARGS_BYTES;
+    auto take = [&](size_t bytes) { const size_t p = at; at += (bytes + 15) & ~size_t(15); return p; };
+    l.n_points = take(sizeof(int) * n);
+    l.xy = take(sizeof(double) * n * K * 2);
+    l.start_yaw = take(sizeof(double) * n);
+    l.end_yaw = take(sizeof(double) * n);
+    l.vaj = take(sizeof(double) * n * 3);
+    l.oaj = take(sizeof(double) * n * 3);
+    l.mask = take(sizeof(int) * n);
+    l.bytes = at;
+    return l;
+}
 
 } // namespace
 
@@ -190,6 +226,12 @@ int alore_backend_create(const alore_backend_config* cfg, int device, int max_pi
     if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_check, check_in_bytes(B), hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_check, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_check_done, hipEventDisableTiming);
+    const size_t build_bytes = build_layout(B, flat_traj::MAX_POINTS).bytes;
+    A(dalloc(&h->d_build_status, B)); A(dalloc(&h->d_build_in, build_bytes));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_build, build_bytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_params, sizeof(backend::Params), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_build, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_params, hipEventDisableTiming);
     if (e != hipSuccess) {
         free_all(h);
         delete h;
@@ -274,6 +316,20 @@ int alore_backend_predicted_state(alore_backend_handle h, int count, double reso
     if (e == hipSuccess) e = hipDeviceSynchronize();
     (void)hipFree(d_in); (void)hipFree(d_out); (void)hipFree(d_fwd);
     if (e != hipSuccess) return fail(h, ALORE_BE_E_HIP, "predicted_state", e);
+    return ALORE_BE_OK;
+}
+
+int alore_backend_predicted_state_device(alore_backend_handle h, int count, double resolution, const double* d_start_time,
+                                         const double* d_time, const double* d_start_xytheta, double* d_xytheta, double* d_vaj,
+                                         double* d_oaj, int* d_forward, void* stream)
+{
+    if (!h || count < 1 || count > h->B || !d_time || !d_xytheta || !d_vaj || !d_oaj || !d_forward || !(resolution > 0.0))
+        return fail(h, ALORE_BE_E_INVALID, "predicted_state_device: bad argument");
+    if (!h->timed || count > h->count) return fail(h, ALORE_BE_E_INVALID, "predicted_state_device: no plan for these slots (alore_backend_plan first)");
+    BE_TRY(h, hipSetDevice(h->device));
+    backend::PredictArgs g{count, h->P, h->d_M, h->r_T, h->r_coef, h->d_sxyt, d_start_time, d_time, d_start_xytheta, resolution,
+                           h->cfg.icr_xv, h->cfg.standard_diff != 0, d_xytheta, d_vaj, d_oaj, d_forward};
+    BE_TRY(h, backend::predicted_state(g, (hipStream_t)stream));
     return ALORE_BE_OK;
 }
 
@@ -369,6 +425,112 @@ int alore_backend_set_problems(alore_backend_handle h, int count, const alore_fl
     return ALORE_BE_OK;
 }
 
+void alore_front_end_default_params(alore_front_end_params* p)
+{
+    std::memset(p, 0, sizeof(*p));
+    flat_traj::default_params(p);
+}
+
+int alore_backend_set_paths(alore_backend_handle h, int count, const alore_backend_paths* p, const alore_front_end_params* fe,
+                            int device_pointers, const int* mask, int mask_stride_bytes, void* stream)
+{
+    if (!h || count < 1 || count > h->B || !p || !p->n_points || !p->xy || !p->start_yaw || !p->end_yaw)
+        return fail(h, ALORE_BE_E_INVALID, "set_paths: bad argument");
+    if (p->max_points < 2 || p->max_points > flat_traj::MAX_POINTS) return fail(h, ALORE_BE_E_UNSUPPORTED, "set_paths: max_points must be 2 .. 31");
+    if (mask && (mask_stride_bytes < (int)sizeof(int) || mask_stride_bytes % (int)sizeof(int)))
+        return fail(h, ALORE_BE_E_INVALID, "set_paths: the mask stride must be a positive multiple of sizeof(int)");
+    alore_front_end_params prm;
+    if (fe) prm = *fe; else alore_front_end_default_params(&prm);
+    if (!(prm.sample_time > 0.0) || !(prm.max_vel > 0.0) || !(prm.max_acc > 0.0) || prm.min_traj_num < 1)
+        return fail(h, ALORE_BE_E_INVALID, "set_paths: sample_time, max_vel, max_acc and min_traj_num must be positive");
+    BE_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (h->build_pending) BE_TRY(h, hipEventSynchronize(h->ev_build)); // the pinned block is free again
+    h->build_pending = false;
+    const size_t n = count, K = p->max_points;
+    backend::BuildArgs g{};
+    g.count = count; g.P = h->P; g.K = p->max_points;
+    g.fe = prm;
+    size_t up = BUILD_ARGS_BYTES;
+    if (device_pointers) {
+        g.n_points = p->n_points; g.xy = p->xy; g.start_yaw = p->start_yaw; g.end_yaw = p->end_yaw;
+        g.start_vaj = p->start_vaj; g.start_oaj = p->start_oaj;
+        g.mask = mask; g.mask_stride = mask ? mask_stride_bytes : 0;
+    } else {
+        const BuildLayout l = build_layout(n, K);
+        char *hb = h->h_build, *db = h->d_build_in;
+        std::memcpy(hb + l.n_points, p->n_points, sizeof(int) * n);
+        std::memcpy(hb + l.xy, p->xy, sizeof(double) * n * K * 2);
+        std::memcpy(hb + l.start_yaw, p->start_yaw, sizeof(double) * n);
+        std::memcpy(hb + l.end_yaw, p->end_yaw, sizeof(double) * n);
+        if (p->start_vaj) std::memcpy(hb + l.vaj, p->start_vaj, sizeof(double) * n * 3);
+        if (p->start_oaj) std::memcpy(hb + l.oaj, p->start_oaj, sizeof(double) * n * 3);
+        if (mask)
+            for (size_t b = 0; b < n; ++b) ((int*)(hb + l.mask))[b] = *(const int*)((const char*)mask + b * (size_t)mask_stride_bytes);
+        g.n_points = (const int*)(db + l.n_points); g.xy = (const double*)(db + l.xy);
+        g.start_yaw = (const double*)(db + l.start_yaw); g.end_yaw = (const double*)(db + l.end_yaw);
+        g.start_vaj = p->start_vaj ? (const double*)(db + l.vaj) : nullptr;
+        g.start_oaj = p->start_oaj ? (const double*)(db + l.oaj) : nullptr;
+        g.mask = mask ? (const int*)(db + l.mask) : nullptr;
+        g.mask_stride = mask ? (int)sizeof(int) : 0;
+        up = l.bytes;
+    }
+    g.M = h->d_M; g.if_cut = h->d_cut; g.inner = h->d_inner; g.init_T = h->d_initT; g.positions = h->d_pos; g.head = h->d_head;
+    g.tail = h->d_tail; g.start_xy = h->d_sxy; g.final_xy = h->d_fxy; g.sxyt = h->d_sxyt;
+    g.status = h->d_build_status; g.order = h->d_order;
+    std::memcpy(h->h_build, &g, sizeof(g));
+    BE_TRY(h, hipMemcpyAsync(h->d_build_in, h->h_build, up, hipMemcpyHostToDevice, s));
+    BE_TRY(h, hipEventRecord(h->ev_build, s));
+    h->build_pending = true;
+    BE_TRY(h, backend::build_problems((const backend::BuildArgs*)h->d_build_in, count, s));
+    h->count = count;
+    if (!device_pointers) {
+        int* hst = (int*)h->h_stage;
+        BE_TRY(h, hipMemcpyAsync(hst, h->d_build_status, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+        BE_TRY(h, hipStreamSynchronize(s));
+        for (size_t b = 0; b < n; ++b) {
+            if (hst[b] == flat_traj::E_POINTS) return fail(h, ALORE_BE_E_INVALID, "set_paths: a path has fewer than 2 or more than max_points way-points");
+            if (hst[b] == flat_traj::E_PIECES) return fail(h, ALORE_BE_E_UNSUPPORTED, "set_paths: more pieces than the handle was created for");
+        }
+    }
+    return ALORE_BE_OK;
+}
+
+int alore_backend_device_build_status(alore_backend_handle h, const int** out)
+{
+    if (!h || !out) return fail(h, ALORE_BE_E_INVALID, "device_build_status: bad argument");
+    *out = h->d_build_status;
+    return ALORE_BE_OK;
+}
+
+int alore_backend_build_status(alore_backend_handle h, int count, int* out)
+{
+    if (!h || count < 1 || count > h->B || !out) return fail(h, ALORE_BE_E_INVALID, "build_status: bad argument");
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, hipDeviceSynchronize());
+    BE_TRY(h, hipMemcpy(out, h->d_build_status, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost));
+    return ALORE_BE_OK;
+}
+
+int alore_backend_get_problems(alore_backend_handle h, int count, int* n_pieces, double* inner, double* init_T, double* positions,
+                               double* head, double* tail, double* start_xytheta, double* final_xy, int* if_cut)
+{
+    if (!h || count < 1 || count > h->B) return fail(h, ALORE_BE_E_INVALID, "get_problems: bad argument");
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, hipDeviceSynchronize());
+    const size_t n = count, P = h->P;
+    if (n_pieces) BE_TRY(h, hipMemcpy(n_pieces, h->d_M, sizeof(int) * n, hipMemcpyDeviceToHost));
+    if (inner) BE_TRY(h, hipMemcpy(inner, h->d_inner, sizeof(double) * n * (P - 1) * 2, hipMemcpyDeviceToHost));
+    if (init_T) BE_TRY(h, hipMemcpy(init_T, h->d_initT, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (positions) BE_TRY(h, hipMemcpy(positions, h->d_pos, sizeof(double) * n * P * 2, hipMemcpyDeviceToHost));
+    if (head) BE_TRY(h, hipMemcpy(head, h->d_head, sizeof(double) * n * 6, hipMemcpyDeviceToHost));
+    if (tail) BE_TRY(h, hipMemcpy(tail, h->d_tail, sizeof(double) * n * 6, hipMemcpyDeviceToHost));
+    if (start_xytheta) BE_TRY(h, hipMemcpy(start_xytheta, h->d_sxyt, sizeof(double) * n * 3, hipMemcpyDeviceToHost));
+    if (final_xy) BE_TRY(h, hipMemcpy(final_xy, h->d_fxy, sizeof(double) * n * 2, hipMemcpyDeviceToHost));
+    if (if_cut) BE_TRY(h, hipMemcpy(if_cut, h->d_cut, sizeof(int) * n, hipMemcpyDeviceToHost));
+    return ALORE_BE_OK;
+}
+
 int alore_backend_plan(alore_backend_handle h, int count, void* stream)
 {
     if (!h || count < 1 || count > h->count) return fail(h, ALORE_BE_E_INVALID, "plan: upload the problems first");
@@ -379,6 +541,29 @@ int alore_backend_plan(alore_backend_handle h, int count, void* stream)
     if (count == h->count) p.order = h->d_order; // the whole uploaded set: longest problems first
     BE_TRY(h, hipEventRecord(h->ev0, s));
     BE_TRY(h, backend::launch(p, h->d_params, h->P, s));
+    BE_TRY(h, hipEventRecord(h->ev1, s));
+    h->timed = true;
+    return ALORE_BE_OK;
+}
+
+int alore_backend_plan_masked(alore_backend_handle h, int count, const int* mask, int mask_stride_bytes, void* stream)
+{
+    if (!h || count < 1 || count > h->count) return fail(h, ALORE_BE_E_INVALID, "plan_masked: upload the problems first");
+    if (!h->d_map) return fail(h, ALORE_BE_E_INVALID, "plan_masked: no map (alore_backend_set_map)");
+    if (mask && (mask_stride_bytes < (int)sizeof(int) || mask_stride_bytes % (int)sizeof(int)))
+        return fail(h, ALORE_BE_E_INVALID, "plan_masked: the mask stride must be a positive multiple of sizeof(int)");
+    BE_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (h->params_pending) BE_TRY(h, hipEventSynchronize(h->ev_params)); // the pinned block is free again
+    h->params_pending = false;
+    *h->h_params = base_params(h, count, backend::MODE_PLAN);
+    if (count == h->count) h->h_params->order = h->d_order;
+    h->h_params->mask = mask;
+    h->h_params->mask_stride = mask ? mask_stride_bytes : 0;
+    BE_TRY(h, hipEventRecord(h->ev0, s));
+    BE_TRY(h, backend::launch(*h->h_params, h->d_params, h->P, s));
+    BE_TRY(h, hipEventRecord(h->ev_params, s));
+    h->params_pending = true;
     BE_TRY(h, hipEventRecord(h->ev1, s));
     h->timed = true;
     return ALORE_BE_OK;

@@ -72,6 +72,9 @@ struct Params {
     int* ret_out;     // [B][3]: ret, iterations, evaluations
     const int* order;  // optional: workgroup w works on problem order[w] (longest problems first: a launch ends with its slowest wavefront)
     long long* stamps; // diagnostic (ALORE_BE_STAMPS=1): [64] cycles per phase of workgroup 0, [63] = last stamp
+    // alore_backend_plan_masked: a workgroup whose slot b has the int at (char*)mask + b * mask_stride equal to 0 returns at entry
+    const int* mask; // null: every slot is planned
+    int mask_stride; // bytes
 };
 
 size_t lds_bytes(int P);
@@ -94,6 +97,25 @@ struct CheckArgs {
 };
 // the kernel reads its arguments from d_args (device memory, filled in stream order before the launch)
 hipError_t check_plans(const CheckArgs* d_args, int count, hipStream_t s);
+
+// FlatTrajData from way-point paths (flat_traj_build.hip: build_problems_kernel, one wavefront per path, then launch_order_kernel)
+struct BuildArgs {
+    int count, P, K; // K: way-points per path in xy (<= 31)
+    alore_front_end_params fe;
+    const int* n_points;                   // [count]
+    const double* xy;                      // [count][K][2]
+    const double *start_yaw, *end_yaw;     // [count]
+    const double *start_vaj, *start_oaj;   // [count][3] or null (zeros)
+    const int* mask;                       // null, or slot b is rebuilt when the int at (char*)mask + b * mask_stride is not 0
+    int mask_stride;
+    // the problem slots (ProblemStore) and the plan start pose
+    int *M, *if_cut;
+    double *inner, *init_T, *positions, *head, *tail, *start_xy, *final_xy, *sxyt;
+    int* status; // [count] build status: 0 built, 1 masked out, -1 bad point count, -2 more pieces than the slot holds
+    int* order;  // [count] launch order: most pieces first, stable in the slot index
+};
+// both kernels read their arguments from d_args (device memory, filled in stream order before the launch)
+hipError_t build_problems(const BuildArgs* d_args, int count, hipStream_t s);
 
 // MSPlanner::get_the_predicted_state[_and_path] on the plans of the last launch (esdf_build.hip)
 struct PredictArgs {

@@ -1389,6 +1389,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     const int lane = threadIdx.x;
     if ((int)blockIdx.x >= prm.count) return;
     const int b = prm.order ? prm.order[blockIdx.x] : (int)blockIdx.x;
+    // alore_backend_plan_masked: a slot the mask leaves out keeps its stored plan (nothing below runs, no barrier has been passed)
+    if (prm.mask && *(const int*)((const char*)prm.mask + (size_t)b * prm.mask_stride) == 0) return;
     const Config& c = prm.cfg;
     load_problem<P>(prm, lbase, b);
     const int M = uni(e.M), n = uni(e.n), nstride = 3 * prm.prob.P;

@@ -189,6 +189,78 @@ int alore_backend_check_plans(alore_backend_handle h, int count, const double *t
 /* device slab [max_problems] of the records of the last check; valid until the handle is destroyed */
 int alore_backend_device_check(alore_backend_handle h, const alore_backend_check **out);
 
+/* ---- problems from way-point paths, on the device ----------------------------------------------------- */
+/* What turns the front end's pruned polyline into FlatTrajData: getSampleTraj and getTrajsWithTime (front_end/src/jps_planner/
+ * jps_planner.cpp:212-366) with the trapezoid of :378-441, one wavefront per path (csrc/flat_traj_build.h holds the arithmetic,
+ * csrc/flat_traj_build.hip the kernel).  alore_front_end_default_params fills the values of jps3ms.yaml, global_planning3ms.yaml
+ * and car3ms.yaml. */
+typedef struct alore_front_end_params {
+    double distance_weight, yaw_weight; /* jps_distance_weight, jps_yaw_weight */
+    double traj_cut_length;             /* trajCutLength */
+    double sample_time;                 /* timeResolution */
+    int min_traj_num;                   /* mintrajNum */
+    double max_vel, max_acc;
+} alore_front_end_params;
+void alore_front_end_default_params(alore_front_end_params *p);
+
+/* `count` paths of up to max_points (<= 31) way-points each; arrays of HOST or DEVICE memory (alore_backend_set_paths says which) */
+typedef struct alore_backend_paths {
+    int max_points;          /* K: row length of xy */
+    const int *n_points;     /* [count], 2 .. K */
+    const double *xy;        /* [count][K][2]; rows are read up to n_points */
+    const double *start_yaw; /* [count] */
+    const double *end_yaw;   /* [count] */
+    const double *start_vaj; /* [count][3] or NULL (zeros): v, a, j of the arc length at the start (v starts the trapezoid) */
+    const double *start_oaj; /* [count][3] or NULL (zeros): omega, alpha, jerk of the yaw at the start */
+} alore_backend_paths;
+
+/* build status of a slot */
+#define ALORE_BE_BUILD_OK 0
+#define ALORE_BE_BUILD_MASKED 1         /* the mask left the slot out: nothing of it was touched */
+#define ALORE_BE_BUILD_E_POINTS (-1)    /* fewer than 2 or more than K way-points: slot untouched */
+#define ALORE_BE_BUILD_E_PIECES (-2)    /* more pieces than the handle was created for: slot untouched */
+
+/* Builds the problems of slots 0..count-1 from the paths, in the layout alore_backend_set_problems uploads, and the launch order
+ * (most pieces first, stable in the slot index), and sets the number of uploaded problems to count like alore_backend_set_problems.
+ * fe NULL: the defaults.  mask NULL: every slot; otherwise slot b is rebuilt when the int at (char *)mask + b * mask_stride_bytes is
+ * not 0 and left untouched when it is 0 -- with mask_stride_bytes = sizeof(alore_backend_check) the `collision` words of the slab of
+ * alore_backend_device_check are a mask as they lie.  A path that does not build leaves its slot untouched; the outcome per slot
+ * is in the build-status slab.
+ * device_pointers == 0: the arrays of `p` and the mask are HOST memory; they are uploaded, the stream is synchronised, and the call
+ * returns ALORE_BE_E_INVALID / ALORE_BE_E_UNSUPPORTED for the first slot that did not build (bad point count / too many pieces).
+ * device_pointers != 0: they are DEVICE memory, read in stream order; nothing crosses the bus but the argument block, nothing is
+ * allocated and nothing waits (a second call waits for the first one's argument block to have left the host, not for its kernel).
+ * ORDERING.  Between this call and the next plan launch a rebuilt slot holds its new n_pieces and start pose next to the results of
+ * its old plan: alore_backend_check_plans, alore_backend_predicted_state[_device], alore_backend_path_points and
+ * alore_backend_results on such a slot in that window are the caller's to avoid (alore_backend_set_problems has the same window).
+ * In a replan cycle, check and predict first, then set the paths, then plan. */
+int alore_backend_set_paths(alore_backend_handle h, int count, const alore_backend_paths *p, const alore_front_end_params *fe,
+                            int device_pointers, const int *mask, int mask_stride_bytes, void *stream);
+/* device slab [max_problems] of the build status of the last alore_backend_set_paths; valid until the handle is destroyed */
+int alore_backend_device_build_status(alore_backend_handle h, const int **out);
+/* the same copied to HOST memory out[count]; waits for the device */
+int alore_backend_build_status(alore_backend_handle h, int count, int *out);
+/* The problem slots as they lie on the device, copied to HOST arrays (any pointer may be NULL; P = max_pieces as rounded by the
+ * handle, 16 or 32): n_pieces [count], inner [count][(P-1)*2] (yaw, s), init_T [count], positions [count][P*2] (way-point xy,
+ * then final xy), head / tail [count][6] ([yaw | s][p v a]), start_xytheta [count][3], final_xy [count][2], if_cut [count].
+ * Waits for the device. */
+int alore_backend_get_problems(alore_backend_handle h, int count, int *n_pieces, double *inner, double *init_T, double *positions,
+                               double *head, double *tail, double *start_xytheta, double *final_xy, int *if_cut);
+
+/* alore_backend_predicted_state with DEVICE inputs and outputs, on `stream`: no allocation, no copy, no synchronisation.
+ * d_start_time and d_start_xytheta may be NULL (0 / the plan's start pose), as may any output but d_xytheta, d_vaj and d_oaj.
+ * Its d_xytheta, d_vaj and d_oaj are the start pose and start_vaj / start_oaj of a replan from the predicted state
+ * (plan_manager.hpp:587-588): alore_backend_set_paths reads them in stream order. */
+int alore_backend_predicted_state_device(alore_backend_handle h, int count, double resolution, const double *d_start_time,
+                                         const double *d_time, const double *d_start_xytheta, double *d_xytheta, double *d_vaj,
+                                         double *d_oaj, int *d_forward, void *stream);
+
+/* alore_backend_plan for the slots a DEVICE mask names (read like the mask of alore_backend_set_paths; NULL: every slot): the
+ * workgroup of a slot whose mask word is 0 returns at entry, and the stored plan, status record and history of that slot stay
+ * bit for bit.  Nothing waits: the argument block goes up from pinned memory (a second call waits for the first one's block to
+ * have left the host). */
+int alore_backend_plan_masked(alore_backend_handle h, int count, const int *mask, int mask_stride_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
