@@ -83,6 +83,23 @@ class PathsC(C.Structure):
                 ("end_yaw", C.c_void_p), ("start_vaj", C.c_void_p), ("start_oaj", C.c_void_p)]
 
 
+class MapParamsC(C.Structure):
+    """alore_backend_map_params (include/alore_backend.h)"""
+    _fields_ = [("p_hit", C.c_double), ("p_miss", C.c_double), ("p_min", C.c_double), ("p_max", C.c_double), ("p_occ", C.c_double),
+                ("detection_range", C.c_double), ("perspective", C.c_int)]
+
+
+class ScanC(C.Structure):
+    """alore_backend_scan: a cloud (host or device address) and the pose it was taken at"""
+    _fields_ = [("points", C.c_void_p), ("n_points", C.c_int), ("point_stride_bytes", C.c_int), ("odom", C.c_double * 3)]
+
+
+class MapViewC(C.Structure):
+    _fields_ = [("grid", C.c_void_p), ("log_odds", C.c_void_p), ("dist", C.c_void_p), ("count_hit", C.c_void_p),
+                ("count_all", C.c_void_p), ("nx", C.c_int), ("ny", C.c_int),
+                ("x_lo", C.c_double), ("y_lo", C.c_double), ("res", C.c_double)]
+
+
 MAX_PATH_POINTS = 31
 BUILD_OK, BUILD_MASKED, BUILD_E_POINTS, BUILD_E_PIECES = 0, 1, -1, -2
 
@@ -125,6 +142,15 @@ def _bind(L):
     L.alore_backend_get_problems.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), DP, DP, DP, DP, DP, DP, DP, C.POINTER(C.c_int)]
     L.alore_backend_predicted_state_device.argtypes = [C.c_void_p, C.c_int, C.c_double] + [C.c_void_p] * 8
     L.alore_backend_plan_masked.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.alore_backend_map_default_params.argtypes = [C.POINTER(MapParamsC)]
+    L.alore_backend_map_default_params.restype = None
+    L.alore_backend_map_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(MapParamsC)]
+    L.alore_backend_map_logodds.argtypes = [C.c_void_p, DP]
+    L.alore_backend_map_set_grid.argtypes = [C.c_void_p, C.POINTER(C.c_ubyte)]
+    L.alore_backend_map_integrate.argtypes = [C.c_void_p, C.c_int, C.POINTER(ScanC), C.c_int, C.c_int, C.c_void_p]
+    L.alore_backend_map_update_esdf.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p]
+    L.alore_backend_map_get.argtypes = [C.c_void_p, C.POINTER(C.c_ubyte), DP, DP]
+    L.alore_backend_map_device.argtypes = [C.c_void_p, C.POINTER(MapViewC)]
     L._backend_bound = True
 
 
@@ -138,6 +164,15 @@ def default_config() -> BackendConfig:
     c = BackendConfig()
     L.alore_backend_default_config(C.byref(c))
     return c
+
+
+def default_map_params() -> MapParamsC:
+    """mapsim.yaml and planner_sim.launch: 0.99, 0.35, 0.12, 0.90, 0.80, range 27 m, perspective mode"""
+    L = _lib.load()
+    _bind(L)
+    p = MapParamsC()
+    L.alore_backend_map_default_params(C.byref(p))
+    return p
 
 
 def _dp(a):
@@ -226,6 +261,85 @@ class BatchedMSPlanner:
         self._check(self.L.alore_backend_build_esdf(self.h, g.ctypes.data_as(C.POINTER(C.c_ubyte)), g.shape[0], g.shape[1], x_lo, y_lo, res,
                                                     float(odom[0]), float(odom[1]), float(detection_range), _dp(dist)))
         return dist
+
+    # ---- the resident occupancy map: point clouds in, log-odds, cell states and the ESDF updated in place on the device
+    def map_create(self, nx: int, ny: int, x_lo: float, y_lo: float, res: float, params: MapParamsC | None = None, **fields):
+        """plan_env::SDFmap on the device: all cells unknown, log-odds at clamp_min - 0.01, distances DBL_MAX.  params: a
+        MapParamsC (None: the defaults), fields: single members to change (detection_range=2.0, perspective=0, ...).  The map
+        becomes the planner's map; set_map / build_esdf end it."""
+        p = MapParamsC()
+        if params is None:
+            self.L.alore_backend_map_default_params(C.byref(p))
+        else:
+            C.memmove(C.byref(p), C.byref(params), C.sizeof(p))
+        for k, v in fields.items():
+            if k not in dict(MapParamsC._fields_):
+                raise TypeError(f"alore_backend_map_params has no field {k}")
+            setattr(p, k, v)
+        self._check(self.L.alore_backend_map_create(self.h, int(nx), int(ny), float(x_lo), float(y_lo), float(res), C.byref(p)))
+        self.map_shape = (int(nx), int(ny))
+        self.map_params = p
+
+    @property
+    def map_logodds(self) -> np.ndarray:
+        """logit of p_hit, p_miss, p_min, p_max, p_occ as the library computed them"""
+        out = np.zeros(5)
+        self._check(self.L.alore_backend_map_logodds(self.h, _dp(out)))
+        return out
+
+    def map_set_grid(self, grid: np.ndarray):
+        """seeds the cell states from a prior map ([nx][ny] of 0 unknown, 1 unoccupied, 2 occupied); waits"""
+        g = np.ascontiguousarray(grid, dtype=np.uint8)
+        if g.shape != getattr(self, "map_shape", None):
+            raise BackendError(f"map_set_grid: the grid must have the map's shape {getattr(self, 'map_shape', None)}")
+        self._check(self.L.alore_backend_map_set_grid(self.h, g.ctypes.data_as(C.POINTER(C.c_ubyte))))
+
+    def map_integrate(self, scans, update_esdf: bool = True, stream=None, point_stride_bytes: int | None = None):
+        """One updateOccupancyCallback per scan, in order, each followed (update_esdf) by updateESDF2d in its window.  scans: a list
+        of (points, odom) with odom = (x, y[, yaw]) in host values and points either NumPy [n][k >= 2] (x, y first; converted to
+        float32; uploaded, the call waits) or, for all scans, torch float32 device tensors [n][k] / raw device addresses given as
+        (address, n_points) (read in place in stream order, nothing waits).  point_stride_bytes: bytes between points for raw
+        addresses (default: the row stride of the array or tensor)."""
+        n = len(scans)
+        arr = (ScanC * max(n, 1))()
+        keep, device = [], None
+        for k, (pts, odom) in enumerate(scans):
+            a = arr[k]
+            if isinstance(pts, tuple):
+                dev, a.points, a.n_points, a.point_stride_bytes = True, int(pts[0]) or None, int(pts[1]), int(point_stride_bytes or 8)
+            elif isinstance(pts, np.ndarray) or not hasattr(pts, "data_ptr"):
+                q = np.asarray(pts, np.float32)
+                q = np.ascontiguousarray(q.reshape(len(q), -1)) if q.size else np.zeros((0, 2), np.float32)
+                keep.append(q)
+                dev, a.points, a.n_points, a.point_stride_bytes = False, q.ctypes.data if q.size else None, q.shape[0], max(q.shape[1], 2) * 4
+            else:
+                if str(pts.dtype) != "torch.float32" or pts.dim() != 2 or pts.stride(1) != 1:
+                    raise BackendError("map_integrate: device points must be a float32 tensor [n][k >= 2] with unit stride along k")
+                keep.append(pts)
+                dev, a.points, a.n_points = True, int(pts.data_ptr()) if pts.shape[0] else None, int(pts.shape[0])
+                a.point_stride_bytes = int(point_stride_bytes or pts.stride(0) * 4)
+            if device is not None and dev != device:
+                raise BackendError("map_integrate: the scans of one call are all host arrays or all device tensors")
+            device = dev
+            a.odom[0], a.odom[1], a.odom[2] = float(odom[0]), float(odom[1]), float(odom[2]) if len(odom) > 2 else 0.0
+        self._check(self.L.alore_backend_map_integrate(self.h, n, arr, int(bool(device)), int(bool(update_esdf)), _stream(stream)))
+
+    def map_update_esdf(self, odom, detection_range: float | None = None, stream=None):
+        """updateESDF2d alone in the window odom +- detection_range (None: the map's own); asynchronous"""
+        r = self.map_params.detection_range if detection_range is None else float(detection_range)
+        self._check(self.L.alore_backend_map_update_esdf(self.h, float(odom[0]), float(odom[1]), r, _stream(stream)))
+
+    def map_state(self) -> dict:
+        """the resident map copied to the host (waits): grid uint8 [nx][ny], log_odds and dist float64 [nx][ny]"""
+        shape = getattr(self, "map_shape", (0, 0))
+        grid, lo, dist = np.zeros(shape, np.uint8), np.zeros(shape), np.zeros(shape)
+        self._check(self.L.alore_backend_map_get(self.h, grid.ctypes.data_as(C.POINTER(C.c_ubyte)), _dp(lo), _dp(dist)))
+        return {"grid": grid, "log_odds": lo, "dist": dist}
+
+    def map_device(self) -> MapViewC:
+        v = MapViewC()
+        self._check(self.L.alore_backend_map_device(self.h, C.byref(v)))
+        return v
 
     def predicted_state(self, times, resolution: float = 0.01, start_times=None, start_xytheta=None):
         """MSPlanner::get_the_predicted_state[_and_path] for the plans of the last launch"""

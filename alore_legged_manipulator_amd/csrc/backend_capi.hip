@@ -52,6 +52,17 @@ struct alore_backend_planner {
     backend::Params* h_params = nullptr;
     hipEvent_t ev_params = nullptr;
     bool params_pending = false;
+    // the resident occupancy map (alore_backend_map_create): state grid, log-odds and counts; its distance field is d_map.  The
+    // argument blocks of up to MAP_SCANS scans go up from pinned memory in one copy
+    bool resident = false;
+    backend::OccMap omap{};
+    backend::EsdfWorkspace esdf_ws{};
+    char *h_scan = nullptr, *d_scan = nullptr;
+    size_t scan_block = 0;
+    hipEvent_t ev_scan = nullptr, ev_scan_done = nullptr; // the upload of the previous blocks has left h_scan; their kernels have ended
+    bool scan_pending = false;
+    char* d_points = nullptr; // staging of host points (grows)
+    size_t points_bytes = 0;
 };
 
 namespace {
@@ -78,8 +89,32 @@ hipError_t dalloc(T** p, size_t count)
     return e;
 }
 
+constexpr int MAP_SCANS = 8; // scans per upload of argument blocks
+
+// ends the resident occupancy map; the distance field (d_map) stays the handle's map
+void end_map(alore_backend_handle h)
+{
+    if (!h->resident && !h->h_scan && !h->d_points) return;
+    (void)hipDeviceSynchronize();
+    void* ptrs[] = {h->omap.grid, h->omap.log_odds, h->omap.count_hit, h->omap.count_all, h->esdf_ws.tmp, h->esdf_ws.pos, h->esdf_ws.neg,
+                    h->esdf_ws.v, h->esdf_ws.z, h->d_scan, h->d_points};
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+    if (h->h_scan) (void)hipHostFree(h->h_scan);
+    delete[] h->omap.h_row;
+    h->omap = backend::OccMap{};
+    h->esdf_ws = backend::EsdfWorkspace{};
+    h->h_scan = h->d_scan = h->d_points = nullptr;
+    h->points_bytes = 0;
+    h->scan_pending = false;
+    h->resident = false;
+}
+
 void free_all(alore_backend_handle h)
 {
+    end_map(h);
+    if (h->ev_scan) (void)hipEventDestroy(h->ev_scan);
+    if (h->ev_scan_done) (void)hipEventDestroy(h->ev_scan_done);
     if (h->d_stamps) {
         long long st[64];
         if (hipMemcpy(st, h->d_stamps, sizeof(st), hipMemcpyDeviceToHost) == hipSuccess) {
@@ -256,6 +291,7 @@ int alore_backend_set_map(alore_backend_handle h, const double* dist, int nx, in
 {
     if (!h || !dist || nx < 2 || ny < 2 || !(res > 0.0)) return fail(h, ALORE_BE_E_INVALID, "set_map: bad argument");
     BE_TRY(h, hipSetDevice(h->device));
+    end_map(h);
     if (h->d_map) { (void)hipFree(h->d_map); h->d_map = nullptr; }
     BE_TRY(h, hipMalloc((void**)&h->d_map, sizeof(double) * (size_t)nx * ny));
     BE_TRY(h, hipMemcpy(h->d_map, dist, sizeof(double) * (size_t)nx * ny, hipMemcpyHostToDevice));
@@ -268,6 +304,7 @@ int alore_backend_build_esdf(alore_backend_handle h, const unsigned char* grid, 
 {
     if (!h || !grid || nx < 2 || ny < 2 || !(res > 0.0) || !(detection_range > 0.0)) return fail(h, ALORE_BE_E_INVALID, "build_esdf: bad argument");
     BE_TRY(h, hipSetDevice(h->device));
+    end_map(h);
     const size_t n = (size_t)nx * ny;
     const bool same = h->d_map && h->map.nx == nx && h->map.ny == ny && h->map.x_lo == x_lo && h->map.y_lo == y_lo && h->map.res == res;
     if (!same) {
@@ -721,6 +758,195 @@ int alore_backend_lbfgs(alore_backend_handle h, int count, int stage, double* x,
 {
     return run_piece(h, count, backend::MODE_LBFGS, stage, x, lam, rho, safe_dis, time_weight, max_iter, cost, nullptr, ret, iters, evals,
                      xy_err, stream);
+}
+
+// ---- the resident occupancy map ----------------------------------------------------------------------------------------------
+void alore_backend_map_default_params(alore_backend_map_params* p)
+{
+    std::memset(p, 0, sizeof(*p));
+    p->p_hit = 0.99; p->p_miss = 0.35; p->p_min = 0.12; p->p_max = 0.90; p->p_occ = 0.80; // plan_env/config/mapsim.yaml
+    p->detection_range = 27.0; p->perspective = 1;                                           // planner_sim.launch
+}
+
+int alore_backend_map_create(alore_backend_handle h, int nx, int ny, double x_lo, double y_lo, double res, const alore_backend_map_params* params)
+{
+    if (!h) return ALORE_BE_E_INVALID;
+    alore_backend_map_params prm;
+    if (params) prm = *params; else alore_backend_map_default_params(&prm);
+    auto prob = [](double p) { return p > 0.0 && p < 1.0; };
+    if (nx < 2 || ny < 2 || nx > 32768 || ny > 32768 || !(res > 0.0) || !std::isfinite(res) || !std::isfinite(x_lo) || !std::isfinite(y_lo))
+        return fail(h, ALORE_BE_E_INVALID, "map_create: bad geometry");
+    if (!prob(prm.p_hit) || !prob(prm.p_miss) || !prob(prm.p_min) || !prob(prm.p_max) || !prob(prm.p_occ) || !(prm.p_min < prm.p_max) ||
+        !(prm.detection_range > 0.0) || !std::isfinite(prm.detection_range) || !(prm.detection_range / res < 1.0e6))
+        return fail(h, ALORE_BE_E_INVALID, "map_create: probabilities must lie in (0, 1) with p_min < p_max, detection_range must be positive");
+    BE_TRY(h, hipSetDevice(h->device));
+    end_map(h);
+    if (h->d_map) { (void)hipFree(h->d_map); h->d_map = nullptr; }
+    h->map = backend::MapView{};
+    const size_t n = (size_t)nx * ny;
+    backend::OccMap& m = h->omap;
+    m.nx = nx; m.ny = ny; m.x_lo = x_lo; m.y_lo = y_lo; m.res = res; m.range = prm.detection_range; m.perspective = prm.perspective != 0;
+    backend::occ_log_odds(prm, m.log_odds5);
+    m.h_row = new (std::nothrow) double[(size_t)backend::occ_lattice_cap(m.range, res)];
+    backend::EsdfWorkspace& w = h->esdf_ws;
+    backend::esdf_workspace_size(nx, ny, res, m.range, &w.cells, &w.lines);
+    h->scan_block = backend::occ_block_bytes(nx, ny);
+    hipError_t e = m.h_row ? hipSuccess : hipErrorOutOfMemory;
+    auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    // the ESDF's window can end one cell past the map where ceil((nx res) / res) or ceil((ny res) / res) rounds up (as in the
+    // reference): esdf_rows then reads up to the whole row nx, cells n .. n + ny.  They are zeros (unknown) here, not whatever
+    // follows the allocation
+    A(dalloc(&m.grid, n + (size_t)ny + 1)); A(dalloc(&m.count_hit, n)); A(dalloc(&m.count_all, n));
+    if (e == hipSuccess) e = hipMalloc((void**)&m.log_odds, sizeof(double) * n);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_map, sizeof(double) * n);
+    if (e == hipSuccess) e = hipMalloc((void**)&w.tmp, sizeof(double) * w.cells);
+    if (e == hipSuccess) e = hipMalloc((void**)&w.pos, sizeof(double) * w.cells);
+    if (e == hipSuccess) e = hipMalloc((void**)&w.neg, sizeof(double) * w.cells);
+    if (e == hipSuccess) e = hipMalloc((void**)&w.v, sizeof(int) * (size_t)w.lines * (w.lines + 2));
+    if (e == hipSuccess) e = hipMalloc((void**)&w.z, sizeof(double) * (size_t)w.lines * (w.lines + 3));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_scan, h->scan_block * MAP_SCANS);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_scan, h->scan_block * MAP_SCANS, hipHostMallocDefault);
+    if (e == hipSuccess && !h->ev_scan) e = hipEventCreateWithFlags(&h->ev_scan, hipEventDisableTiming);
+    if (e == hipSuccess && !h->ev_scan_done) e = hipEventCreateWithFlags(&h->ev_scan_done, hipEventDisableTiming);
+    if (e == hipSuccess) e = backend::occ_fill(m.log_odds, n, m.log_odds5[2] - 0.01, nullptr);
+    if (e == hipSuccess) e = backend::esdf_fill_max(h->d_map, n, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    h->resident = true; // end_map frees what was allocated
+    if (e != hipSuccess) {
+        end_map(h);
+        if (h->d_map) { (void)hipFree(h->d_map); h->d_map = nullptr; }
+        return fail(h, e == hipErrorOutOfMemory ? ALORE_BE_E_NOMEM : ALORE_BE_E_HIP, "map_create", e);
+    }
+    h->map = backend::MapView{h->d_map, nx, ny, x_lo, y_lo, x_lo + nx * res, y_lo + ny * res, res};
+    return ALORE_BE_OK;
+}
+
+#define BE_MAP(h, what)                                                                                                   \
+    do {                                                                                                                  \
+        if (!h) return ALORE_BE_E_INVALID;                                                                                \
+        if (!h->resident) return fail(h, ALORE_BE_E_INVALID, what ": no resident map (alore_backend_map_create; alore_backend_set_map and alore_backend_build_esdf end it)"); \
+    } while (0)
+
+int alore_backend_map_logodds(alore_backend_handle h, double out[5])
+{
+    BE_MAP(h, "map_logodds");
+    if (!out) return fail(h, ALORE_BE_E_INVALID, "map_logodds: bad argument");
+    std::memcpy(out, h->omap.log_odds5, sizeof(double) * 5);
+    return ALORE_BE_OK;
+}
+
+int alore_backend_map_set_grid(alore_backend_handle h, const unsigned char* grid)
+{
+    BE_MAP(h, "map_set_grid");
+    if (!grid) return fail(h, ALORE_BE_E_INVALID, "map_set_grid: bad argument");
+    const size_t n = (size_t)h->omap.nx * h->omap.ny;
+    for (size_t c = 0; c < n; ++c)
+        if (grid[c] > 2) return fail(h, ALORE_BE_E_INVALID, "map_set_grid: a cell state is not 0, 1 or 2");
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, hipDeviceSynchronize());
+    BE_TRY(h, hipMemcpy(h->omap.grid, grid, n, hipMemcpyHostToDevice));
+    return ALORE_BE_OK;
+}
+
+int alore_backend_map_integrate(alore_backend_handle h, int n_scans, const alore_backend_scan* scans, int device_points, int update_esdf,
+                                void* stream)
+{
+    BE_MAP(h, "map_integrate");
+    if (n_scans < 1 || !scans) return fail(h, ALORE_BE_E_INVALID, "map_integrate: bad argument");
+    const backend::OccMap& m = h->omap;
+    size_t stage = 0;
+    for (int k = 0; k < n_scans; ++k) {
+        const alore_backend_scan& sc = scans[k];
+        if (sc.n_points < 0 || (sc.n_points > 0 && !sc.points) || sc.point_stride_bytes < 8 || sc.point_stride_bytes % 4)
+            return fail(h, ALORE_BE_E_INVALID, "map_integrate: a scan needs n_points >= 0, points, and a stride that is a multiple of 4 and at least 8");
+        if (!(sc.odom[0] > m.x_lo && sc.odom[0] < m.x_lo + m.nx * m.res && sc.odom[1] > m.y_lo && sc.odom[1] < m.y_lo + m.ny * m.res))
+            return fail(h, ALORE_BE_E_INVALID, "map_integrate: the sensor position of a scan is not strictly inside the map");
+        if (sc.n_points > 0) stage += (((size_t)(sc.n_points - 1) * sc.point_stride_bytes + 8) + 15) & ~size_t(15);
+    }
+    BE_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (!device_points && stage > h->points_bytes) {
+        BE_TRY(h, hipDeviceSynchronize()); // an earlier call on another stream may still read the old buffer
+        if (h->d_points) { (void)hipFree(h->d_points); h->d_points = nullptr; h->points_bytes = 0; }
+        BE_TRY(h, hipMalloc((void**)&h->d_points, stage));
+        h->points_bytes = stage;
+    }
+    // the map_integrate and map_update_esdf calls before (on whatever stream) have read their blocks and left the ESDF workspace;
+    // an event that was never recorded does not hold the stream
+    BE_TRY(h, hipStreamWaitEvent(s, h->ev_scan_done, 0));
+    size_t at = 0;
+    for (int first = 0; first < n_scans; first += MAP_SCANS) {
+        const int chunk = std::min(MAP_SCANS, n_scans - first);
+        if (h->scan_pending) BE_TRY(h, hipEventSynchronize(h->ev_scan)); // the pinned blocks are free again
+        h->scan_pending = false;
+        for (int k = 0; k < chunk; ++k) {
+            const alore_backend_scan& sc = scans[first + k];
+            const char* pts = (const char*)sc.points;
+            if (!device_points && sc.n_points > 0) {
+                const size_t bytes = (size_t)(sc.n_points - 1) * sc.point_stride_bytes + 8;
+                BE_TRY(h, hipMemcpyAsync(h->d_points + at, sc.points, bytes, hipMemcpyHostToDevice, s));
+                pts = h->d_points + at;
+                at += (bytes + 15) & ~size_t(15);
+            }
+            if (!backend::occ_prepare_scan(m, sc.odom[0], sc.odom[1], pts, sc.n_points, sc.point_stride_bytes, h->h_scan + k * h->scan_block,
+                                           h->d_scan + k * h->scan_block))
+                return fail(h, ALORE_BE_E_INVALID, "map_integrate: the sensor position of a scan is not strictly inside the map");
+        }
+        BE_TRY(h, hipMemcpyAsync(h->d_scan, h->h_scan, h->scan_block * chunk, hipMemcpyHostToDevice, s));
+        BE_TRY(h, hipEventRecord(h->ev_scan, s));
+        h->scan_pending = true;
+        for (int k = 0; k < chunk; ++k) {
+            const alore_backend_scan& sc = scans[first + k];
+            BE_TRY(h, backend::occ_enqueue_scan(h->h_scan + k * h->scan_block, h->d_scan + k * h->scan_block, s));
+            if (update_esdf) {
+                int empty = 0;
+                BE_TRY(h, backend::esdf_enqueue(m.grid, m.nx, m.ny, m.res, m.x_lo, m.y_lo, sc.odom[0], sc.odom[1], m.range, h->d_map, h->esdf_ws, s, &empty));
+            }
+        }
+        BE_TRY(h, hipEventRecord(h->ev_scan_done, s));
+    }
+    if (!device_points) BE_TRY(h, hipStreamSynchronize(s));
+    return ALORE_BE_OK;
+}
+
+int alore_backend_map_update_esdf(alore_backend_handle h, double odom_x, double odom_y, double detection_range, void* stream)
+{
+    BE_MAP(h, "map_update_esdf");
+    if (!std::isfinite(odom_x) || !std::isfinite(odom_y) || !(detection_range > 0.0) || !std::isfinite(detection_range))
+        return fail(h, ALORE_BE_E_INVALID, "map_update_esdf: bad argument");
+    BE_TRY(h, hipSetDevice(h->device));
+    const backend::OccMap& m = h->omap;
+    int empty = 0;
+    // one ESDF workspace serves every call: wait for the map_integrate or map_update_esdf before, on whatever stream it ran
+    BE_TRY(h, hipStreamWaitEvent((hipStream_t)stream, h->ev_scan_done, 0));
+    const hipError_t e = backend::esdf_enqueue(m.grid, m.nx, m.ny, m.res, m.x_lo, m.y_lo, odom_x, odom_y, detection_range, h->d_map, h->esdf_ws,
+                                               (hipStream_t)stream, &empty);
+    if (e == hipErrorInvalidValue) return fail(h, ALORE_BE_E_INVALID, "map_update_esdf: the window is larger than the map's detection range allows");
+    if (e != hipSuccess) return fail(h, ALORE_BE_E_HIP, "map_update_esdf", e);
+    if (empty) return fail(h, ALORE_BE_E_INVALID, "map_update_esdf: the window around the odometry does not intersect the map");
+    BE_TRY(h, hipEventRecord(h->ev_scan_done, (hipStream_t)stream));
+    return ALORE_BE_OK;
+}
+
+int alore_backend_map_get(alore_backend_handle h, unsigned char* grid, double* log_odds, double* dist)
+{
+    BE_MAP(h, "map_get");
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, hipDeviceSynchronize());
+    const size_t n = (size_t)h->omap.nx * h->omap.ny;
+    if (grid) BE_TRY(h, hipMemcpy(grid, h->omap.grid, n, hipMemcpyDeviceToHost));
+    if (log_odds) BE_TRY(h, hipMemcpy(log_odds, h->omap.log_odds, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (dist) BE_TRY(h, hipMemcpy(dist, h->d_map, sizeof(double) * n, hipMemcpyDeviceToHost));
+    return ALORE_BE_OK;
+}
+
+int alore_backend_map_device(alore_backend_handle h, alore_backend_map_view* out)
+{
+    BE_MAP(h, "map_device");
+    if (!out) return fail(h, ALORE_BE_E_INVALID, "map_device: bad argument");
+    const backend::OccMap& m = h->omap;
+    *out = alore_backend_map_view{m.grid, m.log_odds, h->d_map, m.count_hit, m.count_all, m.nx, m.ny, m.x_lo, m.y_lo, m.res};
+    return ALORE_BE_OK;
 }
 
 } // extern "C"

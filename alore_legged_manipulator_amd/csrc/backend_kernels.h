@@ -150,5 +150,37 @@ hipError_t path_points(const PathArgs& g, hipStream_t s);
 hipError_t esdf_fill_max(double* p, size_t n, hipStream_t s);
 hipError_t esdf_update(const unsigned char* d_grid, int GLX, int GLY, double res, double x_lo, double y_lo, double odom_x, double odom_y,
                        double range, double* d_dist, hipStream_t s, int* empty_window);
+// the same five kernels with a caller-owned workspace: enqueues and returns (no allocation, no wait)
+struct EsdfWorkspace {
+    double *tmp, *pos, *neg, *z; // tmp, pos, neg: [cells]; z: [lines (lines + 3)]
+    int* v;                      // [lines (lines + 2)]
+    size_t cells;                // capacity: (X + 1) (Y + 1) of the largest window
+    int lines;                   // capacity: max(X, Y) + 1
+};
+void esdf_workspace_size(int GLX, int GLY, double res, double range, size_t* cells, int* lines);
+hipError_t esdf_enqueue(const unsigned char* d_grid, int GLX, int GLY, double res, double x_lo, double y_lo, double odom_x, double odom_y,
+                        double range, double* d_dist, const EsdfWorkspace& w, hipStream_t s, int* empty_window);
+
+// occupancy_map.hip: the resident occupancy map (plan_env::SDFmap before updateESDF2d), arithmetic in occupancy_update.h
+struct OccMap {
+    int nx, ny;
+    double x_lo, y_lo, res, range; // range: detection_range
+    int perspective;
+    double log_odds5[5];           // hit, miss, min, max, occ
+    unsigned char* grid;           // [nx][ny] cell states (device)
+    double* log_odds;              // [nx][ny] (device)
+    int *count_hit, *count_all;    // [nx][ny], zero between scans (device)
+    double* h_row;                 // host scratch: one coordinate row of the RemoveOutliers lattice, occ_lattice_cap doubles
+};
+void occ_log_odds(const alore_backend_map_params& p, double out[5]);
+int occ_lattice_cap(double range, double res);
+// the argument block of one scan: the kernels' arguments, then the marks of the lattice's columns [nx] and rows [ny]
+size_t occ_block_bytes(int nx, int ny);
+// fills the host copy of a scan's block (device addresses refer to d_block); false: the sensor is not strictly inside the map
+bool occ_prepare_scan(const OccMap& m, double odom_x, double odom_y, const char* d_points, int n_points, int stride_bytes, char* h_block,
+                      const char* d_block);
+// launches the kernels of the scan whose block has been copied to d_block in stream order
+hipError_t occ_enqueue_scan(const char* h_block, const char* d_block, hipStream_t s);
+hipError_t occ_fill(double* p, size_t n, double value, hipStream_t s);
 
 } // namespace backend

@@ -121,7 +121,43 @@ hipError_t esdf_fill_max(double* p, size_t n, hipStream_t s)
     return hipGetLastError();
 }
 
-// d_grid: device copy of the state grid; d_dist: the map the optimiser reads (updated in the window)
+// the largest window of a map of GLX x GLY cells at this detection range: (X + 1) <= xc, (Y + 1) <= yc
+void esdf_workspace_size(int GLX, int GLY, double res, double range, size_t* cells, int* lines)
+{
+    const double span = ceil(2.0 * range / res) + 3.0;
+    const int xc = span < GLX + 1 ? (int)span : GLX + 1, yc = span < GLY + 1 ? (int)span : GLY + 1;
+    *cells = (size_t)xc * yc;
+    *lines = xc > yc ? xc : yc;
+}
+
+// d_grid: device copy of the state grid; d_dist: the map the optimiser reads (updated in the window).  Enqueues the five kernels
+// on `s` with the caller's workspace (tmp, pos, neg: w.cells doubles; v: w.lines (w.lines + 2) ints; z: w.lines (w.lines + 3)
+// doubles) and returns: nothing is allocated and nothing waits.  A window that the workspace does not hold is refused.
+hipError_t esdf_enqueue(const unsigned char* d_grid, int GLX, int GLY, double res, double x_lo, double y_lo, double odom_x, double odom_y,
+                        double range, double* d_dist, const EsdfWorkspace& w, hipStream_t s, int* empty_window)
+{
+    const double inv = 1.0 / res, gx = GLX * res, gy = GLY * res;
+    const int min_x = (int)floor(fmax(0.0, odom_x - range - x_lo) * inv), min_y = (int)floor(fmax(0.0, odom_y - range - y_lo) * inv);
+    const int max_x = (int)ceil(fmin(gx, odom_x + range - x_lo) * inv) - 1, max_y = (int)ceil(fmin(gy, odom_y + range - y_lo) * inv) - 1;
+    const int X = max_x - min_x, Y = max_y - min_y;
+    *empty_window = (X < 1 || Y < 1) ? 1 : 0;
+    if (*empty_window) return hipSuccess;
+    const size_t total = (size_t)(X + 1) * (Y + 1);
+    const int D = (X > Y ? X : Y) + 1;
+    if (total > w.cells || D > w.lines) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(w.pos, 0, sizeof(double) * total, s);
+    if (e == hipSuccess) e = hipMemsetAsync(w.neg, 0, sizeof(double) * total, s);
+    if (e != hipSuccess) return e;
+    for (int pass = 0; pass < 2; ++pass) {
+        EsdfArgs a{d_grid, GLY, min_x, min_y, X, Y, res, w.tmp, pass == 0 ? w.pos : w.neg, w.v, w.z, D, pass};
+        esdf_rows<<<(X + 64) / 64, 64, 0, s>>>(a);
+        esdf_cols<<<(Y + 64) / 64, 64, 0, s>>>(a);
+    }
+    esdf_combine<<<(unsigned)(((size_t)X * Y + 255) / 256), 256, 0, s>>>(w.pos, w.neg, d_dist, GLY, min_x, min_y, X, Y, res);
+    return hipGetLastError();
+}
+
+// the same with buffers of its own, sized for this window: allocates, waits for the stream and frees
 hipError_t esdf_update(const unsigned char* d_grid, int GLX, int GLY, double res, double x_lo, double y_lo, double odom_x, double odom_y,
                        double range, double* d_dist, hipStream_t s, int* empty_window)
 {
@@ -133,26 +169,17 @@ hipError_t esdf_update(const unsigned char* d_grid, int GLX, int GLY, double res
     if (*empty_window) return hipSuccess;
     const size_t total = (size_t)(X + 1) * (Y + 1);
     const int D = (X > Y ? X : Y) + 1, lines = D;
-    double *tmp = nullptr, *pos = nullptr, *neg = nullptr, *z = nullptr;
-    int* v = nullptr;
-    hipError_t e = hipMalloc((void**)&tmp, sizeof(double) * total);
-    if (e == hipSuccess) e = hipMalloc((void**)&pos, sizeof(double) * total);
-    if (e == hipSuccess) e = hipMalloc((void**)&neg, sizeof(double) * total);
-    if (e == hipSuccess) e = hipMalloc((void**)&v, sizeof(int) * (size_t)lines * (D + 2));
-    if (e == hipSuccess) e = hipMalloc((void**)&z, sizeof(double) * (size_t)lines * (D + 3));
-    if (e == hipSuccess) e = hipMemsetAsync(pos, 0, sizeof(double) * total, s);
-    if (e == hipSuccess) e = hipMemsetAsync(neg, 0, sizeof(double) * total, s);
-    if (e == hipSuccess) {
-        for (int pass = 0; pass < 2; ++pass) {
-            EsdfArgs a{d_grid, GLY, min_x, min_y, X, Y, res, tmp, pass == 0 ? pos : neg, v, z, D, pass};
-            esdf_rows<<<(X + 64) / 64, 64, 0, s>>>(a);
-            esdf_cols<<<(Y + 64) / 64, 64, 0, s>>>(a);
-        }
-        esdf_combine<<<(unsigned)(((size_t)X * Y + 255) / 256), 256, 0, s>>>(pos, neg, d_dist, GLY, min_x, min_y, X, Y, res);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-    }
-    (void)hipFree(tmp); (void)hipFree(pos); (void)hipFree(neg); (void)hipFree(v); (void)hipFree(z);
+    EsdfWorkspace w{};
+    w.cells = total;
+    w.lines = lines;
+    hipError_t e = hipMalloc((void**)&w.tmp, sizeof(double) * total);
+    if (e == hipSuccess) e = hipMalloc((void**)&w.pos, sizeof(double) * total);
+    if (e == hipSuccess) e = hipMalloc((void**)&w.neg, sizeof(double) * total);
+    if (e == hipSuccess) e = hipMalloc((void**)&w.v, sizeof(int) * (size_t)lines * (D + 2));
+    if (e == hipSuccess) e = hipMalloc((void**)&w.z, sizeof(double) * (size_t)lines * (D + 3));
+    if (e == hipSuccess) e = esdf_enqueue(d_grid, GLX, GLY, res, x_lo, y_lo, odom_x, odom_y, range, d_dist, w, s, empty_window);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(w.tmp); (void)hipFree(w.pos); (void)hipFree(w.neg); (void)hipFree(w.v); (void)hipFree(w.z);
     return e;
 }
 

@@ -261,6 +261,75 @@ int alore_backend_predicted_state_device(alore_backend_handle h, int count, doub
  * have left the host). */
 int alore_backend_plan_masked(alore_backend_handle h, int count, const int *mask, int mask_stride_bytes, void *stream);
 
+/* ---- the resident occupancy map: point clouds in, ESDF out, on the device ------------------------------------- */
+/* The half of plan_env::SDFmap that runs before updateESDF2d (sdf_map.cpp: updateOccupancyCallback :35-130, raycastProcess
+ * :132-175, updateOccupancyMap :281-314, RemoveOutliers :316-350), then updateESDF2d itself, on a map that stays on the device:
+ * occupancy log-odds, the cell-state grid (0 unknown, 1 unoccupied, 2 occupied) and the distance field are updated in place, and
+ * the distance field is the map that alore_backend_plan, alore_backend_plan_masked and alore_backend_check_plans read.  Grids are
+ * [nx][ny], cell (ix, iy) at ix * ny + iy, x_hi = x_lo + nx * res.  csrc/occupancy_update.h holds the arithmetic and lists the
+ * deviations from the reference (int counts, non-finite points skipped, a sensor outside the map refused, no access outside the
+ * map at its edge).  Out of scope: the JPS search and removeCornerPts, cirSupRaycastProcess (off in both launch files), TF lookups
+ * and PCL conversion (the caller hands over points in the world frame), the laser simulator. */
+typedef struct alore_backend_map_params {
+    double p_hit, p_miss, p_min, p_max, p_occ; /* probabilities in (0, 1); their logits are the log-odds of the update */
+    double detection_range;
+    int perspective;                           /* if_perspective: 0 raycast and log-odds, 1 window free and points occupied */
+} alore_backend_map_params;
+/* 0.99, 0.35, 0.12, 0.90, 0.80 (plan_env/config/mapsim.yaml), 27.0 and 1 (planner_sim.launch) */
+void alore_backend_map_default_params(alore_backend_map_params *p);
+/* Allocates, once: the state grid (all unknown), the log-odds (clamp_min - 0.01, sdf_map.h:179-180), two count arrays, the
+ * distance field (DBL_MAX) as the handle's map, the ESDF workspace for the largest window of this geometry and detection range,
+ * and a pinned argument block.  params NULL: the defaults.  Replaces a map set before.
+ * A later alore_backend_set_map or alore_backend_build_esdf behaves exactly as without a resident map and ENDS it: the
+ * alore_backend_map_* calls below return ALORE_BE_E_INVALID until the next alore_backend_map_create. */
+int alore_backend_map_create(alore_backend_handle h, int nx, int ny, double x_lo, double y_lo, double res,
+                             const alore_backend_map_params *params);
+/* the log-odds as computed on the host, log(p / (1 - p)): hit, miss, min, max, occ */
+int alore_backend_map_logodds(alore_backend_handle h, double out[5]);
+/* seeds the state grid from a prior map: grid is HOST memory [nx][ny]; synchronises */
+int alore_backend_map_set_grid(alore_backend_handle h, const unsigned char *grid);
+/* one cloud with the pose it was taken at */
+typedef struct alore_backend_scan {
+    const float *points;    /* x, y of point i at (char *)points + i * point_stride_bytes: HOST or DEVICE memory (the call says) */
+    int n_points;           /* may be 0: a cycle without rays */
+    int point_stride_bytes; /* a multiple of 4, at least 8: 8 for x, y pairs, 12 for x, y, z, 16 for a PCL PointXYZ array */
+    double odom[3];         /* x, y, yaw of the sensor in the world frame (HOST values: the pose arrives with the cloud) */
+} alore_backend_scan;
+/* The scans in order, each a full cycle of updateOccupancyCallback: in raycast mode the rays' counts, the log-odds update,
+ * RemoveOutliers on the state grid of the previous cycle, the state update; in perspective mode the window and the points.  With
+ * update_esdf != 0 every scan is followed by updateESDF2d in that scan's window, odom +- detection_range, as in the reference
+ * (its distances depend on the window); a window of less than two cells a side is left out.  A scan whose sensor position is not
+ * strictly inside the map makes the call return ALORE_BE_E_INVALID before anything is enqueued.  With fewer than 32768 rays
+ * through one cell per scan the result is the reference's, which counts in shorts; beyond that (the sensor's cell of a cloud of
+ * 32768 valid points or more) the reference's total wraps negative and the cell takes a hit update, here the count stays exact
+ * and the cell is a miss.
+ * device_points != 0: the points are DEVICE memory, read in stream order; nothing is allocated, nothing crosses the bus but the
+ * argument block and nothing waits (a second call waits for the first one's block to have left the host, and so does every eighth
+ * scan of one call).  The next alore_backend_check_plans or plan launch on the same stream sees the new map.
+ * device_points == 0: the points are HOST memory; they are uploaded through a staging buffer that grows when needed, and the
+ * stream is synchronised before the call returns. */
+int alore_backend_map_integrate(alore_backend_handle h, int n_scans, const alore_backend_scan *scans, int device_points, int update_esdf,
+                                void *stream);
+/* updateESDF2d alone in a window of the caller's choice, odom +- detection_range (no larger than the map's own detection range:
+ * the workspace is sized for that); asynchronous.  map_integrate and map_update_esdf share one ESDF workspace and one argument
+ * block: each call waits on `stream` (a device-side wait, the host does not block) for the map_integrate or map_update_esdf
+ * call before it, on whatever stream that ran, so the calls may use different streams.  They are not safe to issue from two host
+ * threads at once, like every call on one handle.  Readers of the map on ANOTHER stream (check_plans, plan) must be ordered
+ * after the update by the caller; map_set_grid and map_get synchronise the device. */
+int alore_backend_map_update_esdf(alore_backend_handle h, double odom_x, double odom_y, double detection_range, void *stream);
+/* copies to HOST arrays [nx][ny]; any pointer may be NULL; waits for the device */
+int alore_backend_map_get(alore_backend_handle h, unsigned char *grid, double *log_odds, double *dist);
+/* device pointers of the resident map and its geometry; valid until the map ends */
+typedef struct alore_backend_map_view {
+    unsigned char *grid;
+    double *log_odds;
+    double *dist;
+    const int *count_hit, *count_all; /* the rays' counts of a scan in flight; zero between scans */
+    int nx, ny;
+    double x_lo, y_lo, res;
+} alore_backend_map_view;
+int alore_backend_map_device(alore_backend_handle h, alore_backend_map_view *out);
+
 #ifdef __cplusplus
 }
 #endif
