@@ -100,7 +100,14 @@ class MapViewC(C.Structure):
                 ("x_lo", C.c_double), ("y_lo", C.c_double), ("res", C.c_double)]
 
 
+class SearchParamsC(C.Structure):
+    """alore_backend_search_params (include/alore_backend.h)"""
+    _fields_ = [("safe_dis", C.c_double), ("window_margin", C.c_double)]
+
+
 MAX_PATH_POINTS = 31
+SEARCH_OK, SEARCH_MASKED, SEARCH_E_ENDPOINT, SEARCH_E_SAME_CELL, SEARCH_E_WINDOW, SEARCH_E_NO_PATH, SEARCH_E_POINTS = 0, 1, -1, -2, -3, -4, -5
+SEARCH_MAX_CELLS = 32768
 BUILD_OK, BUILD_MASKED, BUILD_E_POINTS, BUILD_E_PIECES = 0, 1, -1, -2
 
 
@@ -151,6 +158,15 @@ def _bind(L):
     L.alore_backend_map_update_esdf.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p]
     L.alore_backend_map_get.argtypes = [C.c_void_p, C.POINTER(C.c_ubyte), DP, DP]
     L.alore_backend_map_device.argtypes = [C.c_void_p, C.POINTER(MapViewC)]
+    L.alore_backend_search_default_params.argtypes = [C.POINTER(SearchParamsC)]
+    L.alore_backend_search_default_params.restype = None
+    L.alore_backend_search_paths.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(SearchParamsC), C.c_int,
+                                             C.c_void_p, C.c_int, C.c_void_p]
+    L.alore_backend_device_paths.argtypes = [C.c_void_p, C.POINTER(PathsC)]
+    L.alore_backend_device_search_status.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.alore_backend_search_status.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.alore_backend_search_sweeps.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.alore_backend_get_paths.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), DP, C.POINTER(C.c_int)]
     L._backend_bound = True
 
 
@@ -172,6 +188,24 @@ def default_map_params() -> MapParamsC:
     _bind(L)
     p = MapParamsC()
     L.alore_backend_map_default_params(C.byref(p))
+    return p
+
+
+def default_search_params() -> SearchParamsC:
+    """jps_safe_dis of jps3ms.yaml (0.3) and a window margin of 3 m"""
+    L = _lib.load()
+    _bind(L)
+    p = SearchParamsC()
+    L.alore_backend_search_default_params(C.byref(p))
+    return p
+
+
+def _search_params(safe_dis, window_margin) -> SearchParamsC:
+    p = default_search_params()
+    if safe_dis is not None:
+        p.safe_dis = float(safe_dis)
+    if window_margin is not None:
+        p.window_margin = float(window_margin)
     return p
 
 
@@ -447,6 +481,70 @@ class BatchedMSPlanner:
         self._check(self.L.alore_backend_get_problems(self.h, n, out["n_pieces"].ctypes.data_as(ip), _dp(out["inner"]), _dp(out["init_T"]),
                                                       _dp(out["positions"]), _dp(out["head"]), _dp(out["tail"]), _dp(out["start_xytheta"]),
                                                       _dp(out["final_xy"]), out["if_cut"].ctypes.data_as(ip)))
+        return out
+
+    # ---- way-point paths by grid search on the handle's map (alore_backend_search_paths)
+    def search_paths(self, start_xy, goal_xy, safe_dis=None, window_margin=None, mask=None):
+        """Shortest 8-connected paths on the current map from start_xy [count][>= 2] to goal_xy [count][>= 2] (NumPy; x, y first),
+        pruned like removeCornerPts, into the device slab of device_paths().  safe_dis / window_margin None: 0.3 / 3.0.  mask: per
+        slot, 0 leaves the slot out.  Waits; raises when a slot fails (search_status() says which and why)."""
+        st = np.ascontiguousarray(np.asarray(start_xy, np.float64).reshape(len(start_xy), -1))
+        gl = np.ascontiguousarray(np.asarray(goal_xy, np.float64).reshape(len(goal_xy), -1))
+        if st.shape[0] != gl.shape[0] or st.shape[1] < 2 or gl.shape[1] < 2:
+            raise BackendError("search_paths: start_xy and goal_xy must be [count][>= 2] arrays of one length")
+        mk = None if mask is None else np.ascontiguousarray(np.asarray(mask).astype(bool), np.int32)
+        p = _search_params(safe_dis, window_margin)
+        self.search_count = st.shape[0]
+        self._check(self.L.alore_backend_search_paths(self.h, st.shape[0], st.ctypes.data, st.strides[0], gl.ctypes.data, gl.strides[0],
+                                                      C.byref(p), 0, None if mk is None else mk.ctypes.data, 4, None))
+
+    def search_paths_device(self, count, start_xy, goal_xy, start_stride=None, goal_stride=None, safe_dis=None, window_margin=None,
+                            mask=None, mask_stride=4, stream=None):
+        """The same with everything resident: float64 torch tensors [count][>= 2] (their own row stride; the xytheta [count][3] of
+        predicted_state_device serves as the starts as it lies) or raw device addresses with a stride in bytes (default 16); mask
+        as for plan().  Nothing is copied but the argument block and nothing waits; search_status() has the outcome per slot."""
+        def stride(a, given):
+            if given is not None:
+                return int(given)
+            return 16 if a is None or isinstance(a, int) else int(a.stride(0) * a.element_size())
+        p = _search_params(safe_dis, window_margin)
+        mp, ms = _mask(mask, mask_stride)
+        self.search_count = int(count)
+        self._check(self.L.alore_backend_search_paths(self.h, int(count), _dev(start_xy), stride(start_xy, start_stride), _dev(goal_xy),
+                                                      stride(goal_xy, goal_stride), C.byref(p), 1, mp, ms, _stream(stream)))
+
+    def device_paths(self) -> PathsC:
+        """the device slab of searched paths as alore_backend_paths: max_points 31, n_points and xy set, the yaws and start
+        derivatives None for the caller to fill (set_paths_device(count, v.max_points, v.n_points, v.xy, start_yaw, end_yaw, ...))"""
+        v = PathsC()
+        self._check(self.L.alore_backend_device_paths(self.h, C.byref(v)))
+        return v
+
+    def device_search_status(self) -> int:
+        p = C.c_void_p()
+        self._check(self.L.alore_backend_device_search_status(self.h, C.byref(p)))
+        return p.value
+
+    def search_status(self, count: int | None = None) -> np.ndarray:
+        """per slot of the last search: 0 found, 1 masked out, -1 end point, -2 same cell, -3 window, -4 no path, -5 points (waits)"""
+        n = int(count or getattr(self, "search_count", 0))
+        out = np.zeros(n, np.int32)
+        self._check(self.L.alore_backend_search_status(self.h, n, out.ctypes.data_as(C.POINTER(C.c_int))))
+        return out
+
+    def search_sweeps(self, count: int | None = None) -> np.ndarray:
+        """diagnostic: sweeps over the window until the field stood still, per slot of the last search (waits)"""
+        n = int(count or getattr(self, "search_count", 0))
+        out = np.zeros(n, np.int32)
+        self._check(self.L.alore_backend_search_sweeps(self.h, n, out.ctypes.data_as(C.POINTER(C.c_int))))
+        return out
+
+    def paths(self, count: int | None = None) -> dict:
+        """the slab of searched paths copied to the host (waits): n_points [count], xy [count][31][2], cost_ab [count][2]"""
+        n = int(count or getattr(self, "search_count", 0))
+        out = {"n_points": np.zeros(n, np.int32), "xy": np.zeros((n, MAX_PATH_POINTS, 2)), "cost_ab": np.zeros((n, 2), np.int32)}
+        ip = C.POINTER(C.c_int)
+        self._check(self.L.alore_backend_get_paths(self.h, n, out["n_points"].ctypes.data_as(ip), _dp(out["xy"]), out["cost_ab"].ctypes.data_as(ip)))
         return out
 
     def predicted_state_device(self, count, times, xytheta, vaj, oaj, forward, resolution: float = 0.01, start_times=None, start_xytheta=None,

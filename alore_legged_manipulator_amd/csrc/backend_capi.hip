@@ -9,6 +9,7 @@
 
 #include "backend_kernels.h"
 #include "flat_traj_build.h"
+#include "path_search.h"
 
 struct alore_backend_planner {
     alore_backend_config cfg;
@@ -63,6 +64,13 @@ struct alore_backend_planner {
     bool scan_pending = false;
     char* d_points = nullptr; // staging of host points (grows)
     size_t points_bytes = 0;
+    // alore_backend_search_paths: the argument block followed by the staged inputs of the host route, pinned and on the device,
+    // and the slab of searched paths
+    char *h_search = nullptr, *d_search_in = nullptr;
+    int *d_path_n = nullptr, *d_path_cost = nullptr, *d_search_status = nullptr, *d_search_sweeps = nullptr;
+    double* d_path_xy = nullptr;
+    hipEvent_t ev_search = nullptr; // the upload of the previous call has left h_search
+    bool search_pending = false;
 };
 
 namespace {
@@ -126,13 +134,16 @@ void free_all(alore_backend_handle h)
     }
     void* ptrs[] = {h->d_map, h->d_M, h->d_cut, h->d_inner, h->d_initT, h->d_pos, h->d_head, h->d_tail, h->d_sxy, h->d_fxy, h->d_sxyt,
                     h->r_inner, h->r_T, h->r_coef, h->r_tail, h->r_ok, h->r_status, h->d_hist, h->d_gram, h->d_pcr, h->d_x, h->d_g, h->d_lam, h->d_rho,
-                    h->d_cost, h->d_err, h->d_ret, h->d_params, h->d_order, h->d_check_in, h->d_check, h->d_build_in, h->d_build_status};
+                    h->d_cost, h->d_err, h->d_ret, h->d_params, h->d_order, h->d_check_in, h->d_check, h->d_build_in, h->d_build_status,
+                    h->d_search_in, h->d_path_n, h->d_path_cost, h->d_search_status, h->d_search_sweeps, h->d_path_xy};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->h_check) (void)hipHostFree(h->h_check);
     if (h->h_build) (void)hipHostFree(h->h_build);
     if (h->h_params) (void)hipHostFree(h->h_params);
+    if (h->h_search) (void)hipHostFree(h->h_search);
+    if (h->ev_search) (void)hipEventDestroy(h->ev_search);
     if (h->ev_build) (void)hipEventDestroy(h->ev_build);
     if (h->ev_params) (void)hipEventDestroy(h->ev_params);
     if (h->ev_check) (void)hipEventDestroy(h->ev_check);
@@ -185,6 +196,10 @@ BuildLayout build_layout(size_t n, size_t K)
     l.bytes = at;
     return l;
 }
+
+// the block of alore_backend_search_paths: arguments, then (host route) starts [n][2], goals [n][2] and the mask [n]
+constexpr size_t SEARCH_ARGS_BYTES = (sizeof(backend::SearchArgs) + 15) & ~size_t(15);
+size_t search_in_bytes(size_t n) { return SEARCH_ARGS_BYTES + sizeof(double) * 4 * n + sizeof(int) * n; }
 
 } // namespace
 
@@ -267,6 +282,11 @@ int alore_backend_create(const alore_backend_config* cfg, int device, int max_pi
     if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_params, sizeof(backend::Params), hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_build, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_params, hipEventDisableTiming);
+    A(dalloc(&h->d_path_n, B)); A(dalloc(&h->d_path_cost, B * 2)); A(dalloc(&h->d_search_status, B)); A(dalloc(&h->d_search_sweeps, B));
+    A(dalloc(&h->d_path_xy, B * psearch::MAX_POINTS * 2)); A(dalloc(&h->d_search_in, search_in_bytes(B)));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_search, search_in_bytes(B), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_search, hipEventDisableTiming);
+    if (e == hipSuccess) e = backend::search_configure();
     if (e != hipSuccess) {
         free_all(h);
         delete h;
@@ -946,6 +966,128 @@ int alore_backend_map_device(alore_backend_handle h, alore_backend_map_view* out
     if (!out) return fail(h, ALORE_BE_E_INVALID, "map_device: bad argument");
     const backend::OccMap& m = h->omap;
     *out = alore_backend_map_view{m.grid, m.log_odds, h->d_map, m.count_hit, m.count_all, m.nx, m.ny, m.x_lo, m.y_lo, m.res};
+    return ALORE_BE_OK;
+}
+
+void alore_backend_search_default_params(alore_backend_search_params* p)
+{
+    psearch::Params d;
+    psearch::default_params(&d);
+    p->safe_dis = d.safe_dis;
+    p->window_margin = d.window_margin;
+}
+
+int alore_backend_search_paths(alore_backend_handle h, int count, const double* start_xy, int start_stride_bytes, const double* goal_xy,
+                               int goal_stride_bytes, const alore_backend_search_params* params, int device_pointers, const int* mask,
+                               int mask_stride_bytes, void* stream)
+{
+    if (!h || count < 1 || count > h->B || !start_xy || !goal_xy) return fail(h, ALORE_BE_E_INVALID, "search_paths: bad argument");
+    const int two = 2 * (int)sizeof(double);
+    if (start_stride_bytes < two || start_stride_bytes % (int)sizeof(double) || goal_stride_bytes < two || goal_stride_bytes % (int)sizeof(double))
+        return fail(h, ALORE_BE_E_INVALID, "search_paths: the strides of start and goal must be multiples of 8, at least 16");
+    if (mask && (mask_stride_bytes < (int)sizeof(int) || mask_stride_bytes % (int)sizeof(int)))
+        return fail(h, ALORE_BE_E_INVALID, "search_paths: the mask stride must be a positive multiple of sizeof(int)");
+    alore_backend_search_params prm;
+    if (params) prm = *params; else alore_backend_search_default_params(&prm);
+    if (!std::isfinite(prm.safe_dis) || !std::isfinite(prm.window_margin) || prm.window_margin < 0.0)
+        return fail(h, ALORE_BE_E_INVALID, "search_paths: safe_dis must be finite, window_margin finite and not negative");
+    if (!h->d_map) return fail(h, ALORE_BE_E_INVALID, "search_paths: no map (alore_backend_set_map / alore_backend_build_esdf / alore_backend_map_create)");
+    BE_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (h->search_pending) BE_TRY(h, hipEventSynchronize(h->ev_search)); // the pinned block is free again
+    h->search_pending = false;
+    const size_t n = count;
+    backend::SearchArgs g{};
+    g.count = count;
+    g.map = h->map;
+    g.safe_dis = prm.safe_dis;
+    g.window_margin = prm.window_margin;
+    size_t up = SEARCH_ARGS_BYTES;
+    if (device_pointers) {
+        g.start = start_xy; g.start_stride = start_stride_bytes;
+        g.goal = goal_xy; g.goal_stride = goal_stride_bytes;
+        g.mask = mask; g.mask_stride = mask ? mask_stride_bytes : 0;
+    } else {
+        double *hs = (double*)(h->h_search + SEARCH_ARGS_BYTES), *hg = hs + 2 * n;
+        int* hm = (int*)(hg + 2 * n);
+        for (size_t b = 0; b < n; ++b) {
+            const double* ps = (const double*)((const char*)start_xy + b * (size_t)start_stride_bytes);
+            const double* pg = (const double*)((const char*)goal_xy + b * (size_t)goal_stride_bytes);
+            hs[2 * b] = ps[0]; hs[2 * b + 1] = ps[1];
+            hg[2 * b] = pg[0]; hg[2 * b + 1] = pg[1];
+            if (mask) hm[b] = *(const int*)((const char*)mask + b * (size_t)mask_stride_bytes);
+        }
+        double* ds = (double*)(h->d_search_in + SEARCH_ARGS_BYTES);
+        g.start = ds; g.start_stride = two;
+        g.goal = ds + 2 * n; g.goal_stride = two;
+        g.mask = mask ? (const int*)(ds + 4 * n) : nullptr;
+        g.mask_stride = mask ? (int)sizeof(int) : 0;
+        up = search_in_bytes(n);
+    }
+    const long long map_cells = (long long)h->map.nx * h->map.ny;
+    g.lds_cells = map_cells < psearch::MAX_CELLS ? (int)map_cells : psearch::MAX_CELLS;
+    g.n_points = h->d_path_n; g.xy = h->d_path_xy; g.cost_ab = h->d_path_cost; g.status = h->d_search_status; g.sweeps = h->d_search_sweeps;
+    std::memcpy(h->h_search, &g, sizeof(g));
+    BE_TRY(h, hipMemcpyAsync(h->d_search_in, h->h_search, up, hipMemcpyHostToDevice, s));
+    BE_TRY(h, hipEventRecord(h->ev_search, s));
+    h->search_pending = true;
+    BE_TRY(h, backend::search_paths((const backend::SearchArgs*)h->d_search_in, count, g.lds_cells, s));
+    if (!device_pointers) {
+        int* hst = (int*)h->h_stage;
+        BE_TRY(h, hipMemcpyAsync(hst, h->d_search_status, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+        BE_TRY(h, hipStreamSynchronize(s));
+        for (size_t b = 0; b < n; ++b) {
+            if (hst[b] == psearch::E_ENDPOINT) return fail(h, ALORE_BE_E_INVALID, "search_paths: an end point is not finite or outside the map");
+            if (hst[b] == psearch::E_SAME_CELL) return fail(h, ALORE_BE_E_INVALID, "search_paths: start and goal lie in one cell");
+            if (hst[b] == psearch::E_NO_PATH) return fail(h, ALORE_BE_E_INVALID, "search_paths: no path inside the window");
+            if (hst[b] == psearch::E_WINDOW) return fail(h, ALORE_BE_E_UNSUPPORTED, "search_paths: the window has more than 32768 cells");
+            if (hst[b] == psearch::E_POINTS) return fail(h, ALORE_BE_E_UNSUPPORTED, "search_paths: more than 1024 raw nodes or 31 way-points");
+        }
+    }
+    return ALORE_BE_OK;
+}
+
+int alore_backend_device_paths(alore_backend_handle h, alore_backend_paths* out)
+{
+    if (!h || !out) return fail(h, ALORE_BE_E_INVALID, "device_paths: bad argument");
+    *out = alore_backend_paths{psearch::MAX_POINTS, h->d_path_n, h->d_path_xy, nullptr, nullptr, nullptr, nullptr};
+    return ALORE_BE_OK;
+}
+
+int alore_backend_device_search_status(alore_backend_handle h, const int** out)
+{
+    if (!h || !out) return fail(h, ALORE_BE_E_INVALID, "device_search_status: bad argument");
+    *out = h->d_search_status;
+    return ALORE_BE_OK;
+}
+
+int alore_backend_search_status(alore_backend_handle h, int count, int* out)
+{
+    if (!h || count < 1 || count > h->B || !out) return fail(h, ALORE_BE_E_INVALID, "search_status: bad argument");
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, hipDeviceSynchronize());
+    BE_TRY(h, hipMemcpy(out, h->d_search_status, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost));
+    return ALORE_BE_OK;
+}
+
+int alore_backend_search_sweeps(alore_backend_handle h, int count, int* out)
+{
+    if (!h || count < 1 || count > h->B || !out) return fail(h, ALORE_BE_E_INVALID, "search_sweeps: bad argument");
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, hipDeviceSynchronize());
+    BE_TRY(h, hipMemcpy(out, h->d_search_sweeps, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost));
+    return ALORE_BE_OK;
+}
+
+int alore_backend_get_paths(alore_backend_handle h, int count, int* n_points, double* xy, int* cost_ab)
+{
+    if (!h || count < 1 || count > h->B) return fail(h, ALORE_BE_E_INVALID, "get_paths: bad argument");
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, hipDeviceSynchronize());
+    const size_t n = count;
+    if (n_points) BE_TRY(h, hipMemcpy(n_points, h->d_path_n, sizeof(int) * n, hipMemcpyDeviceToHost));
+    if (xy) BE_TRY(h, hipMemcpy(xy, h->d_path_xy, sizeof(double) * n * psearch::MAX_POINTS * 2, hipMemcpyDeviceToHost));
+    if (cost_ab) BE_TRY(h, hipMemcpy(cost_ab, h->d_path_cost, sizeof(int) * n * 2, hipMemcpyDeviceToHost));
     return ALORE_BE_OK;
 }
 

@@ -117,6 +117,28 @@ struct BuildArgs {
 // both kernels read their arguments from d_args (device memory, filled in stream order before the launch)
 hipError_t build_problems(const BuildArgs* d_args, int count, hipStream_t s);
 
+// path_search.hip: way-point paths by grid search on the handle's distance field (arithmetic in path_search.h): one workgroup per
+// problem, the cost-to-goal field of the search window in LDS, then the walk and the pruning of removeCornerPts
+struct SearchArgs {
+    int count;
+    MapView map;
+    double safe_dis, window_margin;
+    const double *start, *goal;    // x, y of problem b at (char*)p + b * stride (bytes)
+    int start_stride, goal_stride;
+    const int* mask;               // null, or slot b is searched when the int at (char*)mask + b * mask_stride is not 0
+    int mask_stride;
+    int lds_cells;                 // capacity of the field in LDS: min(nx ny, the largest window)
+    int* n_points;                 // [count]
+    double* xy;                    // [count][31][2]
+    int* cost_ab;                  // [count][2]: the unpruned path costs a + b sqrt(2)
+    int* status;                   // [count]
+    int* sweeps;                   // [count] sweeps until the field stood still (diagnostic)
+};
+// the kernel reads its arguments from d_args (device memory, filled in stream order before the launch)
+hipError_t search_paths(const SearchArgs* d_args, int count, int lds_cells, hipStream_t s);
+// registers the field's LDS size with the runtime (once per device, not in stream order: call before the first search)
+hipError_t search_configure();
+
 // MSPlanner::get_the_predicted_state[_and_path] on the plans of the last launch (esdf_build.hip)
 struct PredictArgs {
     int count, P;

@@ -268,8 +268,8 @@ int alore_backend_plan_masked(alore_backend_handle h, int count, const int *mask
  * the distance field is the map that alore_backend_plan, alore_backend_plan_masked and alore_backend_check_plans read.  Grids are
  * [nx][ny], cell (ix, iy) at ix * ny + iy, x_hi = x_lo + nx * res.  csrc/occupancy_update.h holds the arithmetic and lists the
  * deviations from the reference (int counts, non-finite points skipped, a sensor outside the map refused, no access outside the
- * map at its edge).  Out of scope: the JPS search and removeCornerPts, cirSupRaycastProcess (off in both launch files), TF lookups
- * and PCL conversion (the caller hands over points in the world frame), the laser simulator. */
+ * map at its edge).  Out of scope: cirSupRaycastProcess (off in both launch files), TF lookups and PCL conversion (the caller hands
+ * over points in the world frame), the laser simulator.  The front end's search on this map is alore_backend_search_paths below. */
 typedef struct alore_backend_map_params {
     double p_hit, p_miss, p_min, p_max, p_occ; /* probabilities in (0, 1); their logits are the log-odds of the update */
     double detection_range;
@@ -329,6 +329,64 @@ typedef struct alore_backend_map_view {
     double x_lo, y_lo, res;
 } alore_backend_map_view;
 int alore_backend_map_device(alore_backend_handle h, alore_backend_map_view *out);
+
+/* ---- way-point paths by grid search on the handle's map, on the device ---------------------------------------- */
+/* What produces the paths that alore_backend_set_paths reads: per problem a shortest 8-connected path from a start to a goal over
+ * the cells whose distance is at least a safe distance, pruned by line of sight -- JPSPlanner::plan and removeCornerPts
+ * (front_end/src/jps_planner/jps_planner.cpp:31-68, 97-177, graph_search.cpp:92-243).  The reference's JPS returns one of several
+ * equal-cost paths, which one depends on its heap; here the path is fixed by a contract with exactly one answer, stated in
+ * csrc/path_search.h: the cost is optimal on the reference's graph (eight moves, only the destination must be free, 1 or sqrt 2),
+ * kept as an exact pair (a, b) = a + b sqrt 2; among equal-cost paths the walk from the start keeps its direction when it can and
+ * otherwise takes the first of (1,0) (1,1) (0,1) (-1,1) (-1,0) (-1,-1) (0,-1) (1,-1); the pruning is removeCornerPts' arithmetic.
+ * The safe distance is the reference's (safe_dis capped by 0.8 times the distance at either end cell, not below 0).  The search
+ * stays in a window: the bounding box of the two cells grown by ceil(window_margin / res) cells a side, clipped to the map, at most
+ * ALORE_BE_SEARCH_MAX_CELLS cells.  Deviations: an end point outside the map or not finite is refused (the reference clamps), equal
+ * end cells are refused (the reference hands on a one-point path).  One workgroup per problem, the field of the window in LDS
+ * (csrc/path_search.hip). */
+typedef struct alore_backend_search_params {
+    double safe_dis;      /* jps_safe_dis */
+    double window_margin; /* metres round the bounding box of start and goal */
+} alore_backend_search_params;
+/* 0.3 (front_end/config/jps3ms.yaml) and 3.0 */
+void alore_backend_search_default_params(alore_backend_search_params *p);
+
+#define ALORE_BE_SEARCH_MAX_CELLS 32768
+/* search status of a slot */
+#define ALORE_BE_SEARCH_OK 0
+#define ALORE_BE_SEARCH_MASKED 1          /* the mask left the slot out: nothing of it was touched, n_points included */
+#define ALORE_BE_SEARCH_E_ENDPOINT (-1)   /* a coordinate is not finite or outside [lo, hi] of the map */
+#define ALORE_BE_SEARCH_E_SAME_CELL (-2)  /* start and goal lie in one cell */
+#define ALORE_BE_SEARCH_E_WINDOW (-3)     /* the window has more than ALORE_BE_SEARCH_MAX_CELLS cells */
+#define ALORE_BE_SEARCH_E_NO_PATH (-4)    /* an end cell is not free, or the goal cannot be reached inside the window */
+#define ALORE_BE_SEARCH_E_POINTS (-5)     /* more than 1024 raw nodes, or more than 31 way-points after pruning */
+
+/* Searches slots 0..count-1 on the handle's current map (resident, or set by alore_backend_set_map / alore_backend_build_esdf;
+ * without one: ALORE_BE_E_INVALID).  x, y of slot b are the two doubles at (char *)start_xy + b * start_stride_bytes, likewise the
+ * goal (strides: multiples of 8, at least 16): the d_xytheta [count][3] of alore_backend_predicted_state_device serves as the
+ * starts as it lies, with stride 24.  params NULL: the defaults.  The mask is read as alore_backend_set_paths reads its mask.
+ * A slot that succeeds has 2 .. 31 way-points in the slab of alore_backend_device_paths, the first the given start and the last
+ * the given goal, and status 0; a slot that fails has n_points = 0, its xy row untouched and a negative status, so
+ * alore_backend_set_paths on the slab refuses it with ALORE_BE_BUILD_E_POINTS and its stored plan stays as it is.
+ * device_pointers != 0: start_xy, goal_xy and mask are DEVICE memory read in stream order; nothing is allocated, nothing crosses
+ * the bus but the argument block and nothing waits (a second call waits for the first one's block to have left the host).
+ * device_pointers == 0: they are HOST memory; they are uploaded, the stream is synchronised, and the call returns, for the first
+ * slot that failed, ALORE_BE_E_INVALID (end point, same cell, no path) or ALORE_BE_E_UNSUPPORTED (window, points). */
+int alore_backend_search_paths(alore_backend_handle h, int count, const double *start_xy, int start_stride_bytes, const double *goal_xy,
+                               int goal_stride_bytes, const alore_backend_search_params *params, int device_pointers, const int *mask,
+                               int mask_stride_bytes, void *stream);
+/* The handle's device slab of searched paths [max_problems]: max_points = 31, n_points and xy are set; start_yaw, end_yaw,
+ * start_vaj and start_oaj are NULL for the caller to fill, then the struct goes into alore_backend_set_paths with
+ * device_pointers = 1.  Valid until the handle is destroyed. */
+int alore_backend_device_paths(alore_backend_handle h, alore_backend_paths *out);
+/* device slab [max_problems] of the search status of the last alore_backend_search_paths */
+int alore_backend_device_search_status(alore_backend_handle h, const int **out);
+/* the same copied to HOST memory out[count]; waits for the device */
+int alore_backend_search_status(alore_backend_handle h, int count, int *out);
+/* The searched paths copied to HOST arrays (any pointer may be NULL): n_points [count], xy [count][31][2], cost_ab [count][2] (the
+ * cost a + b sqrt 2 of the unpruned path; written by slots that succeeded).  Waits for the device. */
+int alore_backend_get_paths(alore_backend_handle h, int count, int *n_points, double *xy, int *cost_ab);
+/* diagnostic: sweeps over the window until the field stood still, per slot of the last search; HOST out[count]; waits */
+int alore_backend_search_sweeps(alore_backend_handle h, int count, int *out);
 
 #ifdef __cplusplus
 }
