@@ -105,7 +105,22 @@ class SearchParamsC(C.Structure):
     _fields_ = [("safe_dis", C.c_double), ("window_margin", C.c_double)]
 
 
+class TaskParamsC(C.Structure):
+    """alore_backend_task_params (include/alore_backend.h)"""
+    _fields_ = [("safe_dis", C.c_double), ("window_margin", C.c_double), ("mode", C.c_int)]
+
+
+class TaskViewC(C.Structure):
+    """alore_backend_task_view: device addresses of the slab of missions"""
+    _fields_ = [("max_points", C.c_int), ("max_legs", C.c_int), ("status", C.c_void_p), ("matrix", C.c_void_p), ("order", C.c_void_p),
+                ("n_order", C.c_void_p), ("total", C.c_void_p), ("leg_start_xy", C.c_void_p), ("leg_goal_xy", C.c_void_p),
+                ("fields", C.c_void_p), ("sweeps", C.c_void_p)]
+
+
 MAX_PATH_POINTS = 31
+TASK_MAX_TASKS, TASK_MAX_POINTS, TASK_MAX_LEGS = 10, 21, 20
+TASK_GREEDY, TASK_OPTIMAL = 0, 1
+TASK_OK, TASK_MASKED, TASK_E_ENDPOINT, TASK_E_WINDOW, TASK_E_TASKS, TASK_E_NO_ORDER = 0, 1, -1, -3, -6, -7
 SEARCH_OK, SEARCH_MASKED, SEARCH_E_ENDPOINT, SEARCH_E_SAME_CELL, SEARCH_E_WINDOW, SEARCH_E_NO_PATH, SEARCH_E_POINTS = 0, 1, -1, -2, -3, -4, -5
 SEARCH_MAX_CELLS = 32768
 BUILD_OK, BUILD_MASKED, BUILD_E_POINTS, BUILD_E_PIECES = 0, 1, -1, -2
@@ -167,6 +182,12 @@ def _bind(L):
     L.alore_backend_search_status.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.alore_backend_search_sweeps.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.alore_backend_get_paths.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), DP, C.POINTER(C.c_int)]
+    L.alore_backend_task_default_params.argtypes = [C.POINTER(TaskParamsC)]
+    L.alore_backend_task_default_params.restype = None
+    L.alore_backend_task_plan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(TaskParamsC),
+                                          C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.alore_backend_device_task.argtypes = [C.c_void_p, C.POINTER(TaskViewC)]
+    L.alore_backend_get_task.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_int)] * 5 + [DP, DP] + [C.POINTER(C.c_int)] * 2
     L._backend_bound = True
 
 
@@ -206,6 +227,26 @@ def _search_params(safe_dis, window_margin) -> SearchParamsC:
         p.safe_dis = float(safe_dis)
     if window_margin is not None:
         p.window_margin = float(window_margin)
+    return p
+
+
+def default_task_params() -> TaskParamsC:
+    """jps_safe_dis 0.3, a window margin of 3 m and the greedy order, the reference's live call"""
+    L = _lib.load()
+    _bind(L)
+    p = TaskParamsC()
+    L.alore_backend_task_default_params(C.byref(p))
+    return p
+
+
+def _task_params(safe_dis, window_margin, mode) -> TaskParamsC:
+    p = default_task_params()
+    if safe_dis is not None:
+        p.safe_dis = float(safe_dis)
+    if window_margin is not None:
+        p.window_margin = float(window_margin)
+    if mode is not None:
+        p.mode = int(mode)
     return p
 
 
@@ -286,6 +327,7 @@ class BatchedMSPlanner:
     def set_map(self, dist: np.ndarray, x_lo: float, y_lo: float, res: float):
         dist = np.ascontiguousarray(dist, dtype=np.float64)
         self._check(self.L.alore_backend_set_map(self.h, _dp(dist), dist.shape[0], dist.shape[1], x_lo, y_lo, res))
+        self.map_res = float(res)
 
     def build_esdf(self, grid: np.ndarray, x_lo: float, y_lo: float, res: float, odom=(0.0, 0.0), detection_range: float = 1e3) -> np.ndarray:
         """SDFmap::updateESDF2d on the device from a uint8 state grid (0 unknown, 1 free, 2 occupied); the result becomes
@@ -294,6 +336,7 @@ class BatchedMSPlanner:
         dist = np.zeros(g.shape)
         self._check(self.L.alore_backend_build_esdf(self.h, g.ctypes.data_as(C.POINTER(C.c_ubyte)), g.shape[0], g.shape[1], x_lo, y_lo, res,
                                                     float(odom[0]), float(odom[1]), float(detection_range), _dp(dist)))
+        self.map_res = float(res)
         return dist
 
     # ---- the resident occupancy map: point clouds in, log-odds, cell states and the ESDF updated in place on the device
@@ -312,6 +355,7 @@ class BatchedMSPlanner:
             setattr(p, k, v)
         self._check(self.L.alore_backend_map_create(self.h, int(nx), int(ny), float(x_lo), float(y_lo), float(res), C.byref(p)))
         self.map_shape = (int(nx), int(ny))
+        self.map_res = float(res)
         self.map_params = p
 
     @property
@@ -545,6 +589,73 @@ class BatchedMSPlanner:
         out = {"n_points": np.zeros(n, np.int32), "xy": np.zeros((n, MAX_PATH_POINTS, 2)), "cost_ab": np.zeros((n, 2), np.int32)}
         ip = C.POINTER(C.c_int)
         self._check(self.L.alore_backend_get_paths(self.h, n, out["n_points"].ctypes.data_as(ip), _dp(out["xy"]), out["cost_ab"].ctypes.data_as(ip)))
+        return out
+
+    # ---- the visit order of rearrangement missions from path costs on the handle's map (alore_backend_task_plan)
+    def task_plan(self, n_tasks, points, assignment=None, mode=None, safe_dis=None, window_margin=None, mask=None, check=True):
+        """plan_manager's task planning for a batch of missions (NumPy in): n_tasks [count]; points [count][1 + 2 max_tasks][2], per
+        mission the robot, its n items, its n targets, packed at the beginning of the row; assignment [count][max_tasks] (optimal
+        mode; None: the identity); mode TASK_GREEDY (None) or TASK_OPTIMAL; safe_dis / window_margin None: 0.3 / 3.0; mask: per
+        mission, 0 leaves it out.  Waits.  Raises when a mission fails unless check is False; task_result() has the outcome."""
+        pts = np.ascontiguousarray(np.asarray(points, np.float64))
+        nt = np.ascontiguousarray(np.asarray(n_tasks, np.int32).reshape(-1))
+        if pts.ndim != 3 or pts.shape[2] != 2 or pts.shape[1] < 3 or pts.shape[1] % 2 == 0 or pts.shape[0] != nt.shape[0]:
+            raise BackendError("task_plan: points must be [count][1 + 2 max_tasks][2], n_tasks [count]")
+        max_tasks = (pts.shape[1] - 1) // 2
+        asg = None
+        if assignment is not None:
+            asg = np.ascontiguousarray(np.asarray(assignment, np.int32))
+            if asg.shape != (nt.shape[0], max_tasks):
+                raise BackendError("task_plan: assignment must be [count][max_tasks]")
+        mk = None if mask is None else np.ascontiguousarray(np.asarray(mask).astype(bool), np.int32)
+        p = _task_params(safe_dis, window_margin, mode)
+        self.task_count = nt.shape[0]
+        rc = self.L.alore_backend_task_plan(self.h, nt.shape[0], max_tasks, nt.ctypes.data, pts.ctypes.data, pts.strides[0],
+                                            None if asg is None else asg.ctypes.data, C.byref(p), 0, None if mk is None else mk.ctypes.data,
+                                            4, None)
+        if rc != 0 and not check and self.L.alore_backend_last_error(self.h).decode().startswith("task_plan: mission failed"):
+            return                                                       # the launch ran and a mission failed: its status says why
+        self._check(rc)                                                  # anything else launched nothing: always raised
+
+    def task_plan_device(self, count, max_tasks, n_tasks, points, point_row_stride=None, assignment=None, mode=None, safe_dis=None,
+                         window_margin=None, mask=None, mask_stride=4, stream=None):
+        """The same with everything resident: n_tasks int32 [count], points float64 [count][>= 1 + 2 max_tasks][2] (its own row
+        stride), assignment int32 [count][max_tasks] or None: torch tensors, or raw device addresses (points then with
+        point_row_stride in bytes); mask as for plan().  Nothing is copied but the argument block and nothing waits;
+        task_result() / device_task() have the outcome per mission."""
+        if point_row_stride is None:
+            point_row_stride = 16 * (1 + 2 * int(max_tasks)) if isinstance(points, int) else int(points.stride(0) * points.element_size())
+        p = _task_params(safe_dis, window_margin, mode)
+        mp, ms = _mask(mask, mask_stride)
+        self.task_count = int(count)
+        self._check(self.L.alore_backend_task_plan(self.h, int(count), int(max_tasks), _dev(n_tasks), _dev(points), int(point_row_stride),
+                                                   _dev(assignment), C.byref(p), 1, mp, ms, _stream(stream)))
+
+    def device_task(self) -> TaskViewC:
+        """the device slab of the missions (alore_backend_task_view).  Leg l of every mission goes into search_paths_device as it
+        lies: start v.leg_start_xy + 16 l, goal v.leg_goal_xy + 16 l, both strides 16 * v.max_legs bytes"""
+        v = TaskViewC()
+        self._check(self.L.alore_backend_device_task(self.h, C.byref(v)))
+        return v
+
+    def task_result(self, count: int | None = None, res: float | None = None) -> dict:
+        """the slab of the missions copied to the host (waits): status, n_order, fields, sweeps [count]; matrix [count][21][21][2]
+        (the pairs (a, b), (-1, -1) for no path; entries beyond a mission's points are not written); order [count][20]; total
+        [count][2]; leg_start_xy, leg_goal_xy [count][20][2]; and cost_m [count][21][21] = (a + b sqrt 2) res in metres, inf where
+        there is no path (res: the cell size, None: the one of the map this planner was given)"""
+        n = int(count or getattr(self, "task_count", 0))
+        P, L = TASK_MAX_POINTS, TASK_MAX_LEGS
+        out = {"status": np.zeros(n, np.int32), "matrix": np.zeros((n, P, P, 2), np.int32), "order": np.zeros((n, L), np.int32),
+               "n_order": np.zeros(n, np.int32), "total": np.zeros((n, 2), np.int32), "leg_start_xy": np.zeros((n, L, 2)),
+               "leg_goal_xy": np.zeros((n, L, 2)), "fields": np.zeros(n, np.int32), "sweeps": np.zeros(n, np.int32)}
+        ip = C.POINTER(C.c_int)
+        i = lambda k: out[k].ctypes.data_as(ip)
+        self._check(self.L.alore_backend_get_task(self.h, n, i("status"), i("matrix"), i("order"), i("n_order"), i("total"),
+                                                  _dp(out["leg_start_xy"]), _dp(out["leg_goal_xy"]), i("fields"), i("sweeps")))
+        res = getattr(self, "map_res", None) if res is None else float(res)
+        if res is not None:
+            a, b = out["matrix"][..., 0].astype(np.float64), out["matrix"][..., 1].astype(np.float64)
+            out["cost_m"] = np.where(out["matrix"][..., 0] < 0, np.inf, (a + b * np.sqrt(2.0)) * res)
         return out
 
     def predicted_state_device(self, count, times, xytheta, vaj, oaj, forward, resolution: float = 0.01, start_times=None, start_xytheta=None,

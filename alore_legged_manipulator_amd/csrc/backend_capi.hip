@@ -10,6 +10,7 @@
 #include "backend_kernels.h"
 #include "flat_traj_build.h"
 #include "path_search.h"
+#include "task_plan.h"
 
 struct alore_backend_planner {
     alore_backend_config cfg;
@@ -71,6 +72,14 @@ struct alore_backend_planner {
     double* d_path_xy = nullptr;
     hipEvent_t ev_search = nullptr; // the upload of the previous call has left h_search
     bool search_pending = false;
+    // alore_backend_task_plan: the argument block followed by the staged inputs of the host route, pinned and on the device, and
+    // the slab of the missions
+    char *h_task = nullptr, *d_task_in = nullptr;
+    int *t_status = nullptr, *t_matrix = nullptr, *t_order = nullptr, *t_n_order = nullptr, *t_total = nullptr, *t_fields = nullptr,
+        *t_sweeps = nullptr, *t_src_fields = nullptr, *t_src_sweeps = nullptr;
+    double *t_leg_start = nullptr, *t_leg_goal = nullptr;
+    hipEvent_t ev_task = nullptr; // the upload of the previous call has left h_task
+    bool task_pending = false;
 };
 
 namespace {
@@ -135,9 +144,13 @@ void free_all(alore_backend_handle h)
     void* ptrs[] = {h->d_map, h->d_M, h->d_cut, h->d_inner, h->d_initT, h->d_pos, h->d_head, h->d_tail, h->d_sxy, h->d_fxy, h->d_sxyt,
                     h->r_inner, h->r_T, h->r_coef, h->r_tail, h->r_ok, h->r_status, h->d_hist, h->d_gram, h->d_pcr, h->d_x, h->d_g, h->d_lam, h->d_rho,
                     h->d_cost, h->d_err, h->d_ret, h->d_params, h->d_order, h->d_check_in, h->d_check, h->d_build_in, h->d_build_status,
-                    h->d_search_in, h->d_path_n, h->d_path_cost, h->d_search_status, h->d_search_sweeps, h->d_path_xy};
+                    h->d_search_in, h->d_path_n, h->d_path_cost, h->d_search_status, h->d_search_sweeps, h->d_path_xy,
+                    h->d_task_in, h->t_status, h->t_matrix, h->t_order, h->t_n_order, h->t_total, h->t_fields, h->t_sweeps, h->t_src_fields,
+                    h->t_src_sweeps, h->t_leg_start, h->t_leg_goal};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    if (h->h_task) (void)hipHostFree(h->h_task);
+    if (h->ev_task) (void)hipEventDestroy(h->ev_task);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->h_check) (void)hipHostFree(h->h_check);
     if (h->h_build) (void)hipHostFree(h->h_build);
@@ -200,6 +213,11 @@ BuildLayout build_layout(size_t n, size_t K)
 // the block of alore_backend_search_paths: arguments, then (host route) starts [n][2], goals [n][2] and the mask [n]
 constexpr size_t SEARCH_ARGS_BYTES = (sizeof(backend::SearchArgs) + 15) & ~size_t(15);
 size_t search_in_bytes(size_t n) { return SEARCH_ARGS_BYTES + sizeof(double) * 4 * n + sizeof(int) * n; }
+
+// the block of alore_backend_task_plan: arguments, then (host route) points [n][1 + 2 T][2], n_tasks [n], assignment [n][T], mask [n]
+constexpr size_t TASK_ARGS_BYTES = (sizeof(backend::TaskArgs) + 15) & ~size_t(15);
+constexpr size_t TASK_MATRIX_INTS = (size_t)tplan::P_MAX * tplan::P_MAX * 2;
+size_t task_in_bytes(size_t n, size_t T) { return TASK_ARGS_BYTES + sizeof(double) * 2 * (1 + 2 * T) * n + sizeof(int) * (n + n * T + n); }
 
 } // namespace
 
@@ -287,6 +305,14 @@ int alore_backend_create(const alore_backend_config* cfg, int device, int max_pi
     if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_search, search_in_bytes(B), hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_search, hipEventDisableTiming);
     if (e == hipSuccess) e = backend::search_configure();
+    A(dalloc(&h->t_status, B)); A(dalloc(&h->t_matrix, B * TASK_MATRIX_INTS)); A(dalloc(&h->t_order, B * tplan::MAX_LEGS));
+    A(dalloc(&h->t_n_order, B)); A(dalloc(&h->t_total, B * 2)); A(dalloc(&h->t_fields, B)); A(dalloc(&h->t_sweeps, B));
+    A(dalloc(&h->t_src_fields, B * tplan::MAX_LEGS)); A(dalloc(&h->t_src_sweeps, B * tplan::MAX_LEGS));
+    A(dalloc(&h->t_leg_start, B * tplan::MAX_LEGS * 2)); A(dalloc(&h->t_leg_goal, B * tplan::MAX_LEGS * 2));
+    A(dalloc(&h->d_task_in, task_in_bytes(B, tplan::MAX_TASKS)));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_task, task_in_bytes(B, tplan::MAX_TASKS), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_task, hipEventDisableTiming);
+    if (e == hipSuccess) e = backend::task_configure();
     if (e != hipSuccess) {
         free_all(h);
         delete h;
@@ -1088,6 +1114,119 @@ int alore_backend_get_paths(alore_backend_handle h, int count, int* n_points, do
     if (n_points) BE_TRY(h, hipMemcpy(n_points, h->d_path_n, sizeof(int) * n, hipMemcpyDeviceToHost));
     if (xy) BE_TRY(h, hipMemcpy(xy, h->d_path_xy, sizeof(double) * n * psearch::MAX_POINTS * 2, hipMemcpyDeviceToHost));
     if (cost_ab) BE_TRY(h, hipMemcpy(cost_ab, h->d_path_cost, sizeof(int) * n * 2, hipMemcpyDeviceToHost));
+    return ALORE_BE_OK;
+}
+
+void alore_backend_task_default_params(alore_backend_task_params* p)
+{
+    tplan::Params d;
+    tplan::default_params(&d);
+    p->safe_dis = d.safe_dis;
+    p->window_margin = d.window_margin;
+    p->mode = d.mode;
+}
+
+int alore_backend_task_plan(alore_backend_handle h, int count, int max_tasks, const int* n_tasks, const double* points,
+                            int point_row_stride_bytes, const int* assignment_or_null, const alore_backend_task_params* params,
+                            int device_pointers, const int* mask, int mask_stride_bytes, void* stream)
+{
+    if (!h || count < 1 || count > h->B || !n_tasks || !points) return fail(h, ALORE_BE_E_INVALID, "task_plan: bad argument");
+    if (max_tasks < 1 || max_tasks > tplan::MAX_TASKS) return fail(h, ALORE_BE_E_INVALID, "task_plan: max_tasks must be 1 .. 10");
+    const int row = 2 * (int)sizeof(double) * (1 + 2 * max_tasks);
+    if (point_row_stride_bytes < row || point_row_stride_bytes % (int)sizeof(double))
+        return fail(h, ALORE_BE_E_INVALID, "task_plan: the row stride of the points must be a multiple of 8, at least 16 (1 + 2 max_tasks)");
+    if (mask && (mask_stride_bytes < (int)sizeof(int) || mask_stride_bytes % (int)sizeof(int)))
+        return fail(h, ALORE_BE_E_INVALID, "task_plan: the mask stride must be a positive multiple of sizeof(int)");
+    alore_backend_task_params prm;
+    if (params) prm = *params; else alore_backend_task_default_params(&prm);
+    if (!std::isfinite(prm.safe_dis) || !std::isfinite(prm.window_margin) || prm.window_margin < 0.0)
+        return fail(h, ALORE_BE_E_INVALID, "task_plan: safe_dis must be finite, window_margin finite and not negative");
+    if (prm.mode != tplan::GREEDY && prm.mode != tplan::OPTIMAL) return fail(h, ALORE_BE_E_INVALID, "task_plan: unknown mode");
+    if (!h->d_map) return fail(h, ALORE_BE_E_INVALID, "task_plan: no map (alore_backend_set_map / alore_backend_build_esdf / alore_backend_map_create)");
+    BE_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (h->task_pending) BE_TRY(h, hipEventSynchronize(h->ev_task)); // the pinned block is free again
+    h->task_pending = false;
+    const size_t n = count, T = max_tasks;
+    backend::TaskArgs g{};
+    g.count = count;
+    g.max_tasks = max_tasks;
+    g.mode = prm.mode;
+    g.map = h->map;
+    g.safe_dis = prm.safe_dis;
+    g.window_margin = prm.window_margin;
+    size_t up = TASK_ARGS_BYTES;
+    if (device_pointers) {
+        g.n_tasks = n_tasks;
+        g.points = points; g.point_row_stride = point_row_stride_bytes;
+        g.assign = assignment_or_null;
+        g.mask = mask; g.mask_stride = mask ? mask_stride_bytes : 0;
+    } else {
+        double* hp = (double*)(h->h_task + TASK_ARGS_BYTES);
+        int *hn = (int*)(hp + 2 * (1 + 2 * T) * n), *ha = hn + n, *hm = ha + n * T;
+        for (size_t b = 0; b < n; ++b) {
+            std::memcpy(hp + 2 * (1 + 2 * T) * b, (const char*)points + b * (size_t)point_row_stride_bytes, (size_t)row);
+            hn[b] = n_tasks[b];
+            for (size_t i = 0; i < T; ++i) ha[b * T + i] = assignment_or_null ? assignment_or_null[b * T + i] : (int)i;
+            hm[b] = mask ? *(const int*)((const char*)mask + b * (size_t)mask_stride_bytes) : 1;
+        }
+        const double* dp = (const double*)(h->d_task_in + TASK_ARGS_BYTES);
+        const int* dn = (const int*)(dp + 2 * (1 + 2 * T) * n);
+        g.points = dp; g.point_row_stride = row;
+        g.n_tasks = dn;
+        g.assign = assignment_or_null ? dn + n : nullptr;
+        g.mask = mask ? dn + n + n * T : nullptr;
+        g.mask_stride = mask ? (int)sizeof(int) : 0;
+        up = task_in_bytes(n, T);
+    }
+    const long long map_cells = (long long)h->map.nx * h->map.ny;
+    g.lds_cells = map_cells < psearch::MAX_CELLS ? (int)map_cells : psearch::MAX_CELLS;
+    g.status = h->t_status; g.matrix = h->t_matrix; g.order = h->t_order; g.n_order = h->t_n_order; g.total = h->t_total;
+    g.leg_start_xy = h->t_leg_start; g.leg_goal_xy = h->t_leg_goal; g.fields = h->t_fields; g.sweeps = h->t_sweeps;
+    g.src_fields = h->t_src_fields; g.src_sweeps = h->t_src_sweeps;
+    std::memcpy(h->h_task, &g, sizeof(g));
+    BE_TRY(h, hipMemcpyAsync(h->d_task_in, h->h_task, up, hipMemcpyHostToDevice, s));
+    BE_TRY(h, hipEventRecord(h->ev_task, s));
+    h->task_pending = true;
+    BE_TRY(h, backend::task_plan((const backend::TaskArgs*)h->d_task_in, count, max_tasks, prm.mode, g.lds_cells, s));
+    if (!device_pointers) {
+        int* hst = (int*)h->h_stage;
+        BE_TRY(h, hipMemcpyAsync(hst, h->t_status, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+        BE_TRY(h, hipStreamSynchronize(s));
+        for (size_t b = 0; b < n; ++b) {
+            if (hst[b] == tplan::E_TASKS) return fail(h, ALORE_BE_E_INVALID, "task_plan: mission failed: a task count is outside 1..max_tasks, or an assignment is no permutation");
+            if (hst[b] == tplan::E_ENDPOINT) return fail(h, ALORE_BE_E_INVALID, "task_plan: mission failed: a point is not finite or outside the map");
+            if (hst[b] == tplan::E_NO_ORDER) return fail(h, ALORE_BE_E_INVALID, "task_plan: mission failed: no order has a finite cost");
+            if (hst[b] == tplan::E_WINDOW) return fail(h, ALORE_BE_E_UNSUPPORTED, "task_plan: mission failed: the window has more than 32768 cells");
+        }
+    }
+    return ALORE_BE_OK;
+}
+
+int alore_backend_device_task(alore_backend_handle h, alore_backend_task_view* out)
+{
+    if (!h || !out) return fail(h, ALORE_BE_E_INVALID, "device_task: bad argument");
+    *out = alore_backend_task_view{tplan::P_MAX, tplan::MAX_LEGS, h->t_status, h->t_matrix, h->t_order, h->t_n_order, h->t_total,
+                                   h->t_leg_start, h->t_leg_goal, h->t_fields, h->t_sweeps};
+    return ALORE_BE_OK;
+}
+
+int alore_backend_get_task(alore_backend_handle h, int count, int* status, int* matrix, int* order, int* n_order, int* total,
+                           double* leg_start_xy, double* leg_goal_xy, int* fields, int* sweeps)
+{
+    if (!h || count < 1 || count > h->B) return fail(h, ALORE_BE_E_INVALID, "get_task: bad argument");
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, hipDeviceSynchronize());
+    const size_t n = count, L = tplan::MAX_LEGS;
+    if (status) BE_TRY(h, hipMemcpy(status, h->t_status, sizeof(int) * n, hipMemcpyDeviceToHost));
+    if (matrix) BE_TRY(h, hipMemcpy(matrix, h->t_matrix, sizeof(int) * n * TASK_MATRIX_INTS, hipMemcpyDeviceToHost));
+    if (order) BE_TRY(h, hipMemcpy(order, h->t_order, sizeof(int) * n * L, hipMemcpyDeviceToHost));
+    if (n_order) BE_TRY(h, hipMemcpy(n_order, h->t_n_order, sizeof(int) * n, hipMemcpyDeviceToHost));
+    if (total) BE_TRY(h, hipMemcpy(total, h->t_total, sizeof(int) * n * 2, hipMemcpyDeviceToHost));
+    if (leg_start_xy) BE_TRY(h, hipMemcpy(leg_start_xy, h->t_leg_start, sizeof(double) * n * L * 2, hipMemcpyDeviceToHost));
+    if (leg_goal_xy) BE_TRY(h, hipMemcpy(leg_goal_xy, h->t_leg_goal, sizeof(double) * n * L * 2, hipMemcpyDeviceToHost));
+    if (fields) BE_TRY(h, hipMemcpy(fields, h->t_fields, sizeof(int) * n, hipMemcpyDeviceToHost));
+    if (sweeps) BE_TRY(h, hipMemcpy(sweeps, h->t_sweeps, sizeof(int) * n, hipMemcpyDeviceToHost));
     return ALORE_BE_OK;
 }
 

@@ -139,6 +139,34 @@ hipError_t search_paths(const SearchArgs* d_args, int count, int lds_cells, hipS
 // registers the field's LDS size with the runtime (once per device, not in stream order: call before the first search)
 hipError_t search_configure();
 
+// task_plan.hip: the visit order of rearrangement missions from path costs on the handle's distance field (arithmetic and contract
+// in task_plan.h): task_costs_kernel, one workgroup per (mission, source point), fills the cost matrices; task_order_kernel, one
+// workgroup per mission behind it on the same stream, the orders, totals and legs
+struct TaskArgs {
+    int count, max_tasks, mode;
+    MapView map;
+    double safe_dis, window_margin;
+    const int* n_tasks;            // [count]
+    const double* points;          // point p of mission m at (char*)points + m * point_row_stride + 16 p
+    int point_row_stride;
+    const int* assign;             // null, or [count][max_tasks]
+    const int* mask;               // null, or mission m is planned when the int at (char*)mask + m * mask_stride is not 0
+    int mask_stride;
+    int lds_cells;                 // capacity of the field in LDS: min(nx ny, the largest window)
+    int* status;                   // [count]
+    int* matrix;                   // [count][21][21][2]
+    int* order;                    // [count][20]
+    int* n_order;                  // [count]
+    int* total;                    // [count][2]
+    double *leg_start_xy, *leg_goal_xy; // [count][20][2]
+    int *fields, *sweeps;          // [count]
+    int *src_fields, *src_sweeps;  // [count][20] per source point: what task_order_kernel adds up (no atomics)
+};
+// both kernels read their arguments from d_args (device memory, filled in stream order before the launch)
+hipError_t task_plan(const TaskArgs* d_args, int count, int max_tasks, int mode, int lds_cells, hipStream_t s);
+// registers the LDS sizes with the runtime (once per device, not in stream order: call before the first task_plan)
+hipError_t task_configure();
+
 // MSPlanner::get_the_predicted_state[_and_path] on the plans of the last launch (esdf_build.hip)
 struct PredictArgs {
     int count, P;

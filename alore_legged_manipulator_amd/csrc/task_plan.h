@@ -1,0 +1,345 @@
+// task_plan.h -- the visit order of a rearrangement mission from path costs on the distance field, the arithmetic once (internal).
+// Plain C++17: __host__ __device__ under hipcc, no HIP dependency otherwise.  What the reference's plan_manager does before any
+// trajectory is planned (planning_ddr_opt/plan_manager/include/plan_manager/plan_manager.hpp:210-250): the grid-path length between
+// the robot, the items and the targets (jps_planner_->plan + getPathLength, :287-300 and :370-413), then the order of the visits,
+// solvePathWithGreedy (:347-432, the live call) or BranchAndBoundCombined::solve with a fixed assignment (:252-345,
+// branch_and_bound.hpp).  Stated so that the matrix and both orders have exactly one answer each.  The small functions are what the
+// kernels of task_plan.hip run; plan_one() strings them together serially and is what tests/harness/task_plan_check.cpp and
+// tools/task_plan.py (one host core) run.  The oracle is tests/task_plan_cases.py; harness and device equal it bit for bit.
+//
+// THE CONTRACT
+//   mission  n tasks, 1 <= n <= max_tasks <= MAX_TASKS = 10, and P = 1 + 2 n points (x, y): index 0 the robot, 1..n the items,
+//            n+1..2n the targets (plan_manager.hpp:279).  Missions are batched: mission m has its points packed at the beginning of
+//            a row of 1 + 2 max_tasks points, (char*)points + m * row stride, its n at n_tasks[m], its assignment (optimal mode, may
+//            be absent) at assign[m * max_tasks + i].
+//   status   OK 0, MASKED 1, E_ENDPOINT -1 and E_WINDOW -3 as in path_search.h; E_TASKS -6: n outside 1..max_tasks, or (optimal
+//            mode) a given assignment that is no permutation of 0..n-1; E_NO_ORDER -7 (optimal mode): no order has a finite cost.
+//            A point of the mission that is not finite or outside [lo, hi] is E_ENDPOINT.  The checks come in the order tasks,
+//            end point, window.  A mission that fails a check writes its status and n_order = 0 and nothing else; a masked-out
+//            mission writes status 1 and nothing else.  E_NO_ORDER is found after the matrix: status, n_order = 0, the matrix and
+//            the diagnostics are written, order, total and legs are not.
+//   window   the bounding box of the cells of all P points grown by ceil(window_margin / res) cells a side, clipped to the map;
+//            more than psearch::MAX_CELLS cells is E_WINDOW.  One window per mission: every pair is searched in it.
+//   d(i, j)  the least cost over the reference's graph (eight moves, only the destination must be free, 1 or sqrt 2,
+//            graph_search.cpp:225-243) between the cells of points i and j inside the window, as the exact pair (a, b) for
+//            a + b sqrt 2.  A cell is free when !(dist < safe_ij); safe_ij is the reference's rule for the pair
+//            (jps_planner.cpp:39-42), max(min(max(min(safe_dis, 0.8 dist_i), 0), 0.8 dist_j), 0) with i < j, symmetric for
+//            safe_dis >= 0.  Equal cells give (0, 0), whatever their distance.  Otherwise an end cell that is not free, or no path
+//            in the window, gives INF = (-1, -1) (the reference: DBL_MAX).  d(i, j) = d(j, i).
+//   sums     a route's cost is the component-wise sum of pairs, INF absorbs.  Two sums are ordered exactly: the sign of
+//            da + db sqrt 2 from the signs of da and db, and where they differ from da^2 against 2 db^2 in 64-bit integers (twenty
+//            legs of fewer than 32768 steps: below 2^41).  A finite sum is less than INF, INF is not less than INF.  No
+//            floating-point sum anywhere.
+//   GREEDY   solvePathWithGreedy as written: from point 0 the unvisited item of least d, strict <, so the lowest index wins a tie
+//            and an INF is never chosen; from that item the unvisited target of least d (any target: no assignment in this mode);
+//            from that target again.  It stops where nothing is reachable: n_order may be odd.
+//   OPTIMAL  the fixed-assignment routing of BranchAndBoundCombined::solve: item i goes to target assign[i] (the identity without an
+//            assignment); minimise sum d(previous, item) + d(item, its target) over all item orders, by dynamic programming over
+//            subsets: togo[S][last], the least cost still to pay when the items of S are served and the robot stands at the target
+//            of `last`.  Among optimal orders the one whose item sequence is lexicographically smallest: going forward, always the
+//            lowest item index that still attains the optimum.  The reference's best-first search returns AN optimum; its cost is
+//            the contract, the tie rule is ours.
+//   outputs  status; the matrix [P_MAX][P_MAX][2] (entry (i, j) at (i * P_MAX + j) * 2, i, j < P); order[2 MAX_TASKS] as the
+//            reference publishes it, item index, target index, alternately, each 0-based in its own group; n_order; total[2];
+//            leg_start_xy, leg_goal_xy [2 MAX_TASKS][2], the end points of the legs in visit order, rows beyond n_order untouched;
+//            fields, the number of cost fields computed for the mission (per source k < P - 1 the number of distinct safe_kj over
+//            j > k), and sweeps, the most any of them needed.
+// DEVIATIONS FROM THE REFERENCE
+//   the window: the reference searches the whole map;  an end point outside the map is refused, the reference clamps it;  the tie
+//   rule of the optimal mode;  a leg searched later by psearch uses that pair's own, smaller window, so its cost can exceed d(i, j).
+#ifndef ALORE_TASK_PLAN_H
+#define ALORE_TASK_PLAN_H
+
+#include "path_search.h"
+
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+
+namespace tplan {
+
+constexpr int MAX_TASKS = 10, P_MAX = 1 + 2 * MAX_TASKS, MAX_LEGS = 2 * MAX_TASKS;
+constexpr int OK = 0, MASKED = 1, E_ENDPOINT = -1, E_WINDOW = -3, E_TASKS = -6, E_NO_ORDER = -7;
+constexpr int GREEDY = 0, OPTIMAL = 1;
+constexpr int STATES = (1 << MAX_TASKS) * MAX_TASKS; // togo[S * MAX_TASKS + last]: 80 KiB
+
+struct Params {
+    double safe_dis, window_margin;
+    int mode;
+};
+inline void default_params(Params* p) { p->safe_dis = 0.3; p->window_margin = 3.0; p->mode = GREEDY; } // the reference's live call
+
+struct Cost {
+    int a, b;
+};
+PS_HD Cost inf_cost() { return Cost{-1, -1}; }
+PS_HD bool is_inf(Cost c) { return c.a < 0; }
+PS_HD bool same(Cost p, Cost q) { return p.a == q.a && p.b == q.b; }
+PS_HD Cost add(Cost p, Cost q) { return (is_inf(p) || is_inf(q)) ? inf_cost() : Cost{p.a + q.a, p.b + q.b}; }
+// p < q, exactly
+PS_HD bool less(Cost p, Cost q)
+{
+    if (is_inf(p)) return false;
+    if (is_inf(q)) return true;
+    const long long da = (long long)p.a - q.a, db = (long long)p.b - q.b;
+    if (da >= 0 && db >= 0) return false;
+    if (da <= 0 && db <= 0) return true;             // not both zero here
+    if (da > 0) return da * da < 2 * db * db;        // da - |db| sqrt 2 < 0
+    return da * da > 2 * db * db;                    // -|da| + db sqrt 2 < 0
+}
+PS_HD Cost entry(const int* mat, int i, int j) { return Cost{mat[(i * P_MAX + j) * 2], mat[(i * P_MAX + j) * 2 + 1]}; }
+PS_HD Cost word_cost(unsigned w) { return w >= psearch::UNREACHED ? inf_cost() : Cost{(int)(w >> 16), (int)(w & 0xFFFFu)}; }
+
+struct Mission {
+    int status, P;
+    int x0, y0, wx, wy; // the window: origin in the map and size in cells
+};
+
+// the checks of a mission, in the order tasks, end point, window; pts: the mission's row of points
+PS_HD Mission check_mission(const psearch::Grid& g, int n, int max_tasks, const double* pts, const int* assign, int mode, double window_margin)
+{
+    Mission m{};
+    m.status = E_TASKS;
+    if (max_tasks < 1 || max_tasks > MAX_TASKS || n < 1 || n > max_tasks) return m;
+    if (mode == OPTIMAL && assign) {
+        unsigned seen = 0;
+        for (int i = 0; i < n; ++i) {
+            const int t = assign[i];
+            if (t < 0 || t >= n || ((seen >> t) & 1u)) return m;
+            seen |= 1u << t;
+        }
+    }
+    m.P = 1 + 2 * n;
+    m.status = E_ENDPOINT;
+    int cxa = g.nx, cxb = -1, cya = g.ny, cyb = -1;
+    for (int p = 0; p < m.P; ++p) {
+        const double x = pts[2 * p], y = pts[2 * p + 1];
+        if (!occ::finite_point(x, y)) return m;
+        if (x < g.x_lo || x > g.x_hi || y < g.y_lo || y > g.y_hi) return m;
+        const int cx = occ::cell_1d(x, g.x_lo, g.inv, g.nx), cy = occ::cell_1d(y, g.y_lo, g.inv, g.ny);
+        cxa = cx < cxa ? cx : cxa; cxb = cx > cxb ? cx : cxb;
+        cya = cy < cya ? cy : cya; cyb = cy > cyb ? cy : cyb;
+    }
+    double md = std::ceil(window_margin / g.res);
+    if (!(md > 0.0)) md = 0.0;
+    if (md > 1.0e9) md = 1.0e9;
+    const long long mg = (long long)md;
+    const long long xa = cxa - mg, xb = cxb + mg, ya = cya - mg, yb = cyb + mg;
+    const int x0 = xa < 0 ? 0 : (int)xa, x1 = xb > g.nx - 1 ? g.nx - 1 : (int)xb;
+    const int y0 = ya < 0 ? 0 : (int)ya, y1 = yb > g.ny - 1 ? g.ny - 1 : (int)yb;
+    m.x0 = x0; m.y0 = y0; m.wx = x1 - x0 + 1; m.wy = y1 - y0 + 1;
+    m.status = ((long long)m.wx * m.wy > psearch::MAX_CELLS) ? E_WINDOW : OK;
+    return m;
+}
+
+// the cell of point p in window coordinates, x * wy + y, and the map's distance there (a checked mission: the point is inside)
+PS_HD int point_cell(const psearch::Grid& g, const Mission& m, const double* pts, int p, double* dist)
+{
+    const int cx = occ::cell_1d(pts[2 * p], g.x_lo, g.inv, g.nx), cy = occ::cell_1d(pts[2 * p + 1], g.y_lo, g.inv, g.ny);
+    *dist = g.dist[(long)cx * g.ny + cy];
+    return (cx - m.x0) * m.wy + (cy - m.y0);
+}
+// the safe distance of the pair (i, j), i < j, from the distances at their cells (jps_planner.cpp:39-42)
+PS_HD double pair_safe(double safe_dis, double dist_i, double dist_j)
+{
+    const double s = psearch::max_of(psearch::min_of(safe_dis, 0.8 * dist_i), 0.0);
+    return psearch::max_of(psearch::min_of(s, 0.8 * dist_j), 0.0);
+}
+// the window of the mission as the search's, its goal the cell of the source: what first_word and relax_cell take
+PS_HD psearch::Window field_window(const Mission& m, int source_cell, double safe)
+{
+    psearch::Window w{};
+    w.status = psearch::OK;
+    w.x0 = m.x0; w.y0 = m.y0; w.wx = m.wx; w.wy = m.wy;
+    w.gx = source_cell / m.wy; w.gy = source_cell - w.gx * m.wy;
+    w.sx = w.gx; w.sy = w.gy;
+    w.safe = safe;
+    return w;
+}
+// d(k, j) from the field of source k at its fixed point
+PS_HD Cost read_cost(const unsigned* words, int cell_k, int cell_j) { return cell_k == cell_j ? Cost{0, 0} : word_cost(words[cell_j]); }
+PS_HD void put_entry(int* mat, int i, int j, Cost c)
+{
+    mat[(i * P_MAX + j) * 2] = c.a;
+    mat[(i * P_MAX + j) * 2 + 1] = c.b;
+}
+
+// the global index of a point of the published order: entry e of order[] is an item (e even) or a target (e odd)
+PS_HD int order_point(int n, const int* order, int e) { return (e & 1) ? n + 1 + order[e] : 1 + order[e]; }
+
+// solvePathWithGreedy on the matrix
+PS_HD void greedy_order(const int* mat, int n, int* order, int* n_order, int* total)
+{
+    unsigned items = 0, targets = 0;
+    int at = 0, cur = 0;
+    Cost sum{0, 0};
+    for (int step = 0; step < n; ++step) {
+        Cost best = inf_cost();
+        int pick = -1;
+        for (int i = 0; i < n; ++i) {
+            if ((items >> i) & 1u) continue;
+            const Cost c = entry(mat, cur, 1 + i);
+            if (less(c, best)) { best = c; pick = i; }
+        }
+        if (pick < 0) break;
+        items |= 1u << pick;
+        cur = 1 + pick;
+        order[at++] = pick;
+        sum = add(sum, best);
+        best = inf_cost();
+        pick = -1;
+        for (int i = 0; i < n; ++i) {
+            if ((targets >> i) & 1u) continue;
+            const Cost c = entry(mat, cur, n + 1 + i);
+            if (less(c, best)) { best = c; pick = i; }
+        }
+        if (pick < 0) break;
+        targets |= 1u << pick;
+        cur = n + 1 + pick;
+        order[at++] = pick;
+        sum = add(sum, best);
+    }
+    *n_order = at;
+    total[0] = sum.a;
+    total[1] = sum.b;
+}
+
+// the optimal mode.  step_cost: serve item i next, standing at point `from`, the items of S served: the two legs and what is left
+PS_HD Cost step_cost(const int* mat, int n, const int* assign, const Cost* togo, int from, unsigned S, int i)
+{
+    const int t = n + 1 + (assign ? assign[i] : i);
+    const Cost legs = add(entry(mat, from, 1 + i), entry(mat, 1 + i, t));
+    return add(legs, togo[(S | (1u << i)) * MAX_TASKS + i]);
+}
+// togo[S][last] from the states with one more item served; S holds `last`
+PS_HD Cost togo_state(const int* mat, int n, const int* assign, const Cost* togo, unsigned S, int last)
+{
+    if (S == (1u << n) - 1u) return Cost{0, 0};
+    const int from = n + 1 + (assign ? assign[last] : last);
+    Cost best = inf_cost();
+    for (int i = 0; i < n; ++i) {
+        if ((S >> i) & 1u) continue;
+        const Cost c = step_cost(mat, n, assign, togo, from, S, i);
+        if (less(c, best)) best = c;
+    }
+    return best;
+}
+PS_HD int popcount(unsigned v)
+{
+    int c = 0;
+    for (; v; v &= v - 1) ++c;
+    return c;
+}
+// forward through the filled table: the lexicographically smallest optimal item sequence.  E_NO_ORDER writes nothing but *n_order
+PS_HD int optimal_order(const int* mat, int n, const int* assign, const Cost* togo, int* order, int* n_order, int* total)
+{
+    *n_order = 0;
+    Cost want = inf_cost();
+    for (int i = 0; i < n; ++i) {
+        const Cost c = step_cost(mat, n, assign, togo, 0, 0u, i);
+        if (less(c, want)) want = c;
+    }
+    if (is_inf(want)) return E_NO_ORDER;
+    total[0] = want.a;
+    total[1] = want.b;
+    unsigned S = 0;
+    int from = 0;
+    for (int step = 0; step < n; ++step) {
+        int pick = -1;
+        for (int i = 0; i < n && pick < 0; ++i)
+            if (!((S >> i) & 1u) && same(step_cost(mat, n, assign, togo, from, S, i), want)) pick = i;
+        if (pick < 0) return E_NO_ORDER; // never: the optimum of a state is attained by one of its steps
+        const int t = assign ? assign[pick] : pick;
+        order[2 * step] = pick;
+        order[2 * step + 1] = t;
+        S |= 1u << pick;
+        from = n + 1 + t;
+        want = togo[S * MAX_TASKS + pick];
+    }
+    *n_order = 2 * n;
+    return OK;
+}
+// the end points of the legs in visit order
+PS_HD void write_legs(const double* pts, int n, const int* order, int n_order, double* leg_start_xy, double* leg_goal_xy)
+{
+    int prev = 0;
+    for (int e = 0; e < n_order; ++e) {
+        const int p = order_point(n, order, e);
+        leg_start_xy[2 * e] = pts[2 * prev]; leg_start_xy[2 * e + 1] = pts[2 * prev + 1];
+        leg_goal_xy[2 * e] = pts[2 * p]; leg_goal_xy[2 * e + 1] = pts[2 * p + 1];
+        prev = p;
+    }
+}
+
+// ---- one mission, serially: words[] holds the window (<= psearch::MAX_CELLS), togo[] STATES pairs (optimal mode) ------------------
+struct Out {
+    int* matrix;          // [P_MAX][P_MAX][2]
+    int* order;           // [MAX_LEGS]
+    int* n_order;
+    int* total;           // [2]
+    double* leg_start_xy; // [MAX_LEGS][2]
+    double* leg_goal_xy;
+    int *fields, *sweeps;
+};
+inline int plan_one(const psearch::Grid& g, int n, int max_tasks, const double* pts, const int* assign, const Params& p, unsigned* words,
+                    Cost* togo, const Out& o)
+{
+    const Mission m = check_mission(g, n, max_tasks, pts, assign, p.mode, p.window_margin);
+    if (m.status != OK) { *o.n_order = 0; return m.status; }
+    int cell[P_MAX];
+    double dist[P_MAX], safe[P_MAX];
+    for (int j = 0; j < m.P; ++j) cell[j] = point_cell(g, m, pts, j, &dist[j]);
+    int fields = 0, most = 0;
+    for (int k = 0; k < m.P; ++k) put_entry(o.matrix, k, k, Cost{0, 0});
+    for (int k = 0; k < m.P - 1; ++k) {
+        for (int j = k + 1; j < m.P; ++j) safe[j] = pair_safe(p.safe_dis, dist[k], dist[j]);
+        for (int j = k + 1; j < m.P; ++j) {
+            bool first = true;
+            for (int e = k + 1; e < j; ++e) first = first && !(safe[e] == safe[j]);
+            if (!first) continue;
+            const psearch::Window w = field_window(m, cell[k], safe[j]);
+            for (int x = 0; x < w.wx; ++x)
+                for (int y = 0; y < w.wy; ++y) words[x * w.wy + y] = psearch::first_word(g, w, x, y);
+            int sweeps = 0;
+            for (bool changed = true; changed;) {
+                changed = false;
+                if (sweeps & 1) {
+                    for (int x = w.wx - 1; x >= 0; --x)
+                        for (int y = w.wy - 1; y >= 0; --y) changed |= psearch::relax_cell(words, w.wx, w.wy, x, y);
+                } else {
+                    for (int x = 0; x < w.wx; ++x)
+                        for (int y = 0; y < w.wy; ++y) changed |= psearch::relax_cell(words, w.wx, w.wy, x, y);
+                }
+                ++sweeps;
+            }
+            ++fields;
+            most = sweeps > most ? sweeps : most;
+            for (int e = j; e < m.P; ++e) {
+                if (!(safe[e] == safe[j])) continue;
+                const Cost c = read_cost(words, cell[k], cell[e]);
+                put_entry(o.matrix, k, e, c);
+                put_entry(o.matrix, e, k, c);
+            }
+        }
+    }
+    *o.fields = fields;
+    *o.sweeps = most;
+    int status = OK;
+    if (p.mode == OPTIMAL) {
+        for (int level = n; level >= 1; --level)
+            for (unsigned S = 1; S < (1u << n); ++S) {
+                if (popcount(S) != level) continue;
+                for (int last = 0; last < n; ++last)
+                    if ((S >> last) & 1u) togo[S * MAX_TASKS + last] = togo_state(o.matrix, n, assign, togo, S, last);
+            }
+        status = optimal_order(o.matrix, n, assign, togo, o.order, o.n_order, o.total);
+    } else {
+        greedy_order(o.matrix, n, o.order, o.n_order, o.total);
+    }
+    if (status == OK) write_legs(pts, n, o.order, *o.n_order, o.leg_start_xy, o.leg_goal_xy);
+    return status;
+}
+
+} // namespace tplan
+
+#endif

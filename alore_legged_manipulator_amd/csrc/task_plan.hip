@@ -1,0 +1,215 @@
+// task_plan.hip -- the visit order of rearrangement missions from path costs on the device map (alore_backend_task_plan); the
+// contract and the arithmetic in task_plan.h.
+//
+// task_costs_kernel: one workgroup of 1024 threads per (mission, source point k), for the targets j > k.  Every thread repeats the
+// mission's checks (uniform, scalar); a workgroup that is masked out, surplus (k >= P - 1) or whose mission fails returns there,
+// before any LDS access or barrier, and workgroup k = 0 alone writes the status of such a mission.  The others use the search
+// kernel's field machinery (path_search.hip): psearch::first_word and psearch::relax_cell, one word per window cell in LDS, gather
+// sweeps with one writer per word, alternating direction, an odd run length per thread, a workgroup-wide OR to stop.  The goal of
+// the field is the SOURCE's cell, so after the fixed point the words at the target cells are d(k, j) for every j at once: thread
+// j writes (k, j) and (j, k).  Targets whose safe_kj are equal share a field; a source whose targets differ in it runs one field
+// per distinct value, in order of first appearance.  Every matrix entry has one writer: workgroup k writes row and column k
+// beyond the diagonal and (k, k), workgroup P - 2 also (P - 1, P - 1).  No atomics: the per-source field and sweep counts go to
+// src_fields / src_sweeps, which task_order_kernel adds up.
+// LDS: 512 bytes of tables (the cells of the points, safe_kj) and 4 bytes per cell of the largest window the map allows,
+// min(nx ny, 32768): up to 128.5 KiB, one workgroup per CU then.
+//
+// task_order_kernel: one workgroup of 256 threads per mission, behind the first kernel on the same stream.  The matrix goes to LDS.
+// The optimal mode fills togo[S][last] (80 KiB of LDS, requested in that mode alone: a greedy launch takes 3.5 KiB) level by level in the size of the served set, from n down to 1, a barrier
+// per level: the states of a level read the level above only.  Thread 0 then runs the reconstruction, or the greedy mode, and
+// writes order, total and legs; it also adds up the diagnostics.
+#include "backend_kernels.h"
+#include "task_plan.h"
+
+namespace backend {
+
+namespace ps = psearch;
+namespace tp = tplan;
+
+constexpr int COST_THREADS = 1024, ORDER_THREADS = 256;
+constexpr int TABLE_BYTES = 512;                                   // safe[32] doubles, cell[32] ints, padding
+constexpr int TOGO_BYTES = tp::STATES * (int)sizeof(tp::Cost);     // 81920
+constexpr int MATRIX_INTS = tp::P_MAX * tp::P_MAX * 2;
+// LDS of task_order_kernel: the matrix, the order of thread 0 (no private array), and in the optimal mode alone the states behind them
+constexpr int ORDER_AT = (MATRIX_INTS * (int)sizeof(int) + 15) & ~15;
+constexpr int TOGO_AT = ORDER_AT + ((tp::MAX_LEGS * (int)sizeof(int) + 15) & ~15);
+constexpr int GREEDY_LDS_BYTES = TOGO_AT, OPTIMAL_LDS_BYTES = TOGO_AT + TOGO_BYTES;
+
+extern __shared__ __align__(16) unsigned char task_lds[];
+
+struct MissionIn {
+    const double* pts;
+    const int* assign;
+    int n;
+    bool masked;
+};
+__device__ inline MissionIn mission_in(const TaskArgs& a, int m)
+{
+    MissionIn in;
+    in.masked = a.mask && *(const int*)((const char*)a.mask + (size_t)m * a.mask_stride) == 0;
+    in.pts = (const double*)((const char*)a.points + (size_t)m * a.point_row_stride);
+    in.assign = a.assign ? a.assign + (size_t)m * a.max_tasks : nullptr;
+    in.n = a.n_tasks[m];
+    return in;
+}
+
+__global__ __launch_bounds__(COST_THREADS) void task_costs_kernel(const TaskArgs* __restrict__ gp)
+{
+    const TaskArgs& a = *gp;
+    const int sources = 2 * a.max_tasks; // workgroups per mission: the sources 0 .. P_max - 2
+    const int m = blockIdx.x / sources, k = blockIdx.x - m * sources, tid = threadIdx.x;
+    const MissionIn in = mission_in(a, m);
+    if (in.masked) {
+        if (k == 0 && tid == 0) a.status[m] = tp::MASKED;
+        return;
+    }
+    const ps::Grid g = ps::make_grid(a.map.dist, a.map.nx, a.map.ny, a.map.x_lo, a.map.y_lo, a.map.x_hi, a.map.y_hi, a.map.res);
+    tp::Mission ms = tp::check_mission(g, in.n, a.max_tasks, in.pts, in.assign, a.mode, a.window_margin); // the same in every thread
+    const int cells = ms.wx * ms.wy;
+    if (ms.status == tp::OK && cells > a.lds_cells) ms.status = tp::E_WINDOW; // cannot happen: a window is clipped to the map
+    if (ms.status != tp::OK) {
+        if (k == 0 && tid == 0) {
+            a.status[m] = ms.status;
+            a.n_order[m] = 0;
+        }
+        return;
+    }
+    const int P = ms.P;
+    if (k >= P - 1) return; // surplus: the mission has fewer points than the launch allows
+    double* safe = (double*)task_lds;
+    int* cell = (int*)(task_lds + 256);
+    unsigned* words = (unsigned*)(task_lds + TABLE_BYTES);
+    int* mat = a.matrix + (size_t)m * MATRIX_INTS;
+    if (tid < P) {
+        double dj, dk;
+        cell[tid] = tp::point_cell(g, ms, in.pts, tid, &dj);
+        (void)tp::point_cell(g, ms, in.pts, k, &dk);
+        safe[tid] = tp::pair_safe(a.safe_dis, dk, dj); // used for tid > k only
+    }
+    if (tid == 0) {
+        tp::put_entry(mat, k, k, tp::Cost{0, 0});
+        if (k == P - 2) tp::put_entry(mat, P - 1, P - 1, tp::Cost{0, 0});
+    }
+    __syncthreads();
+    const int cell_k = cell[k];
+    const int chunk = ((cells + COST_THREADS - 1) / COST_THREADS) | 1;
+    const int lo = min(tid * chunk, cells), hi = min(lo + chunk, cells);
+    int fields = 0, most = 0;
+    for (int j = k + 1; j < P; ++j) {
+        const double s = safe[j];
+        bool first = true;
+        for (int e = k + 1; e < j; ++e) first = first && !(safe[e] == s);
+        if (!first) continue; // uniform
+        const ps::Window w = tp::field_window(ms, cell_k, s);
+        for (int c = tid; c < cells; c += COST_THREADS) {
+            const int x = c / w.wy;
+            words[c] = ps::first_word(g, w, x, c - x * w.wy);
+        }
+        __syncthreads();
+        int sweeps = 0;
+        for (;;) {
+            int changed = 0;
+            if (lo < hi) {
+                if (sweeps & 1) {
+                    int x = (hi - 1) / w.wy, y = (hi - 1) - x * w.wy;
+                    for (int c = hi - 1; c >= lo; --c) {
+                        changed |= (int)ps::relax_cell(words, w.wx, w.wy, x, y);
+                        if (--y < 0) { y = w.wy - 1; --x; }
+                    }
+                } else {
+                    int x = lo / w.wy, y = lo - x * w.wy;
+                    for (int c = lo; c < hi; ++c) {
+                        changed |= (int)ps::relax_cell(words, w.wx, w.wy, x, y);
+                        if (++y == w.wy) { y = 0; ++x; }
+                    }
+                }
+            }
+            ++sweeps;
+            if (!__syncthreads_or(changed)) break;
+        }
+        ++fields;
+        most = max(most, sweeps);
+        if (tid >= j && tid < P && safe[tid] == s) {
+            const tp::Cost c = tp::read_cost(words, cell_k, cell[tid]);
+            tp::put_entry(mat, k, tid, c);
+            tp::put_entry(mat, tid, k, c);
+        }
+        __syncthreads(); // the words are read out before the next field overwrites them
+    }
+    if (tid == 0) {
+        a.src_fields[(size_t)m * tp::MAX_LEGS + k] = fields;
+        a.src_sweeps[(size_t)m * tp::MAX_LEGS + k] = most;
+    }
+}
+
+__global__ __launch_bounds__(ORDER_THREADS) void task_order_kernel(const TaskArgs* __restrict__ gp)
+{
+    const TaskArgs& a = *gp;
+    const int m = blockIdx.x, tid = threadIdx.x;
+    const MissionIn in = mission_in(a, m);
+    if (in.masked) return; // task_costs_kernel wrote the status
+    const ps::Grid g = ps::make_grid(a.map.dist, a.map.nx, a.map.ny, a.map.x_lo, a.map.y_lo, a.map.x_hi, a.map.y_hi, a.map.res);
+    const tp::Mission ms = tp::check_mission(g, in.n, a.max_tasks, in.pts, in.assign, a.mode, a.window_margin);
+    if (ms.status != tp::OK || ms.wx * ms.wy > a.lds_cells) return; // likewise
+    const int n = in.n, P = ms.P;
+    int* mat = (int*)task_lds;
+    tp::Cost* togo = a.mode == tp::OPTIMAL ? (tp::Cost*)(task_lds + TOGO_AT) : nullptr; // a greedy launch has no LDS for the states
+    const int* gm = a.matrix + (size_t)m * MATRIX_INTS;
+    for (int e = tid; e < P * P; e += ORDER_THREADS) {
+        const int i = e / P, j = e - i * P, at = (i * tp::P_MAX + j) * 2;
+        mat[at] = gm[at];
+        mat[at + 1] = gm[at + 1];
+    }
+    __syncthreads();
+    if (a.mode == tp::OPTIMAL) {
+        for (int level = n; level >= 1; --level) {
+            for (unsigned S = tid; S < (1u << n); S += ORDER_THREADS) {
+                if (__popc(S) != level) continue;
+                for (int last = 0; last < n; ++last)
+                    if ((S >> last) & 1u) togo[S * tp::MAX_TASKS + last] = tp::togo_state(mat, n, in.assign, togo, S, last);
+            }
+            __syncthreads();
+        }
+    }
+    if (tid != 0) return;
+    int* order = (int*)(task_lds + ORDER_AT);
+    int n_order = 0, total[2] = {0, 0}, status = tp::OK;
+    if (a.mode == tp::OPTIMAL) status = tp::optimal_order(mat, n, in.assign, togo, order, &n_order, total);
+    else tp::greedy_order(mat, n, order, &n_order, total);
+    int fields = 0, most = 0;
+    for (int k = 0; k < P - 1; ++k) {
+        fields += a.src_fields[(size_t)m * tp::MAX_LEGS + k];
+        most = max(most, a.src_sweeps[(size_t)m * tp::MAX_LEGS + k]);
+    }
+    a.status[m] = status;
+    a.n_order[m] = n_order;
+    a.fields[m] = fields;
+    a.sweeps[m] = most;
+    if (status != tp::OK) return;
+    a.total[2 * (size_t)m] = total[0];
+    a.total[2 * (size_t)m + 1] = total[1];
+    for (int e = 0; e < n_order; ++e) a.order[(size_t)m * tp::MAX_LEGS + e] = order[e];
+    tp::write_legs(in.pts, n, order, n_order, a.leg_start_xy + (size_t)m * tp::MAX_LEGS * 2, a.leg_goal_xy + (size_t)m * tp::MAX_LEGS * 2);
+}
+
+static size_t cost_lds_bytes(int lds_cells) { return TABLE_BYTES + sizeof(unsigned) * (size_t)lds_cells; }
+
+hipError_t task_configure()
+{
+    hipError_t e = hipFuncSetAttribute((const void*)task_costs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cost_lds_bytes(ps::MAX_CELLS));
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute((const void*)task_order_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, OPTIMAL_LDS_BYTES);
+}
+
+hipError_t task_plan(const TaskArgs* d_args, int count, int max_tasks, int mode, int lds_cells, hipStream_t s)
+{
+    void* args[] = {&d_args};
+    hipError_t e = hipLaunchKernel((const void*)task_costs_kernel, dim3(count * 2 * max_tasks), dim3(COST_THREADS), args, cost_lds_bytes(lds_cells), s);
+    if (e != hipSuccess) return e;
+    e = hipLaunchKernel((const void*)task_order_kernel, dim3(count), dim3(ORDER_THREADS), args,
+                        mode == tp::OPTIMAL ? OPTIMAL_LDS_BYTES : GREEDY_LDS_BYTES, s);
+    if (e != hipSuccess) return e;
+    return hipGetLastError();
+}
+
+} // namespace backend

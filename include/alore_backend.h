@@ -388,6 +388,74 @@ int alore_backend_get_paths(alore_backend_handle h, int count, int *n_points, do
 /* diagnostic: sweeps over the window until the field stood still, per slot of the last search; HOST out[count]; waits */
 int alore_backend_search_sweeps(alore_backend_handle h, int count, int *out);
 
+/* ---- the visit order of rearrangement missions from path costs on the handle's map, on the device --------------------- */
+/* What plan_manager does before any trajectory is planned (plan_manager.hpp:210-250): the grid-path length between the robot, n
+ * items and n targets, then the order of the visits -- solvePathWithGreedy (:347-432, the reference's live call) or the
+ * fixed-assignment routing of BranchAndBoundCombined::solve (:252-345, branch_and_bound.hpp).  The contract, with exactly one answer
+ * for the cost matrix and for both orders, is stated in csrc/task_plan.h.  A mission has P = 1 + 2 n points: 0 the robot, 1..n the
+ * items, n+1..2n the targets.  d(i, j) is the least cost a + b sqrt 2 on the search's graph between the cells of points i and j
+ * inside the MISSION's window (the bounding box of all P cells grown by ceil(window_margin / res) cells a side, clipped, at most
+ * ALORE_BE_SEARCH_MAX_CELLS cells) with the pair's safe distance, as the exact pair (a, b); (0, 0) for equal cells, (-1, -1) where
+ * there is no path.  Costs are added and ordered exactly, in integers.  Deviations from the reference: the window (the reference
+ * searches the whole map); a point outside the map is refused, not clamped; the optimal mode returns, among optimal orders, the
+ * lexicographically smallest item sequence (the reference's best-first search returns an optimum); a leg searched afterwards by
+ * alore_backend_search_paths uses that pair's own smaller window, so its cost_ab can exceed the matrix entry.  Two kernels
+ * (csrc/task_plan.hip): one workgroup per (mission, source point) fills the matrices, one cost-to-source field serving every
+ * other point of the mission; one workgroup per mission then finds the order. */
+#define ALORE_BE_TASK_MAX_TASKS 10
+#define ALORE_BE_TASK_MAX_POINTS 21 /* 1 + 2 * ALORE_BE_TASK_MAX_TASKS */
+#define ALORE_BE_TASK_MAX_LEGS 20
+#define ALORE_BE_TASK_GREEDY 0
+#define ALORE_BE_TASK_OPTIMAL 1
+/* task status of a mission */
+#define ALORE_BE_TASK_OK 0
+#define ALORE_BE_TASK_MASKED 1          /* the mask left the mission out: only its status was written */
+#define ALORE_BE_TASK_E_ENDPOINT (-1)   /* a point of the mission is not finite or outside [lo, hi] of the map */
+#define ALORE_BE_TASK_E_WINDOW (-3)     /* the mission's window has more than ALORE_BE_SEARCH_MAX_CELLS cells */
+#define ALORE_BE_TASK_E_TASKS (-6)      /* n outside 1..max_tasks, or (optimal mode) an assignment that is no permutation */
+#define ALORE_BE_TASK_E_NO_ORDER (-7)   /* optimal mode: no order has a finite cost (the matrix is written) */
+typedef struct alore_backend_task_params {
+    double safe_dis;      /* jps_safe_dis */
+    double window_margin; /* metres round the bounding box of the mission's points */
+    int mode;             /* ALORE_BE_TASK_GREEDY or ALORE_BE_TASK_OPTIMAL */
+} alore_backend_task_params;
+/* 0.3, 3.0 and ALORE_BE_TASK_GREEDY */
+void alore_backend_task_default_params(alore_backend_task_params *p);
+/* Plans missions 0..count-1 (count <= max_problems) on the handle's current map.  Mission m has n_tasks[m] tasks, 1..max_tasks
+ * (max_tasks <= ALORE_BE_TASK_MAX_TASKS); its points are packed at the beginning of a row of 1 + 2 max_tasks (x, y) pairs at
+ * (char *)points + m * point_row_stride_bytes (a multiple of 8, at least 16 (1 + 2 max_tasks)).  assignment_or_null:
+ * [count][max_tasks] ints, item i of mission m goes to target assignment[m * max_tasks + i]; read in the optimal mode only; NULL:
+ * the identity.  params NULL: the defaults.  The mask is read as alore_backend_search_paths reads its mask.
+ * A failed mission has a negative status and n_order = 0, nothing else of it is written (ALORE_BE_TASK_E_NO_ORDER: its matrix and
+ * diagnostics are).  device_pointers != 0: n_tasks, points, assignment and mask are DEVICE memory read in stream order; nothing
+ * crosses the bus but the argument block and nothing waits.  device_pointers == 0: they are HOST memory; they are uploaded, the
+ * stream is synchronised, and the call returns, for the first mission that failed, ALORE_BE_E_INVALID (tasks, end point, no order)
+ * or ALORE_BE_E_UNSUPPORTED (window); the error text of such a return begins with "task_plan: mission failed", every other error means
+ * that nothing was launched and the slab is as it was.
+ * Successive calls on one handle must be ordered on the device, on one stream or by events: the argument block on the device is the
+ * handle's, and a call overwrites it while the kernels of an earlier call on an unordered stream may still read it. */
+int alore_backend_task_plan(alore_backend_handle h, int count, int max_tasks, const int *n_tasks, const double *points,
+                            int point_row_stride_bytes, const int *assignment_or_null, const alore_backend_task_params *params,
+                            int device_pointers, const int *mask, int mask_stride_bytes, void *stream);
+/* The handle's device slab of the missions [max_problems].  Leg l of every mission goes into alore_backend_search_paths
+ * (device_pointers = 1) as it lies: start_xy = leg_start_xy + 2 l, goal_xy = leg_goal_xy + 2 l, both strides
+ * ALORE_BE_TASK_MAX_LEGS * 16 bytes.  Rows of order and of the legs beyond n_order are left untouched. */
+typedef struct alore_backend_task_view {
+    int max_points, max_legs; /* 21, 20 */
+    const int *status;        /* [.] */
+    const int *matrix;        /* [.][21][21][2]: (a, b) of d(i, j) for i, j < P */
+    const int *order;         /* [.][20]: item index, target index, alternately, each 0-based in its own group */
+    const int *n_order;       /* [.] */
+    const int *total;         /* [.][2]: the cost of the whole route */
+    const double *leg_start_xy, *leg_goal_xy; /* [.][20][2] */
+    const int *fields;        /* [.] diagnostic: cost fields computed for the mission */
+    const int *sweeps;        /* [.] diagnostic: the most sweeps any of them needed */
+} alore_backend_task_view;
+int alore_backend_device_task(alore_backend_handle h, alore_backend_task_view *out);
+/* The slab copied to HOST arrays with the shapes above and [count] rows (any pointer may be NULL).  Waits for the device. */
+int alore_backend_get_task(alore_backend_handle h, int count, int *status, int *matrix, int *order, int *n_order, int *total,
+                           double *leg_start_xy, double *leg_goal_xy, int *fields, int *sweeps);
+
 #ifdef __cplusplus
 }
 #endif
