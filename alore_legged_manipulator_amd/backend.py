@@ -100,6 +100,20 @@ class MapViewC(C.Structure):
                 ("x_lo", C.c_double), ("y_lo", C.c_double), ("res", C.c_double)]
 
 
+class LaserParamsC(C.Structure):
+    """alore_backend_laser_params (include/alore_backend.h): the parameters of the reference's laser simulator"""
+    _fields_ = [("sensing_horizon", C.c_double), ("pc_resolution", C.c_double), ("hrz_laser_line_num", C.c_int),
+                ("vtc_laser_line_num", C.c_int), ("vtc_laser_range_dgr", C.c_double), ("hrz_limited", C.c_int),
+                ("hrz_laser_range_dgr", C.c_double), ("use_resolution_filter", C.c_int), ("if_perspective", C.c_int)]
+
+
+class LaserViewC(C.Structure):
+    """alore_backend_laser_view: device addresses of the slabs of the scans"""
+    _fields_ = [("range_image", C.c_void_p), ("laser_points", C.c_void_p), ("world_points", C.c_void_p), ("index", C.c_void_p),
+                ("compact_points", C.c_void_p), ("n_points", C.c_void_p), ("status", C.c_void_p), ("slots", C.c_int), ("bins", C.c_int),
+                ("max_scans", C.c_int)]
+
+
 class SearchParamsC(C.Structure):
     """alore_backend_search_params (include/alore_backend.h)"""
     _fields_ = [("safe_dis", C.c_double), ("window_margin", C.c_double)]
@@ -123,6 +137,8 @@ TASK_GREEDY, TASK_OPTIMAL = 0, 1
 TASK_OK, TASK_MASKED, TASK_E_ENDPOINT, TASK_E_WINDOW, TASK_E_TASKS, TASK_E_NO_ORDER = 0, 1, -1, -3, -6, -7
 SEARCH_OK, SEARCH_MASKED, SEARCH_E_ENDPOINT, SEARCH_E_SAME_CELL, SEARCH_E_WINDOW, SEARCH_E_NO_PATH, SEARCH_E_POINTS = 0, 1, -1, -2, -3, -4, -5
 SEARCH_MAX_CELLS = 32768
+LASER_OK, LASER_E_POSE, LASER_E_CAPACITY = 0, -1, -2
+LASER_MAX_BINS = 8192
 BUILD_OK, BUILD_MASKED, BUILD_E_POINTS, BUILD_E_PIECES = 0, 1, -1, -2
 
 
@@ -173,6 +189,14 @@ def _bind(L):
     L.alore_backend_map_update_esdf.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p]
     L.alore_backend_map_get.argtypes = [C.c_void_p, C.POINTER(C.c_ubyte), DP, DP]
     L.alore_backend_map_device.argtypes = [C.c_void_p, C.POINTER(MapViewC)]
+    L.alore_backend_laser_default_params.argtypes = [C.POINTER(LaserParamsC)]
+    L.alore_backend_laser_default_params.restype = None
+    L.alore_backend_laser_create.argtypes = [C.c_void_p, C.POINTER(LaserParamsC), C.c_int, C.c_int]
+    L.alore_backend_laser_set_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.alore_backend_laser_scan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.alore_backend_device_laser.argtypes = [C.c_void_p, C.POINTER(LaserViewC)]
+    L.alore_backend_get_laser.argtypes = [C.c_void_p, C.c_int, DP] + [C.POINTER(C.c_float)] * 2 + [C.POINTER(C.c_int), C.POINTER(C.c_float)] + \
+        [C.POINTER(C.c_int)] * 2
     L.alore_backend_search_default_params.argtypes = [C.POINTER(SearchParamsC)]
     L.alore_backend_search_default_params.restype = None
     L.alore_backend_search_paths.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(SearchParamsC), C.c_int,
@@ -210,6 +234,23 @@ def default_map_params() -> MapParamsC:
     p = MapParamsC()
     L.alore_backend_map_default_params(C.byref(p))
     return p
+
+
+def default_laser_params() -> LaserParamsC:
+    """planner_sim.launch and perspective_laser.yaml: horizon 27 m, resolution 0.1 m, 360 x 16 lines over 30 degrees, no horizontal
+    limit, no filter, perspective mode"""
+    L = _lib.load()
+    _bind(L)
+    p = LaserParamsC()
+    L.alore_backend_laser_default_params(C.byref(p))
+    return p
+
+
+class _DeviceArray:
+    """a device allocation of the library as torch.as_tensor reads it"""
+
+    def __init__(self, address, shape, typestr):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(address), False), "version": 2}
 
 
 def default_search_params() -> SearchParamsC:
@@ -525,6 +566,96 @@ class BatchedMSPlanner:
         self._check(self.L.alore_backend_get_problems(self.h, n, out["n_pieces"].ctypes.data_as(ip), _dp(out["inner"]), _dp(out["init_T"]),
                                                       _dp(out["positions"]), _dp(out["head"]), _dp(out["tail"]), _dp(out["start_xytheta"]),
                                                       _dp(out["final_xy"]), out["if_cut"].ctypes.data_as(ip)))
+        return out
+
+    # ---- laser scans of a resident world cloud (alore_backend_laser_*)
+    def laser_create(self, max_scans: int, max_points_per_scan: int = 0, params: LaserParamsC | None = None, **fields):
+        """The reference's laser simulator for batches of up to max_scans poses.  params: a LaserParamsC (None: the defaults),
+        fields: single members to change (if_perspective=0, sensing_horizon=10.0, ...).  max_points_per_scan: the slots of a scan
+        in perspective mode (range mode has hrz x vtc).  Replaces a sensor created before, cloud included."""
+        p = LaserParamsC()
+        if params is None:
+            self.L.alore_backend_laser_default_params(C.byref(p))
+        else:
+            C.memmove(C.byref(p), C.byref(params), C.sizeof(p))
+        for k, v in fields.items():
+            if k not in dict(LaserParamsC._fields_):
+                raise TypeError(f"alore_backend_laser_params has no field {k}")
+            setattr(p, k, v)
+        self._check(self.L.alore_backend_laser_create(self.h, C.byref(p), int(max_scans), int(max_points_per_scan)))
+        self.laser_params = p
+        self.laser_count = 0
+
+    def laser_set_cloud(self, points, stream=None, stride_bytes: int | None = None):
+        """The world cloud: NumPy [n][3 or 4] (converted to float32, uploaded, waits), a torch float32 device tensor [n][k >= 3]
+        with unit stride along k, or a raw device address given as (address, n) with stride_bytes (default 12); device points are
+        copied in stream order."""
+        if isinstance(points, tuple):
+            ptr, n, stride, dev = int(points[0]) or None, int(points[1]), int(stride_bytes or 12), 1
+        elif isinstance(points, np.ndarray) or not hasattr(points, "data_ptr"):
+            q = np.asarray(points, np.float32)
+            q = np.ascontiguousarray(q.reshape(len(q), -1)) if q.size else np.zeros((0, 3), np.float32)
+            ptr, n, stride, dev = q.ctypes.data if q.size else None, q.shape[0], int(stride_bytes or q.shape[1] * 4), 0
+        else:
+            if str(points.dtype) != "torch.float32" or points.dim() != 2 or (points.shape[0] and points.stride(1) != 1):
+                raise BackendError("laser_set_cloud: device points must be a float32 tensor [n][k >= 3] with unit stride along k")
+            ptr, n, dev = int(points.data_ptr()) if points.shape[0] else None, int(points.shape[0]), 1
+            stride = int(stride_bytes or (points.stride(0) * 4 if n else 12))
+        self._check(self.L.alore_backend_laser_set_cloud(self.h, ptr, n, stride, dev, _stream(stream)))
+
+    def laser_scan(self, poses, count: int | None = None, stream=None, pose_stride_bytes: int | None = None):
+        """Renders one scan per pose (x, y, yaw).  poses: NumPy [count][>= 3] (uploaded with the argument block; waits), a torch
+        float64 device tensor [count][>= 3] (its own row stride: the xytheta of predicted_state_device serves as it lies) or a raw
+        device address with count and pose_stride_bytes (default 24); device poses are read in stream order and nothing waits.
+        laser_results() / laser_device_view() have the outcome; every scan has its own status."""
+        if isinstance(poses, int):
+            n, ptr, stride, dev = int(count), poses, int(pose_stride_bytes or 24), 1
+        elif hasattr(poses, "data_ptr"):
+            if str(poses.dtype) != "torch.float64" or poses.dim() != 2 or poses.stride(1) != 1:
+                raise BackendError("laser_scan: device poses must be a float64 tensor [count][>= 3] with unit stride along the row")
+            n, ptr, dev = int(count or poses.shape[0]), int(poses.data_ptr()), 1
+            stride = int(pose_stride_bytes or poses.stride(0) * 8)
+        else:
+            q = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(len(poses), -1))
+            n, ptr, stride, dev = int(count or q.shape[0]), q.ctypes.data, q.strides[0], 0
+        self.laser_count = n
+        self._check(self.L.alore_backend_laser_scan(self.h, n, ptr, stride, dev, _stream(stream)))
+
+    def laser_view(self) -> LaserViewC:
+        v = LaserViewC()
+        self._check(self.L.alore_backend_device_laser(self.h, C.byref(v)))
+        return v
+
+    def laser_device_view(self) -> dict:
+        """torch views on the device slabs (no copy): range_image [max_scans][hrz][vtc] (None in perspective mode), laser_points,
+        world_points and compact_points [max_scans][slots][3], index [max_scans][slots], n_points and status [max_scans].  A row
+        of world_points goes straight into map_integrate([(row, pose)]): NaN slots are skipped there."""
+        import torch
+        v = self.laser_view()
+        S, n = v.max_scans, v.slots
+
+        def view(ptr, shape, typestr):
+            return torch.as_tensor(_DeviceArray(ptr, shape, typestr), device="cuda") if ptr else None
+        p = self.laser_params
+        return {"range_image": view(v.range_image, (S, p.hrz_laser_line_num, p.vtc_laser_line_num), "<f8"),
+                "laser_points": view(v.laser_points, (S, n, 3), "<f4"), "world_points": view(v.world_points, (S, n, 3), "<f4"),
+                "index": view(v.index, (S, n), "<i4"), "compact_points": view(v.compact_points, (S, n, 3), "<f4"),
+                "n_points": view(v.n_points, (S,), "<i4"), "status": view(v.status, (S,), "<i4")}
+
+    def laser_results(self, count: int | None = None) -> dict:
+        """the slabs of the last scans copied to the host (waits): the arrays of laser_device_view() with count for max_scans;
+        range_image is None in perspective mode"""
+        n = int(count or getattr(self, "laser_count", 0))
+        v, p = self.laser_view(), self.laser_params
+        out = {"range_image": np.zeros((n, p.hrz_laser_line_num, p.vtc_laser_line_num)) if v.range_image else None,
+               "laser_points": np.zeros((n, v.slots, 3), np.float32), "world_points": np.zeros((n, v.slots, 3), np.float32),
+               "index": np.zeros((n, v.slots), np.int32), "compact_points": np.zeros((n, v.slots, 3), np.float32),
+               "n_points": np.zeros(n, np.int32), "status": np.zeros(n, np.int32)}
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        self._check(self.L.alore_backend_get_laser(self.h, n, _dp(out["range_image"]), out["laser_points"].ctypes.data_as(fp),
+                                                   out["world_points"].ctypes.data_as(fp), out["index"].ctypes.data_as(ip),
+                                                   out["compact_points"].ctypes.data_as(fp), out["n_points"].ctypes.data_as(ip),
+                                                   out["status"].ctypes.data_as(ip)))
         return out
 
     # ---- way-point paths by grid search on the handle's map (alore_backend_search_paths)

@@ -9,6 +9,7 @@
 
 #include "backend_kernels.h"
 #include "flat_traj_build.h"
+#include "laser_scan_launch.h"
 #include "path_search.h"
 #include "task_plan.h"
 
@@ -80,6 +81,18 @@ struct alore_backend_planner {
     double *t_leg_start = nullptr, *t_leg_goal = nullptr;
     hipEvent_t ev_task = nullptr; // the upload of the previous call has left h_task
     bool task_pending = false;
+    // alore_backend_laser_*: the sensor (alore_backend_laser_create), its world cloud and the slabs of the scans; the argument
+    // block is followed by the staged poses of the host route, pinned and on the device
+    bool has_laser = false, has_cloud = false;
+    laser::Derived laser_d{};
+    int laser_scans = 0, laser_slots = 0, laser_bins = 0, n_cloud = 0;
+    size_t cloud_cap = 0; // points
+    float *d_cloud = nullptr, *l_laser = nullptr, *l_world = nullptr, *l_compact = nullptr;
+    double *l_tables = nullptr, *l_image = nullptr;
+    int *l_index = nullptr, *l_n = nullptr, *l_status = nullptr;
+    char *h_laser = nullptr, *d_laser_in = nullptr;
+    hipEvent_t ev_laser = nullptr; // the upload of the previous call has left h_laser
+    bool laser_pending = false;
 };
 
 namespace {
@@ -127,9 +140,29 @@ void end_map(alore_backend_handle h)
     h->resident = false;
 }
 
+// ends the sensor of alore_backend_laser_create: slabs, tables, cloud and argument block
+void end_laser(alore_backend_handle h)
+{
+    if (!h->has_laser && !h->d_cloud && !h->h_laser) return;
+    (void)hipDeviceSynchronize();
+    void* ptrs[] = {h->d_cloud, h->l_laser, h->l_world, h->l_compact, h->l_tables, h->l_image, h->l_index, h->l_n, h->l_status, h->d_laser_in};
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+    if (h->h_laser) (void)hipHostFree(h->h_laser);
+    h->d_cloud = h->l_laser = h->l_world = h->l_compact = nullptr;
+    h->l_tables = h->l_image = nullptr;
+    h->l_index = h->l_n = h->l_status = nullptr;
+    h->h_laser = h->d_laser_in = nullptr;
+    h->cloud_cap = 0;
+    h->n_cloud = h->laser_scans = h->laser_slots = h->laser_bins = 0;
+    h->has_laser = h->has_cloud = h->laser_pending = false;
+}
+
 void free_all(alore_backend_handle h)
 {
     end_map(h);
+    end_laser(h);
+    if (h->ev_laser) (void)hipEventDestroy(h->ev_laser);
     if (h->ev_scan) (void)hipEventDestroy(h->ev_scan);
     if (h->ev_scan_done) (void)hipEventDestroy(h->ev_scan_done);
     if (h->d_stamps) {
@@ -213,6 +246,10 @@ BuildLayout build_layout(size_t n, size_t K)
 // the block of alore_backend_search_paths: arguments, then (host route) starts [n][2], goals [n][2] and the mask [n]
 constexpr size_t SEARCH_ARGS_BYTES = (sizeof(backend::SearchArgs) + 15) & ~size_t(15);
 size_t search_in_bytes(size_t n) { return SEARCH_ARGS_BYTES + sizeof(double) * 4 * n + sizeof(int) * n; }
+
+// the block of alore_backend_laser_scan: arguments, then (host route) the poses [n][3]
+constexpr size_t LASER_ARGS_BYTES = (sizeof(backend::LaserArgs) + 15) & ~size_t(15);
+size_t laser_in_bytes(size_t n) { return LASER_ARGS_BYTES + sizeof(double) * 3 * n; }
 
 // the block of alore_backend_task_plan: arguments, then (host route) points [n][1 + 2 T][2], n_tasks [n], assignment [n][T], mask [n]
 constexpr size_t TASK_ARGS_BYTES = (sizeof(backend::TaskArgs) + 15) & ~size_t(15);
@@ -992,6 +1029,153 @@ int alore_backend_map_device(alore_backend_handle h, alore_backend_map_view* out
     if (!out) return fail(h, ALORE_BE_E_INVALID, "map_device: bad argument");
     const backend::OccMap& m = h->omap;
     *out = alore_backend_map_view{m.grid, m.log_odds, h->d_map, m.count_hit, m.count_all, m.nx, m.ny, m.x_lo, m.y_lo, m.res};
+    return ALORE_BE_OK;
+}
+
+void alore_backend_laser_default_params(alore_backend_laser_params* p)
+{
+    laser::Params d;
+    laser::default_params(&d);
+    *p = alore_backend_laser_params{d.sensing_horizon, d.pc_resolution, d.hrz_laser_line_num, d.vtc_laser_line_num, d.vtc_laser_range_dgr,
+                                    d.hrz_limited, d.hrz_laser_range_dgr, d.use_resolution_filter, d.if_perspective};
+}
+
+int alore_backend_laser_create(alore_backend_handle h, const alore_backend_laser_params* params, int max_scans, int max_points_per_scan)
+{
+    if (!h) return ALORE_BE_E_INVALID;
+    alore_backend_laser_params prm;
+    if (params) prm = *params; else alore_backend_laser_default_params(&prm);
+    const laser::Params lp{prm.sensing_horizon, prm.pc_resolution, prm.hrz_laser_line_num, prm.vtc_laser_line_num, prm.vtc_laser_range_dgr,
+                           prm.hrz_limited, prm.hrz_laser_range_dgr, prm.use_resolution_filter, prm.if_perspective};
+    if (!laser::valid(lp))
+        return fail(h, ALORE_BE_E_INVALID, "laser_create: needs vtc_laser_line_num >= 2, hrz_laser_line_num >= 1, at most 8192 bins, a positive horizon and resolution, vtc_laser_range_dgr in (0, 180)");
+    if (max_scans < 1 || (lp.if_perspective && max_points_per_scan < 1))
+        return fail(h, ALORE_BE_E_INVALID, "laser_create: max_scans and, in perspective mode, max_points_per_scan must be at least 1");
+    BE_TRY(h, hipSetDevice(h->device));
+    end_laser(h);
+    const laser::Derived d = laser::derive(lp);
+    const size_t S = (size_t)max_scans, bins = (size_t)d.hrz * d.vtc, slots = d.perspective ? (size_t)max_points_per_scan : bins;
+    std::vector<double> tables((size_t)laser::table_doubles(d));
+    laser::make_tables(d, tables.data());
+    hipError_t e = hipSuccess;
+    auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    h->has_laser = true; // end_laser frees what was allocated
+    A(hipMalloc((void**)&h->l_tables, sizeof(double) * tables.size()));
+    A(hipMalloc((void**)&h->l_laser, sizeof(float) * S * slots * 3));
+    A(hipMalloc((void**)&h->l_world, sizeof(float) * S * slots * 3));
+    A(hipMalloc((void**)&h->l_index, sizeof(int) * S * slots));
+    if (!d.perspective) {
+        A(hipMalloc((void**)&h->l_image, sizeof(double) * S * bins));
+        A(hipMalloc((void**)&h->l_compact, sizeof(float) * S * slots * 3));
+    }
+    A(dalloc(&h->l_n, S)); A(dalloc(&h->l_status, S));
+    A(hipMalloc((void**)&h->d_laser_in, laser_in_bytes(S)));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_laser, laser_in_bytes(S), hipHostMallocDefault);
+    if (e == hipSuccess && !h->ev_laser) e = hipEventCreateWithFlags(&h->ev_laser, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMemcpy(h->l_tables, tables.data(), sizeof(double) * tables.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = backend::laser_configure();
+    if (e != hipSuccess) {
+        end_laser(h);
+        return fail(h, e == hipErrorOutOfMemory ? ALORE_BE_E_NOMEM : ALORE_BE_E_HIP, "laser_create", e);
+    }
+    h->laser_d = d;
+    h->laser_scans = max_scans; h->laser_slots = (int)slots; h->laser_bins = (int)bins;
+    return ALORE_BE_OK;
+}
+
+int alore_backend_laser_set_cloud(alore_backend_handle h, const float* points, int n, int stride_bytes, int device_points, void* stream)
+{
+    if (!h) return ALORE_BE_E_INVALID;
+    if (!h->has_laser) return fail(h, ALORE_BE_E_INVALID, "laser_set_cloud: no sensor (alore_backend_laser_create)");
+    if (n < 0 || n > (1 << 30) || (n > 0 && !points) || stride_bytes < 12 || stride_bytes % 4)
+        return fail(h, ALORE_BE_E_INVALID, "laser_set_cloud: needs 0 <= n <= 2^30, points, and a stride that is a multiple of 4 and at least 12");
+    BE_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if ((size_t)n > h->cloud_cap || !h->d_cloud) {
+        BE_TRY(h, hipDeviceSynchronize()); // a scan on another stream may still read the old cloud
+        if (h->d_cloud) { (void)hipFree(h->d_cloud); h->d_cloud = nullptr; h->cloud_cap = 0; }
+        h->has_cloud = false;
+        BE_TRY(h, hipMalloc((void**)&h->d_cloud, sizeof(float) * 3 * (size_t)(n ? n : 1)));
+        h->cloud_cap = (size_t)(n ? n : 1);
+    }
+    if (n > 0 && device_points) {
+        BE_TRY(h, hipMemcpy2DAsync(h->d_cloud, 12, points, (size_t)stride_bytes, 12, (size_t)n, hipMemcpyDeviceToDevice, s));
+    } else if (n > 0) {
+        std::vector<float> packed(3 * (size_t)n);
+        for (size_t i = 0; i < (size_t)n; ++i) std::memcpy(&packed[3 * i], (const char*)points + i * (size_t)stride_bytes, 12);
+        BE_TRY(h, hipMemcpyAsync(h->d_cloud, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice, s));
+        BE_TRY(h, hipStreamSynchronize(s));
+    }
+    h->n_cloud = n;
+    h->has_cloud = true;
+    return ALORE_BE_OK;
+}
+
+int alore_backend_laser_scan(alore_backend_handle h, int count, const double* poses, int pose_stride_bytes, int device_poses, void* stream)
+{
+    if (!h) return ALORE_BE_E_INVALID;
+    if (!h->has_laser) return fail(h, ALORE_BE_E_INVALID, "laser_scan: no sensor (alore_backend_laser_create)");
+    if (!h->has_cloud) return fail(h, ALORE_BE_E_INVALID, "laser_scan: no world cloud (alore_backend_laser_set_cloud)");
+    if (count < 1 || count > h->laser_scans || !poses) return fail(h, ALORE_BE_E_INVALID, "laser_scan: count must be 1 .. max_scans, poses not NULL");
+    const int three = 3 * (int)sizeof(double);
+    if (pose_stride_bytes < three || pose_stride_bytes % (int)sizeof(double))
+        return fail(h, ALORE_BE_E_INVALID, "laser_scan: the pose stride must be a multiple of 8, at least 24");
+    BE_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (h->laser_pending) BE_TRY(h, hipEventSynchronize(h->ev_laser)); // the pinned block is free again
+    h->laser_pending = false;
+    const size_t n = count;
+    backend::LaserArgs g{};
+    g.count = count; g.n_cloud = h->n_cloud; g.slots = h->laser_slots;
+    g.d = h->laser_d;
+    g.cloud = h->d_cloud;
+    g.tables = h->l_tables;
+    size_t up = LASER_ARGS_BYTES;
+    if (device_poses) {
+        g.poses = poses; g.pose_stride = pose_stride_bytes;
+    } else {
+        double* hp = (double*)(h->h_laser + LASER_ARGS_BYTES);
+        for (size_t i = 0; i < n; ++i) std::memcpy(hp + 3 * i, (const char*)poses + i * (size_t)pose_stride_bytes, three);
+        g.poses = (const double*)(h->d_laser_in + LASER_ARGS_BYTES); g.pose_stride = three;
+        up = laser_in_bytes(n);
+    }
+    g.image = h->l_image; g.laser_pts = h->l_laser; g.world_pts = h->l_world; g.index = h->l_index; g.compact = h->l_compact;
+    g.n_points = h->l_n; g.status = h->l_status;
+    std::memcpy(h->h_laser, &g, sizeof(g));
+    BE_TRY(h, hipMemcpyAsync(h->d_laser_in, h->h_laser, up, hipMemcpyHostToDevice, s));
+    BE_TRY(h, hipEventRecord(h->ev_laser, s));
+    h->laser_pending = true;
+    BE_TRY(h, backend::laser_scan((const backend::LaserArgs*)h->d_laser_in, count, h->laser_d.perspective, h->laser_bins, s));
+    if (!device_poses) BE_TRY(h, hipStreamSynchronize(s));
+    return ALORE_BE_OK;
+}
+
+int alore_backend_device_laser(alore_backend_handle h, alore_backend_laser_view* out)
+{
+    if (!h || !out) return fail(h, ALORE_BE_E_INVALID, "device_laser: bad argument");
+    if (!h->has_laser) return fail(h, ALORE_BE_E_INVALID, "device_laser: no sensor (alore_backend_laser_create)");
+    *out = alore_backend_laser_view{h->l_image, h->l_laser, h->l_world, h->l_index, h->laser_d.perspective ? h->l_laser : h->l_compact,
+                                    h->l_n, h->l_status, h->laser_slots, h->laser_bins, h->laser_scans};
+    return ALORE_BE_OK;
+}
+
+int alore_backend_get_laser(alore_backend_handle h, int count, double* range_image, float* laser_points, float* world_points, int* index,
+                            float* compact_points, int* n_points, int* status)
+{
+    if (!h) return ALORE_BE_E_INVALID;
+    if (!h->has_laser) return fail(h, ALORE_BE_E_INVALID, "get_laser: no sensor (alore_backend_laser_create)");
+    if (count < 1 || count > h->laser_scans) return fail(h, ALORE_BE_E_INVALID, "get_laser: count must be 1 .. max_scans");
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, hipDeviceSynchronize());
+    const size_t n = count, pts = n * (size_t)h->laser_slots;
+    if (range_image && h->l_image) BE_TRY(h, hipMemcpy(range_image, h->l_image, sizeof(double) * n * (size_t)h->laser_bins, hipMemcpyDeviceToHost));
+    if (laser_points) BE_TRY(h, hipMemcpy(laser_points, h->l_laser, sizeof(float) * pts * 3, hipMemcpyDeviceToHost));
+    if (world_points) BE_TRY(h, hipMemcpy(world_points, h->l_world, sizeof(float) * pts * 3, hipMemcpyDeviceToHost));
+    if (index) BE_TRY(h, hipMemcpy(index, h->l_index, sizeof(int) * pts, hipMemcpyDeviceToHost));
+    if (compact_points)
+        BE_TRY(h, hipMemcpy(compact_points, h->laser_d.perspective ? h->l_laser : h->l_compact, sizeof(float) * pts * 3, hipMemcpyDeviceToHost));
+    if (n_points) BE_TRY(h, hipMemcpy(n_points, h->l_n, sizeof(int) * n, hipMemcpyDeviceToHost));
+    if (status) BE_TRY(h, hipMemcpy(status, h->l_status, sizeof(int) * n, hipMemcpyDeviceToHost));
     return ALORE_BE_OK;
 }
 

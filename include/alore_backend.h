@@ -269,7 +269,8 @@ int alore_backend_plan_masked(alore_backend_handle h, int count, const int *mask
  * [nx][ny], cell (ix, iy) at ix * ny + iy, x_hi = x_lo + nx * res.  csrc/occupancy_update.h holds the arithmetic and lists the
  * deviations from the reference (int counts, non-finite points skipped, a sensor outside the map refused, no access outside the
  * map at its edge).  Out of scope: cirSupRaycastProcess (off in both launch files), TF lookups and PCL conversion (the caller hands
- * over points in the world frame), the laser simulator.  The front end's search on this map is alore_backend_search_paths below. */
+ * over points in the world frame).  The laser simulator that makes the clouds is the alore_backend_laser_* section below, the front
+ * end's search on this map alore_backend_search_paths after it. */
 typedef struct alore_backend_map_params {
     double p_hit, p_miss, p_min, p_max, p_occ; /* probabilities in (0, 1); their logits are the log-odds of the update */
     double detection_range;
@@ -329,6 +330,82 @@ typedef struct alore_backend_map_view {
     double x_lo, y_lo, res;
 } alore_backend_map_view;
 int alore_backend_map_device(alore_backend_handle h, alore_backend_map_view *out);
+
+/* ---- laser scans of a resident world cloud, on the device ----------------------------------------------------- */
+/* What produces the clouds that alore_backend_map_integrate reads: the reference's laser simulator
+ * (utils/laser_simulator/src/laser_sim_node.cpp) holds the world as a point cloud and publishes, at every sensing tick, what a robot
+ * at the current pose sees -- renderSensedPoints (:423-533), a range image over hrz x vtc laser lines with occlusion and the optional
+ * resolution filter, or perspectivePoints (:343-421, what planner_sim.launch runs), every world point within the horizon.  Here the
+ * world cloud stays on the device and one call renders the scans of a batch of poses, one workgroup per scan (csrc/laser_scan.hip).
+ * The contract -- the order of every operation, the per-line sine and cosine tables computed once on the host, the deviations from
+ * the reference (in range on the double sum; non-finite points and, in range mode, a point at the sensor skipped; the filter's
+ * spread clamped in double and to one turn of the ring) -- is stated in csrc/laser_scan.h.  The fields are the node's parameters
+ * (:540-581).  The voxel filter of rcvGlobalPointCloudCallBack is the caller's, as PCL conversion is elsewhere. */
+typedef struct alore_backend_laser_params {
+    double sensing_horizon, pc_resolution;
+    int hrz_laser_line_num, vtc_laser_line_num;
+    double vtc_laser_range_dgr;
+    int hrz_limited;
+    double hrz_laser_range_dgr;
+    int use_resolution_filter;
+    int if_perspective; /* 0 renderSensedPoints, 1 perspectivePoints */
+} alore_backend_laser_params;
+/* 27.0, 0.1, 360, 16, 30.0, 0, 90.0, 0, 1 (planner_sim.launch, config/perspective_laser.yaml); config/normal_laser.yaml, the
+ * occluding sensor, has horizon 10.0, 360 x 2 lines over 10 degrees and the filter on */
+void alore_backend_laser_default_params(alore_backend_laser_params *p);
+
+#define ALORE_BE_LASER_MAX_BINS 8192
+/* status of a scan */
+#define ALORE_BE_LASER_OK 0
+#define ALORE_BE_LASER_E_POSE (-1)     /* x, y or yaw is not finite: count 0, an empty image, NaN slots */
+#define ALORE_BE_LASER_E_CAPACITY (-2) /* perspective mode: more points within the horizon than slots; n_points is the true count */
+
+/* Allocates, once: the slabs of max_scans scans, the line tables and a pinned argument block.  A scan has hrz x vtc slots in range
+ * mode and max_points_per_scan slots in perspective mode (where max_points_per_scan must be at least 1; range mode ignores it).
+ * params NULL: the defaults.  ALORE_BE_E_INVALID before anything is allocated for vtc_laser_line_num < 2 (the reference divides by
+ * zero), hrz_laser_line_num < 1, more than ALORE_BE_LASER_MAX_BINS bins, a horizon or resolution that is not positive and finite,
+ * vtc_laser_range_dgr outside (0, 180), or hrz_limited with a horizontal range that is not positive.  Replaces a sensor created
+ * before, cloud included. */
+int alore_backend_laser_create(alore_backend_handle h, const alore_backend_laser_params *params, int max_scans, int max_points_per_scan);
+/* The world cloud: x, y, z of point i are the three floats at (char *)points + i * stride_bytes (a multiple of 4, at least 12: 12
+ * for triples, 16 for a PCL PointXYZ array).  n == 0 is legal (points may be NULL then); at most 2^30 points (the kernels index
+ * them with an int).  device_points == 0: HOST memory, packed,
+ * uploaded, and the stream is synchronised.  device_points != 0: DEVICE memory, copied in stream order; the device buffer grows
+ * (with a device synchronisation) only when n exceeds every cloud set before. */
+int alore_backend_laser_set_cloud(alore_backend_handle h, const float *points, int n, int stride_bytes, int device_points, void *stream);
+/* Renders scans 0..count-1 (count <= max_scans): x, y, yaw of scan i are the three doubles at (char *)poses + i *
+ * pose_stride_bytes (a multiple of 8, at least 24), so the d_xytheta [count][3] of alore_backend_predicted_state_device serves as
+ * the poses as it lies.  Every scan gets a status (above) and a count; a scan that fails leaves the others as they are.
+ * device_poses != 0: DEVICE memory read in stream order; nothing is allocated, nothing crosses the bus but the argument block and
+ * nothing waits (a second call waits for the first one's block to have left the host).  device_poses == 0: HOST memory; the poses
+ * go up with the argument block and the stream is synchronised before the call returns.  The return value speaks of the call,
+ * not of the scans: read their status.  Without alore_backend_laser_create or alore_backend_laser_set_cloud: ALORE_BE_E_INVALID.
+ * The argument block on the device and the slabs are the handle's: successive calls must be ordered on the device (one stream, or
+ * events), as for alore_backend_search_paths. */
+int alore_backend_laser_scan(alore_backend_handle h, int count, const double *poses, int pose_stride_bytes, int device_poses, void *stream);
+/* The device slabs, scan i at row i; valid until the next alore_backend_laser_create or the end of the handle.
+ * Range mode: range_image [max_scans][bins] (bins = hrz x vtc, bin (x, y) at x * vtc + y, 9999.0 where nothing was hit);
+ * laser_points and world_points [max_scans][slots][3], slot = bin, three NaN where the bin was not hit; n_points the number of hit
+ * bins; index [max_scans][slots] the hit bins in x-major order (the reference's message), -1 from n_points on; compact_points
+ * [max_scans][slots][3] their laser-frame points in that order, NaN from n_points on.
+ * Perspective mode: laser_points (rot^T (p - t)) and world_points (the source point) [max_scans][slots][3] and index (the source
+ * index) for the n_points points within the horizon in no particular order, NaN and -1 beyond; range_image is NULL and
+ * compact_points is laser_points.
+ * Scan i goes into alore_backend_map_integrate(device_points = 1) as alore_backend_scan{points = world_points + i * slots * 3,
+ * n_points = slots, point_stride_bytes = 12}: non-finite points are skipped there. */
+typedef struct alore_backend_laser_view {
+    double *range_image;
+    float *laser_points, *world_points;
+    int *index;
+    float *compact_points;
+    int *n_points, *status;
+    int slots, bins, max_scans;
+} alore_backend_laser_view;
+int alore_backend_device_laser(alore_backend_handle h, alore_backend_laser_view *out);
+/* The slabs of scans 0..count-1 copied to HOST arrays of the shapes above with count for max_scans (any pointer may be NULL;
+ * range_image is not written in perspective mode).  Waits for the device. */
+int alore_backend_get_laser(alore_backend_handle h, int count, double *range_image, float *laser_points, float *world_points, int *index,
+                            float *compact_points, int *n_points, int *status);
 
 /* ---- way-point paths by grid search on the handle's map, on the device ---------------------------------------- */
 /* What produces the paths that alore_backend_set_paths reads: per problem a shortest 8-connected path from a start to a goal over
