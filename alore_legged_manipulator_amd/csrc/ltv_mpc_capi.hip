@@ -4,6 +4,7 @@
 // what they are (ltv_mpc.hip, the solver kernels, is built without them -- see ltv_mpc.h).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -13,19 +14,17 @@
 #include <vector>
 
 #include "ltv_mpc.h"
+#include "ltv_plant.h"
 #include "minco_spline.h"
 #include "nmpc_kernels.h"
 
 namespace ltv {
 
-// getRefPoints of the `mpc` node on the trajectory store: thread = (robot, i), then smooth_yaw per robot
-__global__ void ltv_refs_kernel(nmpc::RefStore s, int B, int T, double dt, double now, double* xref, double* dref, int* at_goal)
+// node i of robot r, getRefPoints of the `mpc` node on the trajectory store (m: the robot's meta record, valid): the reference
+// pose with the heading normalised to (-pi, pi], the reference inputs, and getRefPoints' at-goal test
+struct RefNode { double X, Y, psi, v, w; };
+__device__ __forceinline__ void ltv_ref_node(const nmpc::RefStore& s, const double* m, int r, int i, double dt, double now, RefNode& o, int& goal)
 {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)B * T) return;
-    const int r = (int)(t / T), i = (int)(t % T);
-    const double* m = s.meta + (size_t)r * 8;
-    if (m[6] == 0.0) { if (i == 0 && at_goal) at_goal[r] = 0; return; }
     const double duration = m[1], xv = m[2], res = m[3];
     const int np = (int)m[4], nc = (int)m[5];
     const double* dur = s.dur + (size_t)r * s.P;
@@ -49,18 +48,43 @@ __global__ void ltv_refs_kernel(nmpc::RefStore s, int B, int T, double dt, doubl
     const double* ck = s.ckpt + ((size_t)r * s.C + index) * 2;
     double xd1, yd1, xd2, yd2, xd3, yd3; // one sincos per Simpson node
     minco::xydot(p1, v1, xv, xd1, yd1); minco::xydot(p2, v2, xv, xd2, yd2); minco::xydot(p3, v3, xv, xd3, yd3);
-    const double X = ck[0] + diff_t / 6.0 * (xd1 + 4.0 * xd2 + xd3);
-    const double Y = ck[1] + diff_t / 6.0 * (yd1 + 4.0 * yd2 + yd3);
+    o.X = ck[0] + diff_t / 6.0 * (xd1 + 4.0 * xd2 + xd3);
+    o.Y = ck[1] + diff_t / 6.0 * (yd1 + 4.0 * yd2 + yd3);
     double psi = p3[0];
     if (std::isfinite(psi)) { // a non-finite sample is handed on as it is: get_cmd flags the robot (status 2)
         while (psi > M_PI) psi -= 2 * M_PI;
         while (psi < -M_PI) psi += 2 * M_PI;
     }
+    o.psi = psi;
+    o.v = v3[1];
+    o.w = v3[0];
+    goal = (t_cur > duration + 1.0) ? 1 : 0;
+}
+// one step of smooth_yaw: `cur` moved by whole turns until it is within a quarter turn of `prev` (pre_tick_kernel; the loops of
+// ltv_unwrap_kernel below, which keeps its own text so that its code object stays what it was)
+__device__ __forceinline__ void ltv_unwrap_step(double& cur, double prev)
+{
+    double dy = cur - prev;
+    while (dy >= M_PI / 2) { cur -= 2 * M_PI; dy = cur - prev; }
+    while (dy <= -M_PI / 2) { cur += 2 * M_PI; dy = cur - prev; }
+}
+
+// getRefPoints of the `mpc` node on the trajectory store: thread = (robot, i), then smooth_yaw per robot
+__global__ void ltv_refs_kernel(nmpc::RefStore s, int B, int T, double dt, double now, double* xref, double* dref, int* at_goal)
+{
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long)B * T) return;
+    const int r = (int)(t / T), i = (int)(t % T);
+    const double* m = s.meta + (size_t)r * 8;
+    if (m[6] == 0.0) { if (i == 0 && at_goal) at_goal[r] = 0; return; }
+    RefNode n;
+    int goal;
+    ltv_ref_node(s, m, r, i, dt, now, n, goal);
     double* xo = xref + ((size_t)r * T + i) * 3;
-    xo[0] = X; xo[1] = Y; xo[2] = psi;
-    dref[((size_t)r * T + i) * 2] = v3[1];
-    dref[((size_t)r * T + i) * 2 + 1] = v3[0];
-    if (i == 0 && at_goal) at_goal[r] = (t_cur > duration + 1.0) ? 1 : 0;
+    xo[0] = n.X; xo[1] = n.Y; xo[2] = n.psi;
+    dref[((size_t)r * T + i) * 2] = n.v;
+    dref[((size_t)r * T + i) * 2 + 1] = n.w;
+    if (i == 0 && at_goal) at_goal[r] = goal;
 }
 __global__ void ltv_unwrap_kernel(nmpc::RefStore s, int B, int T, const double* est, double* xref)
 {
@@ -86,6 +110,104 @@ __global__ void ltv_unwrap_kernel(nmpc::RefStore s, int B, int T, const double* 
     }
 }
 
+// ---- the closed loop on the device (alore_ltv_closed_loop_run and its pieces)
+struct PreTick {
+    nmpc::RefStore s;       // pre_tick_kernel only
+    alore_ltv_plant_params p;
+    const double* meta;     // RefStore::meta of the last sampling, or null: every robot counts as having a trajectory
+    int B, T;
+    double dt, now;
+    double *xref, *dref;    // [B][T][3], [B][T][2]
+    int* goal;              // [B] at-goal flags: in, of the sampling the last solve used; out (pre_tick_kernel), of this tick's
+    double* pose;           // the plant, one slab: pose [stride][3], then vw [stride][2], then desired [stride][2]
+    int stride;             // robots the slabs are laid out for (max_robots)
+    const double* cmd;      // [B][2] of the last solve
+    const int* status;      // [B]
+    double* tr_pose;        // the trace record of the plant step, or null: pose [stride][3], then cmd [stride][2]
+    int* tr_status;         // status [stride], then at_goal [stride]
+    int do_plant;           // pre_tick_kernel: 0 on the first tick of a run
+};
+
+// the plant step of robot r (ltv_plant.h) and its trace record; every calling lane computes, `writer` lanes store.  Returns the pose.
+__device__ __forceinline__ void plant_robot(const PreTick& a, int r, bool has, int goal, bool writer, double& th_out)
+{
+    double* const vwp = a.pose + (size_t)a.stride * 3;
+    double* const desp = a.pose + (size_t)a.stride * 5;
+    ltv_plant::State st;
+    st.x = a.pose[(size_t)r * 3]; st.y = a.pose[(size_t)r * 3 + 1]; st.th = a.pose[(size_t)r * 3 + 2];
+    st.v = vwp[(size_t)r * 2]; st.w = vwp[(size_t)r * 2 + 1];
+    st.dv = desp[(size_t)r * 2]; st.dw = desp[(size_t)r * 2 + 1];
+    const double cv = a.cmd[(size_t)r * 2], cw = a.cmd[(size_t)r * 2 + 1];
+    const int status = a.status[r];
+    ltv_plant::step(a.p, has, goal != 0, cv, cw, st);
+    th_out = st.th;
+    if (!writer) return;
+    a.pose[(size_t)r * 3] = st.x; a.pose[(size_t)r * 3 + 1] = st.y; a.pose[(size_t)r * 3 + 2] = st.th;
+    vwp[(size_t)r * 2] = st.v; vwp[(size_t)r * 2 + 1] = st.w;
+    desp[(size_t)r * 2] = st.dv; desp[(size_t)r * 2 + 1] = st.dw;
+    if (a.tr_pose) {
+        a.tr_pose[(size_t)r * 3] = st.x; a.tr_pose[(size_t)r * 3 + 1] = st.y; a.tr_pose[(size_t)r * 3 + 2] = st.th;
+        double* const tc = a.tr_pose + (size_t)a.stride * 3;
+        tc[(size_t)r * 2] = (has && goal) ? 0.0 : cv; tc[(size_t)r * 2 + 1] = (has && goal) ? 0.0 : cw;
+        a.tr_status[r] = status; a.tr_status[(size_t)a.stride + r] = goal;
+    }
+}
+
+// alore_ltv_plant_step: thread = robot
+__global__ void plant_step_kernel(PreTick a)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.B) return;
+    const bool has = a.meta ? a.meta[(size_t)r * 8 + 6] != 0.0 : true;
+    double th;
+    plant_robot(a, r, has, a.goal[r], true, th);
+}
+
+// One launch in front of the solve of tick t: the plant step and trace record of tick t - 1, getRefPoints of tick t and smooth_yaw
+// against the pose that plant step has just produced.  Wavefront = robot, lane i = node i (T <= 64).  The plant's dependent
+// substeps run on every lane alike (uniform, no broadcast needed) while the sampling loads of the lane are in flight; the heading
+// walk hands the unwrapped value from lane to lane by a wavefront shift, as nmpc::ref_sample_smooth_body does, instead of T
+// dependent round trips through memory.  The arithmetic is that of plant_step_kernel, ltv_refs_kernel and ltv_unwrap_kernel
+// (the same device functions): the same bits.
+__global__ __launch_bounds__(64) void pre_tick_kernel(PreTick a)
+{
+    const int r = blockIdx.x, i = threadIdx.x;
+    const double* m = a.s.meta + (size_t)r * 8;
+    const bool has = m[6] != 0.0;
+    double th;
+    if (a.do_plant) {
+        // the flag of tick t - 1: read and (below) overwritten by lane 0, handed to the others in registers
+        const int gp = __shfl((i == 0) ? a.goal[r] : 0, 0);
+        plant_robot(a, r, has, gp, i == 0, th);
+    } else {
+        th = a.pose[(size_t)r * 3 + 2];
+    }
+    if (!has) { if (i == 0) a.goal[r] = 0; return; }
+    const bool in = i < a.T;
+    RefNode n{0.0, 0.0, 0.0, 0.0, 0.0};
+    int goal = 0;
+    if (in) ltv_ref_node(a.s, m, r, i, a.dt, a.now, n, goal);
+    // smooth_yaw: node 0 against the pose, node k against the unwrapped node k - 1; the walk stops at the first heading that is
+    // not finite (ltv_unwrap_kernel returns there) -- a stopped lane hands on NaN, which stops every lane after it
+    double cur = n.psi, prev = th;
+    for (int k = 0; k < a.T; ++k) { // wavefront-uniform
+        double pass = cur;
+        if (i == k) {
+            if (std::isfinite(prev) && std::isfinite(cur)) { ltv_unwrap_step(cur, prev); pass = cur; }
+            else pass = __builtin_nan("");
+        }
+        const int clo = __builtin_amdgcn_update_dpp(0, __double2loint(pass), 0x138, 0xF, 0xF, false); // wave_shr:1
+        const int chi = __builtin_amdgcn_update_dpp(0, __double2hiint(pass), 0x138, 0xF, 0xF, false);
+        if (i == k + 1) prev = __hiloint2double(chi, clo);
+    }
+    if (!in) return;
+    double* xo = a.xref + ((size_t)r * a.T + i) * 3;
+    xo[0] = n.X; xo[1] = n.Y; xo[2] = cur;
+    a.dref[((size_t)r * a.T + i) * 2] = n.v;
+    a.dref[((size_t)r * a.T + i) * 2 + 1] = n.w;
+    if (i == 0) a.goal[r] = goal;
+}
+
 } // namespace ltv
 
 // internal accessor of the NMPC handle's trajectory store (nmpc_capi.hip)
@@ -102,6 +224,16 @@ struct alore_ltv_solver {
     long long* d_stamps = nullptr;
     char* h_stage = nullptr; // pinned
     size_t stage_bytes = 0;
+    // the plant of the closed loop (alore_ltv_plant_init)
+    bool plant_ready = false;
+    alore_ltv_plant_params plant{};
+    double* d_pose = nullptr; // one slab: pose [B][3], then vw [B][2] (d_vw), then desired [B][2] (d_des)
+    double *d_vw = nullptr, *d_des = nullptr;
+    const double* plant_meta = nullptr; // RefStore::meta of the last device sampling
+    int trace_cap = 0;                  // ticks the ring holds
+    long long trace_total = 0;          // plant steps recorded since the trace was emptied
+    double* d_tr_pose = nullptr;        // per tick of the ring: pose [B][3], then cmd [B][2]
+    int* d_tr_status = nullptr;         // per tick of the ring: status [B], then at_goal [B]
 };
 
 namespace {
@@ -122,8 +254,17 @@ hipError_t zalloc(T** p, size_t n)
     if (e == hipSuccess) e = hipMemset(*p, 0, sizeof(T) * (n ? n : 1));
     return e;
 }
+void plant_free(alore_ltv_handle h)
+{
+    void* ptrs[] = {h->d_pose, h->d_tr_pose, h->d_tr_status};
+    for (void* p : ptrs) if (p) (void)hipFree(p);
+    h->d_pose = h->d_vw = h->d_des = h->d_tr_pose = nullptr;
+    h->d_tr_status = nullptr;
+    h->plant_ready = false; h->trace_cap = 0; h->trace_total = 0; h->plant_meta = nullptr;
+}
 void lfree(alore_ltv_handle h)
 {
+    plant_free(h);
     void* ptrs[] = {h->d_now, h->d_xref, h->d_dref, h->d_out, h->d_buff, h->d_xopt, h->d_ws, h->d_est, h->d_st, h->d_sweeps, h->d_status, h->d_goal, h->d_cmd, h->d_relin, h->d_du};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
@@ -414,6 +555,257 @@ int alore_ltv_set_state(alore_ltv_handle h, int B, const double* output, const d
     const size_t T = h->cfg.predict_steps, dl = h->cfg.delay_num;
     if (output) LTV_TRY(h, hipMemcpyAsync(h->d_out, output, sizeof(double) * B * T * 2, hipMemcpyHostToDevice, s));
     if (buff && dl > 0) LTV_TRY(h, hipMemcpyAsync(h->d_buff, buff, sizeof(double) * B * dl * 2, hipMemcpyHostToDevice, s));
+    LTV_TRY(h, hipStreamSynchronize(s));
+    return ALORE_LTV_OK;
+}
+
+// ---- the closed loop on the device
+
+void alore_ltv_plant_default_params(alore_ltv_plant_params* p)
+{
+    std::memset(p, 0, sizeof(*p));
+    p->max_acc = 2.0; p->max_domega = 4.0; p->pose_pub_period = 0.01; p->state_propa_period = 0.002;
+    p->substeps = 5; p->follow = 0;
+}
+
+int alore_ltv_plant_init(alore_ltv_handle h, const alore_ltv_plant_params* p, int max_trace_ticks)
+{
+    if (!h) return ALORE_LTV_E_INVALID;
+    if (!p || max_trace_ticks < 0) return lfail(h, ALORE_LTV_E_INVALID, "plant_init: bad argument");
+    if (!ltv_plant::valid(*p)) return lfail(h, ALORE_LTV_E_INVALID, "plant_init: the plant parameters must be finite and positive, substeps at least 1");
+    LTV_TRY(h, hipSetDevice(h->device));
+    LTV_TRY(h, hipDeviceSynchronize()); // a run still in flight reads what is freed below
+    plant_free(h);
+    const size_t B = h->B, M = max_trace_ticks;
+    hipError_t e = hipSuccess;
+    auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    A(zalloc(&h->d_pose, B * 7));
+    if (M > 0) { A(zalloc(&h->d_tr_pose, M * B * 5)); A(zalloc(&h->d_tr_status, M * B * 2)); }
+    if (e == hipSuccess) { h->d_vw = h->d_pose + B * 3; h->d_des = h->d_pose + B * 5; }
+    if (e != hipSuccess) { plant_free(h); return lfail(h, e == hipErrorOutOfMemory ? ALORE_LTV_E_NOMEM : ALORE_LTV_E_HIP, "plant_init: allocation", e); }
+    h->plant = *p;
+    h->plant.follow = p->follow ? 1 : 0;
+    h->trace_cap = max_trace_ticks;
+    h->plant_ready = true;
+    return ALORE_LTV_OK;
+}
+
+// the checks every device call starts with; null: fine
+static const char* plant_args_bad(alore_ltv_handle h, int B)
+{
+    if (!h->plant_ready) return "alore_ltv_plant_init has not been called";
+    if (B < 1 || B > h->B) return "B out of range";
+    return nullptr;
+}
+static const char* store_bad(alore_ltv_handle h, void* nmpc, int B, nmpc::RefStore* rs)
+{
+    int cap = 0, dev = -1;
+    if (!nmpc || alore_nmpc_internal_refstore(nmpc, rs, &cap, &dev) != 0 || cap < B || dev != h->device)
+        return "the NMPC handle has no trajectory store for B robots on this device";
+    return nullptr;
+}
+// n_relin / du_th of the device solve (du_th < 0: the fixed count)
+static const char* solve_args_bad(int n_relin, double du_th)
+{
+    if (n_relin < 1) return "n_relin must be at least 1";
+    if (std::isnan(du_th)) return "du_th is NaN";
+    return nullptr;
+}
+#define LTV_ARGS(h, who, expr)                                                                          \
+    do {                                                                                                \
+        if (const char* why_ = (expr)) return lfail(h, ALORE_LTV_E_INVALID, (std::string(who ": ") + why_).c_str()); \
+    } while (0)
+
+int alore_ltv_plant_set_state(alore_ltv_handle h, int B, const double* pose, const double* vw, const double* desired, void* stream)
+{
+    if (!h) return ALORE_LTV_E_INVALID;
+    LTV_ARGS(h, "plant_set_state", plant_args_bad(h, B));
+    if (!pose) return lfail(h, ALORE_LTV_E_INVALID, "plant_set_state: pose is null");
+    LTV_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    double* sp = (double*)h->h_stage;
+    double* sv = sp + (size_t)B * 3;
+    double* sd = sv + (size_t)B * 2;
+    std::memcpy(sp, pose, sizeof(double) * B * 3);
+    if (vw) std::memcpy(sv, vw, sizeof(double) * B * 2); else std::memset(sv, 0, sizeof(double) * B * 2);
+    if (desired) std::memcpy(sd, desired, sizeof(double) * B * 2); else std::memset(sd, 0, sizeof(double) * B * 2);
+    LTV_TRY(h, hipMemcpyAsync(h->d_pose, sp, sizeof(double) * B * 3, hipMemcpyHostToDevice, s));
+    LTV_TRY(h, hipMemcpyAsync(h->d_vw, sv, sizeof(double) * B * 2, hipMemcpyHostToDevice, s));
+    LTV_TRY(h, hipMemcpyAsync(h->d_des, sd, sizeof(double) * B * 2, hipMemcpyHostToDevice, s));
+    LTV_TRY(h, hipStreamSynchronize(s)); // the slab is reused
+    h->trace_total = 0;
+    return ALORE_LTV_OK;
+}
+
+int alore_ltv_plant_get_state(alore_ltv_handle h, int B, double* pose, double* vw, int* at_goal, void* stream)
+{
+    if (!h) return ALORE_LTV_E_INVALID;
+    LTV_ARGS(h, "plant_get_state", plant_args_bad(h, B));
+    LTV_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    double* sp = (double*)h->h_stage;
+    double* sv = sp + (size_t)B * 3;
+    int* sg = (int*)(sv + (size_t)B * 2);
+    if (pose) LTV_TRY(h, hipMemcpyAsync(sp, h->d_pose, sizeof(double) * B * 3, hipMemcpyDeviceToHost, s));
+    if (vw) LTV_TRY(h, hipMemcpyAsync(sv, h->d_vw, sizeof(double) * B * 2, hipMemcpyDeviceToHost, s));
+    if (at_goal) LTV_TRY(h, hipMemcpyAsync(sg, h->d_goal, sizeof(int) * B, hipMemcpyDeviceToHost, s));
+    LTV_TRY(h, hipStreamSynchronize(s));
+    if (pose) std::memcpy(pose, sp, sizeof(double) * B * 3);
+    if (vw) std::memcpy(vw, sv, sizeof(double) * B * 2);
+    if (at_goal) std::memcpy(at_goal, sg, sizeof(int) * B);
+    return ALORE_LTV_OK;
+}
+
+int alore_ltv_plant_device(alore_ltv_handle h, alore_ltv_plant_view* out)
+{
+    if (!h) return ALORE_LTV_E_INVALID;
+    if (!out) return lfail(h, ALORE_LTV_E_INVALID, "plant_device: bad argument");
+    if (!h->plant_ready) return lfail(h, ALORE_LTV_E_INVALID, "plant_device: alore_ltv_plant_init has not been called");
+    out->pose = h->d_pose; out->vw = h->d_vw; out->cmd = h->d_cmd; out->at_goal = h->d_goal; out->status = h->d_status;
+    return ALORE_LTV_OK;
+}
+
+namespace {
+// what the kernels of a tick take; record: this launch does a plant step, which takes the next slot of the trace ring
+ltv::PreTick tick_args(alore_ltv_handle h, int B, bool record)
+{
+    ltv::PreTick a{};
+    a.p = h->plant; a.meta = h->plant_meta; a.B = B; a.T = h->cfg.predict_steps; a.dt = h->cfg.dt;
+    a.xref = h->d_xref; a.dref = h->d_dref; a.goal = h->d_goal;
+    a.pose = h->d_pose; a.stride = h->B; a.cmd = h->d_cmd; a.status = h->d_status;
+    if (record && h->trace_cap > 0) {
+        const size_t slot = (size_t)(h->trace_total % h->trace_cap) * h->B; // a record is laid out for max_robots robots
+        a.tr_pose = h->d_tr_pose + slot * 5; a.tr_status = h->d_tr_status + slot * 2;
+    }
+    if (record) ++h->trace_total;
+    return a;
+}
+// the enqueue of each piece; the arguments have been checked
+hipError_t enq_refs(alore_ltv_handle h, const nmpc::RefStore& rs, int B, double now, hipStream_t s)
+{
+    const int T = h->cfg.predict_steps;
+    const long total = (long)B * T;
+    hipLaunchKernelGGL(ltv::ltv_refs_kernel, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, s, rs, B, T, h->cfg.dt, now, h->d_xref, h->d_dref,
+                       h->d_goal);
+    hipLaunchKernelGGL(ltv::ltv_unwrap_kernel, dim3((B + 63) / 64), dim3(64), 0, s, rs, B, T, h->d_pose, h->d_xref);
+    h->plant_meta = rs.meta;
+    return hipGetLastError();
+}
+hipError_t enq_pre_tick(alore_ltv_handle h, const nmpc::RefStore& rs, int B, double now, bool do_plant, hipStream_t s)
+{
+    h->plant_meta = rs.meta;
+    ltv::PreTick a = tick_args(h, B, do_plant);
+    a.s = rs; a.now = now; a.do_plant = do_plant ? 1 : 0;
+    hipLaunchKernelGGL(ltv::pre_tick_kernel, dim3(B), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t enq_solve(alore_ltv_handle h, int B, int n_relin, double du_th, int reset, hipStream_t s)
+{
+    ltv::DevConv d{};
+    d.c = h->cfg; d.B = B; d.stride = h->B;
+    d.now = h->d_pose;
+    d.xref = h->d_xref; d.dref = h->d_dref; d.output = h->d_out; d.buff = h->d_buff; d.xopt = h->d_xopt;
+    d.ws = h->d_ws; d.st = h->d_st; d.sweeps = h->d_sweeps; d.status = h->d_status; d.cmd = h->d_cmd;
+    d.n_relin = n_relin; d.reset = reset;
+    d.stamps = h->d_stamps;
+    if (du_th < 0.0) return ltv::launch_get_cmd(d, false, s);
+    d.du_th = std::isinf(du_th) ? 1.7976931348623157e308 : du_th; // "always met": the kernel compares finite numbers only
+    d.relin_iters = h->d_relin; d.du = h->d_du;
+    return ltv::launch_get_cmd_converge(d, s);
+}
+hipError_t enq_plant(alore_ltv_handle h, int B, hipStream_t s)
+{
+    const ltv::PreTick a = tick_args(h, B, true);
+    hipLaunchKernelGGL(ltv::plant_step_kernel, dim3((B + 63) / 64), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+} // namespace
+
+int alore_ltv_refs_from_store_device(alore_ltv_handle h, void* nmpc, int B, double now, void* stream)
+{
+    if (!h) return ALORE_LTV_E_INVALID;
+    nmpc::RefStore rs;
+    LTV_ARGS(h, "refs_from_store_device", plant_args_bad(h, B));
+    if (!std::isfinite(now)) return lfail(h, ALORE_LTV_E_INVALID, "refs_from_store_device: now is not finite");
+    LTV_ARGS(h, "refs_from_store_device", store_bad(h, nmpc, B, &rs));
+    LTV_TRY(h, hipSetDevice(h->device));
+    LTV_TRY(h, enq_refs(h, rs, B, now, (hipStream_t)stream));
+    return ALORE_LTV_OK;
+}
+
+int alore_ltv_get_cmd_device(alore_ltv_handle h, int B, int n_relin, double du_th, int reset, void* stream)
+{
+    if (!h) return ALORE_LTV_E_INVALID;
+    LTV_ARGS(h, "get_cmd_device", plant_args_bad(h, B));
+    LTV_ARGS(h, "get_cmd_device", solve_args_bad(n_relin, du_th));
+    LTV_TRY(h, hipSetDevice(h->device));
+    LTV_TRY(h, enq_solve(h, B, n_relin, du_th, reset ? 1 : 0, (hipStream_t)stream));
+    return ALORE_LTV_OK;
+}
+
+int alore_ltv_plant_step(alore_ltv_handle h, int B, void* stream)
+{
+    if (!h) return ALORE_LTV_E_INVALID;
+    LTV_ARGS(h, "plant_step", plant_args_bad(h, B));
+    LTV_TRY(h, hipSetDevice(h->device));
+    LTV_TRY(h, enq_plant(h, B, (hipStream_t)stream));
+    return ALORE_LTV_OK;
+}
+
+int alore_ltv_closed_loop_run(alore_ltv_handle h, void* nmpc, int B, double t0, double dt_tick, int n_ticks, int n_relin, double du_th, int reset,
+                              void* stream)
+{
+    if (!h) return ALORE_LTV_E_INVALID;
+    nmpc::RefStore rs;
+    LTV_ARGS(h, "closed_loop_run", plant_args_bad(h, B));
+    if (n_ticks < 1) return lfail(h, ALORE_LTV_E_INVALID, "closed_loop_run: n_ticks must be at least 1");
+    if (!std::isfinite(t0) || !std::isfinite(dt_tick)) return lfail(h, ALORE_LTV_E_INVALID, "closed_loop_run: t0 and dt_tick must be finite");
+    LTV_ARGS(h, "closed_loop_run", solve_args_bad(n_relin, du_th));
+    LTV_ARGS(h, "closed_loop_run", store_bad(h, nmpc, B, &rs));
+    LTV_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const char* env = std::getenv("ALORE_LTV_CLOSED_LOOP_SERIAL");
+    const bool serial = env && env[0] == '1';
+    for (int k = 0; k < n_ticks; ++k) {
+        const double now = t0 + k * dt_tick;
+        const int rst = (k == 0 && reset) ? 1 : 0;
+        if (serial) {
+            LTV_TRY(h, enq_refs(h, rs, B, now, s));
+            LTV_TRY(h, enq_solve(h, B, n_relin, du_th, rst, s));
+            LTV_TRY(h, enq_plant(h, B, s));
+        } else {
+            LTV_TRY(h, enq_pre_tick(h, rs, B, now, k > 0, s));
+            LTV_TRY(h, enq_solve(h, B, n_relin, du_th, rst, s));
+        }
+    }
+    if (!serial) LTV_TRY(h, enq_plant(h, B, s));
+    return ALORE_LTV_OK;
+}
+
+int alore_ltv_plant_get_trace(alore_ltv_handle h, int B, int max_ticks, double* pose, double* cmd, int* status, int* at_goal, int* n_ticks_out,
+                              void* stream)
+{
+    if (!h) return ALORE_LTV_E_INVALID;
+    LTV_ARGS(h, "plant_get_trace", plant_args_bad(h, B));
+    if (max_ticks < 0 || !n_ticks_out) return lfail(h, ALORE_LTV_E_INVALID, "plant_get_trace: bad argument");
+    LTV_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    long long n = h->trace_total < h->trace_cap ? h->trace_total : h->trace_cap;
+    if (n > max_ticks) n = max_ticks;
+    *n_ticks_out = (int)n;
+    // rows of the ring are max_robots apart; the oldest returned tick is `first`, and the ring may wrap once inside the range
+    const size_t HB = h->B, cap = h->trace_cap;
+    for (long long done = 0; done < n;) {
+        const size_t slot = (size_t)((h->trace_total - n + done) % (long long)cap);
+        const size_t rows = std::min<size_t>(cap - slot, (size_t)(n - done));
+        const double* td = h->d_tr_pose + slot * HB * 5;
+        const int* ti = h->d_tr_status + slot * HB * 2;
+        if (pose) LTV_TRY(h, hipMemcpy2DAsync(pose + (size_t)done * B * 3, sizeof(double) * B * 3, td, sizeof(double) * HB * 5, sizeof(double) * B * 3, rows, hipMemcpyDeviceToHost, s));
+        if (cmd) LTV_TRY(h, hipMemcpy2DAsync(cmd + (size_t)done * B * 2, sizeof(double) * B * 2, td + HB * 3, sizeof(double) * HB * 5, sizeof(double) * B * 2, rows, hipMemcpyDeviceToHost, s));
+        if (status) LTV_TRY(h, hipMemcpy2DAsync(status + (size_t)done * B, sizeof(int) * B, ti, sizeof(int) * HB * 2, sizeof(int) * B, rows, hipMemcpyDeviceToHost, s));
+        if (at_goal) LTV_TRY(h, hipMemcpy2DAsync(at_goal + (size_t)done * B, sizeof(int) * B, ti + HB, sizeof(int) * HB * 2, sizeof(int) * B, rows, hipMemcpyDeviceToHost, s));
+        done += (long long)rows;
+    }
     LTV_TRY(h, hipStreamSynchronize(s));
     return ALORE_LTV_OK;
 }

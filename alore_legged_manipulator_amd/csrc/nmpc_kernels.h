@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/alore_nmpc.h"
+#include "plant_substeps.h"   // PlantParams, plant_substeps: shared with the plant of the LTV-MPC (ltv_plant.h)
 #include "nmpc_launch_plan.h" // LaunchGeom, block_lds_floats, block_geometry, TP_KMAX: everything of a launch that is decided without a GPU
 
 namespace nmpc {
@@ -143,10 +144,6 @@ struct BackendView {
 };
 hipError_t launch_traj_from_backend(const RefStore& s, const BackendView& v, int count, double t0, double res, int res_int, double xv,
                                     int* n_panels, double* inc, int* overflow, hipStream_t st);
-struct PlantParams { // simulator.h: max_a_, max_domega_, Pose_pub_rate_ (a period), State_Propa_rate_ (a period)
-    double max_a, max_domega, pose_pub_period, propa_period;
-    int substeps; // StatePropaCallback calls per control tick
-};
 // the plant step of tick t with the completion of tick t + 1's references (ref_sampler_device.h: plant_ahead_one)
 struct PlantAhead {
     const float* u;        // [B][N][2] inputs the solve of tick t left

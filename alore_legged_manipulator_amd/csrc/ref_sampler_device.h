@@ -120,38 +120,7 @@ __device__ __forceinline__ void ref_sample_smooth_body(const RefStore& s, const 
     }
 }
 
-// The substeps of one control tick (StatePropaCallback, simulator.h:234-275).  The heading changes once per substep and its sine /
-// cosine after the update are those the next substep starts with: one evaluation per tick, then a rotation by the substep's angle
-// w * period -- a few milliradians, whose sine and cosine are short series (next terms d^9 / 9! and d^8 / 8!: below the last bit
-// for |d| < 0.03); a larger angle takes the full evaluation.  The reference calls cos and sin four times per substep; the rotation
-// differs from them by rounding (1e-16 per substep, nothing carried over to the next tick).
-__device__ __forceinline__ void plant_substeps(const PlantParams& p, double desired_v, double desired_w, double vy, double& x, double& y, double& th,
-                                               double& v, double& w)
-{
-    double sn, cs;
-    sincos(th, &sn, &cs);
-    for (int k = 0; k < p.substeps; ++k) {
-        if (fabs(v - desired_v) >= p.pose_pub_period * p.max_a) v += p.pose_pub_period * p.max_a * (desired_v - v) / fabs(desired_v - v);
-        else v = desired_v;
-        if (fabs(w - desired_w) >= p.pose_pub_period * p.max_domega) w += p.pose_pub_period * p.max_domega * (desired_w - w) / fabs(desired_w - w);
-        else w = desired_w;
-        x += v * p.propa_period * cs;
-        y += v * p.propa_period * sn;
-        const double d = w * p.propa_period;
-        th += d;
-        if (fabs(d) < 0.03) {
-            const double d2 = d * d;
-            const double sd = d * (1.0 - d2 * (1.0 / 6.0) * (1.0 - d2 * (1.0 / 20.0) * (1.0 - d2 * (1.0 / 42.0))));
-            const double cd = 1.0 - d2 * 0.5 * (1.0 - d2 * (1.0 / 12.0) * (1.0 - d2 * (1.0 / 30.0)));
-            const double c1 = cs * cd - sn * sd, s1 = sn * cd + cs * sd;
-            cs = c1; sn = s1;
-        } else {
-            sincos(th, &sn, &cs);
-        }
-        x -= vy * p.propa_period * sn;
-        y += vy * p.propa_period * cs;
-    }
-}
+// plant_substeps (StatePropaCallback, simulator.h:234-275): plant_substeps.h, through nmpc_kernels.h
 
 // The plant step of tick t for robot r and what the sampler of tick t + 1 could not do without the pose it produces: the at-goal
 // flag of tick t (getRefPoints' test, from `now` of tick t), the plant (simulator.h:234-275, see plant_kernel), then x0 <- pose

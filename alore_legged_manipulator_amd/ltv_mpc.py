@@ -18,6 +18,16 @@ class LtvConfig(C.Structure):
                 ("max_omega", C.c_double), ("max_acc", C.c_double), ("max_domega", C.c_double), ("max_sweeps", C.c_int)]
 
 
+class LtvPlantParams(C.Structure):
+    _fields_ = [("max_acc", C.c_double), ("max_domega", C.c_double), ("pose_pub_period", C.c_double), ("state_propa_period", C.c_double),
+                ("substeps", C.c_int), ("follow", C.c_int)]
+
+
+class LtvPlantView(C.Structure):
+    """device pointers (alore_ltv_plant_view): pose [B][3] at a 24-byte stride, vw [B][2], cmd [B][2], at_goal [B], status [B]"""
+    _fields_ = [("pose", C.c_void_p), ("vw", C.c_void_p), ("cmd", C.c_void_p), ("at_goal", C.c_void_p), ("status", C.c_void_p)]
+
+
 def _bind(L):
     if getattr(L, "_ltv_bound", False):
         return
@@ -34,6 +44,18 @@ def _bind(L):
     L.alore_ltv_commands.argtypes = [C.c_void_p, C.c_int, DP, IP, C.c_void_p]
     L.alore_ltv_tick.argtypes = [C.c_void_p, C.c_int, DP, C.c_int, C.c_int, DP, IP, C.c_void_p]
     L.alore_ltv_set_state.argtypes = [C.c_void_p, C.c_int, DP, DP, C.c_void_p]
+    # the closed loop on the device
+    L.alore_ltv_plant_default_params.argtypes = [C.POINTER(LtvPlantParams)]
+    L.alore_ltv_plant_default_params.restype = None
+    L.alore_ltv_plant_init.argtypes = [C.c_void_p, C.POINTER(LtvPlantParams), C.c_int]
+    L.alore_ltv_plant_set_state.argtypes = [C.c_void_p, C.c_int, DP, DP, DP, C.c_void_p]
+    L.alore_ltv_plant_get_state.argtypes = [C.c_void_p, C.c_int, DP, DP, IP, C.c_void_p]
+    L.alore_ltv_plant_device.argtypes = [C.c_void_p, C.POINTER(LtvPlantView)]
+    L.alore_ltv_refs_from_store_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]
+    L.alore_ltv_get_cmd_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p]
+    L.alore_ltv_plant_step.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.alore_ltv_closed_loop_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p]
+    L.alore_ltv_plant_get_trace.argtypes = [C.c_void_p, C.c_int, C.c_int, DP, DP, IP, IP, IP, C.c_void_p]
     L._ltv_bound = True
 
 
@@ -138,6 +160,78 @@ class BatchedLtvMpc:
         self._relin_info(n)
         return {"output": out, "cmd": out[:, self.d].copy(), "xopt": xopt, "sweeps": sw, "status": st,
                 "relin_iters": self.relin_iters, "du": self.du}
+
+    # ---- the closed loop on the device: sampling from the plant's pose, the solve, the simulator's plant (no host in the loop).
+    # Successive calls are ordered on the default stream.  du_th None: n_relin fixed passes; else the converge rule, n_relin its cap.
+    def plant_init(self, max_trace_ticks=0, **params):
+        """the plant of planner_sim.launch behind the `mpc` node; params: fields of alore_ltv_plant_params (follow=1: the plant
+        holds the commanded velocity over the tick); max_trace_ticks: size of the per-tick trace ring"""
+        p = LtvPlantParams()
+        self.L.alore_ltv_plant_default_params(C.byref(p))
+        for k, v in params.items():
+            setattr(p, k, v)
+        self._check(self.L.alore_ltv_plant_init(self.h, C.byref(p), int(max_trace_ticks)))
+        self.plant_params = p
+
+    def plant_set_state(self, pose, vw=None, desired=None):
+        pose = np.ascontiguousarray(pose, np.float64)
+        vw = None if vw is None else np.ascontiguousarray(vw, np.float64)
+        desired = None if desired is None else np.ascontiguousarray(desired, np.float64)
+        self._n = pose.shape[0]
+        self._check(self.L.alore_ltv_plant_set_state(self.h, self._n, _dp(pose), _dp(vw), _dp(desired), None))
+
+    def plant_get_state(self, n=None):
+        """-> pose (n, 3), vw (n, 2), at_goal (n,) bool.  Synchronises."""
+        n = self._n if n is None else n
+        pose = np.zeros((n, 3)); vw = np.zeros((n, 2)); goal = np.zeros(n, np.int32)
+        self._check(self.L.alore_ltv_plant_get_state(self.h, n, _dp(pose), _dp(vw), goal.ctypes.data_as(IP), None))
+        return pose, vw, goal.astype(bool)
+
+    def plant_view(self) -> LtvPlantView:
+        v = LtvPlantView()
+        self._check(self.L.alore_ltv_plant_device(self.h, C.byref(v)))
+        return v
+
+    @staticmethod
+    def _du(du_th):
+        return -1.0 if du_th is None else float(du_th)
+
+    def refs_from_store_device(self, nmpc_engine, now, n=None):
+        n = self._n if n is None else n
+        self._check(self.L.alore_ltv_refs_from_store_device(self.h, nmpc_engine.h, n, float(now), None))
+
+    def get_cmd_device(self, n_relin=5, du_th=None, reset=False, n=None):
+        n = self._n if n is None else n
+        self._check(self.L.alore_ltv_get_cmd_device(self.h, n, int(n_relin), self._du(du_th), 1 if reset else 0, None))
+
+    def plant_step(self, n=None):
+        n = self._n if n is None else n
+        self._check(self.L.alore_ltv_plant_step(self.h, n, None))
+
+    def closed_loop_run(self, nmpc_engine, t0, dt_tick, n_ticks, n_relin=5, du_th=None, reset=False, n=None):
+        """n_ticks control periods at now = t0 + k * dt_tick, enqueued back to back; returns without waiting"""
+        n = self._n if n is None else n
+        self._check(self.L.alore_ltv_closed_loop_run(self.h, nmpc_engine.h, n, float(t0), float(dt_tick), int(n_ticks), int(n_relin),
+                                                     self._du(du_th), 1 if reset else 0, None))
+
+    def plant_trace(self, max_ticks, n=None):
+        """the most recent plant steps, oldest first -> dict pose (k, n, 3), cmd (k, n, 2), status (k, n), at_goal (k, n).  Synchronises."""
+        n = self._n if n is None else n
+        m = max(int(max_ticks), 0)
+        pose = np.zeros((m, n, 3)); cmd = np.zeros((m, n, 2)); st = np.zeros((m, n), np.int32); goal = np.zeros((m, n), np.int32)
+        k = C.c_int(0)
+        self._check(self.L.alore_ltv_plant_get_trace(self.h, n, m, _dp(pose), _dp(cmd), st.ctypes.data_as(IP), goal.ctypes.data_as(IP),
+                                                     C.byref(k), None))
+        k = k.value
+        return {"pose": pose[:k], "cmd": cmd[:k], "status": st[:k], "at_goal": goal[:k]}
+
+    def results(self, n=None):
+        """alore_ltv_results: the stored output, xopt, sweeps and status as they lie on the device.  Synchronises."""
+        n = self._n if n is None else n
+        out = np.zeros((n, self.T, 2)); xopt = np.zeros((n, self.T + 1, 3))
+        sw = np.zeros(n, np.int32); st = np.zeros(n, np.int32)
+        self._check(self.L.alore_ltv_results(self.h, n, _dp(out), _dp(xopt), sw.ctypes.data_as(IP), st.ctypes.data_as(IP), None))
+        return {"output": out, "cmd": out[:, self.d].copy(), "xopt": xopt, "sweeps": sw, "status": st}
 
     def tick_converge(self, now_state, max_relin=150, du_th=0.01, reset=False):
         """tick with the stopping rule of get_cmd_converge: cmd (n, 2), status, relin_iters; self.du is fetched as well"""
