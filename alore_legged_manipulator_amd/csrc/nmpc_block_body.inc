@@ -260,12 +260,31 @@ next_item:
                 }
             }
         };
+        // Full block of a grid build (np_ == G, wavefront-uniform; not the shared copy, not the gather): the image is G * 25 * N resp.
+        // G * 5 * N contiguous floats whose size is known when the kernel is compiled, so the pieces are issued in a straight line -- no
+        // test and no clamp per piece (only the one piece that is not full clamps), the LDS base a pointer of the LDS address space
+        // straight from the declaration (dma_full_block, nmpc_block_kernel.hip): 2 instructions per piece where the guarded form takes
+        // 15.  The ragged last block, the shared copy and the gather keep the guarded form; so do the builds of several iterations
+        // (left as they are) and the persistent build without diagnostics, which spills more with the straight line.
         const bool gather = TWOPH && role == 2;
-        if (p.shared & ALORE_NMPC_SHARED_W) dma(pb.W, 25 * N, oW, std::integral_constant<int, UW>{}); // one copy for the batch
-        else if (gather) dma_gather(pb.W, 25 * N, oW, std::integral_constant<int, UW>{});
-        else dma(pb.W + (size_t)prob0 * 25 * N, np_ * 25 * N, oW, std::integral_constant<int, UW>{});
-        if (gather) dma_gather(pb.y, 5 * N, oY, std::integral_constant<int, UY>{});
-        else dma(pb.y + (size_t)prob0 * 5 * N, np_ * 5 * N, oY, std::integral_constant<int, UY>{});
+        bool issued = false;
+        if constexpr (FULLN && ONCE && (DIAG || !PERSIST)) {
+            if (np_ == G && !(p.shared & ALORE_NMPC_SHARED_W) && !gather) {
+                const lds_f32_ptr l3 = (lds_f32_ptr)lds_raw;
+                const float* gW = pb.W + (size_t)prob0 * (25 * NMAX);
+                const float* gY = pb.y + (size_t)prob0 * (5 * NMAX);
+                dma_full_block<G * 25 * NMAX>(gW, gW + 4 * lane, l3, lane);
+                dma_full_block<G * 5 * NMAX>(gY, gY + 4 * lane, l3 + ((G * 25 * NMAX + 255) & ~255), lane);
+                issued = true;
+            }
+        }
+        if (!issued) {
+            if (p.shared & ALORE_NMPC_SHARED_W) dma(pb.W, 25 * N, oW, std::integral_constant<int, UW>{}); // one copy for the batch
+            else if (gather) dma_gather(pb.W, 25 * N, oW, std::integral_constant<int, UW>{});
+            else dma(pb.W + (size_t)prob0 * 25 * N, np_ * 25 * N, oW, std::integral_constant<int, UW>{});
+            if (gather) dma_gather(pb.y, 5 * N, oY, std::integral_constant<int, UY>{});
+            else dma(pb.y + (size_t)prob0 * 5 * N, np_ * 5 * N, oY, std::integral_constant<int, UY>{});
+        }
     }
     float x[S][3], u[S][2], od[S][3], lbv[S][2], ubv[S][2], xN[3];
     float mu0[S], mu1[S]; // bound multipliers: the incoming dual until the first forward sweep overwrites it
@@ -300,6 +319,19 @@ next_item:
     }
     __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): the DMA pieces have landed
     wave_sync();
+    // Single-iteration grid builds: what the objective needs of the terminal cost -- the diagonal of WN and yN as they came from memory --
+    // waits in LDS, in the padding behind the W image (6 floats per group), instead of being read from global memory a second time at the
+    // very end of the wavefront, where nothing covers that round trip.  Written only now: the surplus lanes of the last DMA piece write
+    // into this padding.  (Before the mask below replaces yN of a problem that sits out: these are the values a second read would return.)
+    constexpr bool STASH = FULLN && ONCE;
+    constexpr int oT = G * 25 * NMAX; // first float behind the W image of a full block
+    if constexpr (STASH) {
+        static_assert(((G * 25 * NMAX + 255) & ~255) - G * 25 * NMAX >= 6 * G, "the padding behind the W image holds 6 floats per group");
+        if (j == top) {
+            float* t = lds + oT + 6 * g;
+            t[0] = WN[0]; t[1] = WN[4]; t[2] = WN[8]; t[3] = yN[0]; t[4] = yN[1]; t[5] = yN[2];
+        }
+    }
     if constexpr (TWOPH) {
         if (grp.tp_trace != nullptr && threadIdx.x == 0) grp.tp_trace[(size_t)blockIdx.x * 4 + 1] = (long long)__builtin_amdgcn_s_memrealtime();
     }
@@ -355,6 +387,12 @@ next_item:
     auto body = [&](auto diagw_tag, auto clean_tag) __attribute__((always_inline)) { // (a body past the inliner's size limit would become a call, with every capture in scratch: seen with a 7-stages-per-lane build)
     constexpr bool DIAGW = decltype(diagw_tag)::value;
     constexpr bool CLEAN = decltype(clean_tag)::value; // first pass of a two-phase grid: no prediction, one sweep, problems whose working set moves are queued
+    // Diagonal weights, single-iteration grid builds: once a stage's cost is formed, the off-diagonal entries of its W record in LDS are
+    // dead (tested +-0 above, never read again), so the iterate -- needed again only in phase C -- is parked there by the lane that owns
+    // the stage: x, u in entries 1 .. 5 of the stage's record, the terminal node in entries 7 .. 9 of stage N - 1's.  Phase C reads it
+    // back from LDS instead of from global memory.  Shared W (one copy for all groups: no record of one's own) keeps the global read.
+    constexpr bool PARK = STASH && DIAGW;
+    const bool park = PARK && !(p.shared & ALORE_NMPC_SHARED_W); // wavefront-uniform
     // the two instantiations begin with the same instructions; merged in front of the branch they would stay live through both
     if constexpr (CLEAN) asm volatile("; first pass, diagonal weights" ::: "memory");
     else if constexpr (DIAGW) asm volatile("; diagonal weights" ::: "memory");
@@ -458,6 +496,19 @@ next_item:
             qN[0] = wn[0] * e0 + wn[1] * e1 + wn[2] * e2;
             qN[1] = wn[3] * e0 + wn[4] * e1 + wn[5] * e2;
             qN[2] = wn[6] * e0 + wn[7] * e1 + wn[8] * e2;
+        }
+        if constexpr (PARK) {
+            if (park) {
+#pragma unroll
+                for (int s = 0; s < S; ++s) {
+                    float* Wp = lds + oW + ge * 25 * N + 25 * (j * S + s);
+                    Wp[1] = x[s][0]; Wp[2] = x[s][1]; Wp[3] = x[s][2]; Wp[4] = u[s][0]; Wp[5] = u[s][1];
+                }
+                if (j == top) {
+                    float* Wp = lds + oW + ge * 25 * N + 25 * (N - 1);
+                    Wp[7] = xN[0]; Wp[8] = xN[1]; Wp[9] = xN[2];
+                }
+            }
         }
         { // element [S]: first node of the next lane; the terminal node goes where node N falls
             QA[S].x = lane_next<L>(QA[0].x); QA[S].y = lane_next<L>(QA[0].y); QB[S].x = lane_next<L>(QB[0].x); QC[S].x = lane_next<L>(QC[0].x);
@@ -1269,7 +1320,15 @@ next_item:
         }
 
         float gd = 0.0f, comp = 0.0f;
-        if constexpr (ONCE) {
+        if (PARK && park) { // parked in the dead entries of the lane's own W records after phase A
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                const float* Wp = lds + oW + ge * 25 * N + 25 * (j * S + s);
+                x[s][0] = Wp[1]; x[s][1] = Wp[2]; x[s][2] = Wp[3]; u[s][0] = Wp[4]; u[s][1] = Wp[5];
+            }
+            const float* Wn = lds + oW + ge * 25 * N + 25 * (N - 1);
+            xN[0] = Wn[7]; xN[1] = Wn[8]; xN[2] = Wn[9]; // meaningful in lane `top`, which alone uses it
+        } else if constexpr (ONCE) {
             // single-iteration build: the iterate was only needed for the linearisation; it is read again here (L2 / MALL) so
             // that x, u do not occupy 5 S + 3 registers per lane through the prediction and the sweeps
             typedef float f3u __attribute__((ext_vector_type(3), aligned(4)));
@@ -1375,7 +1434,10 @@ next_item:
         }
         if (j == top) { // the reference uses only the diagonal of WN here (acado_solver.c:1442-1444)
             float w0 = WN[0], w4 = WN[4], w8 = WN[8], y0 = yN[0], y1 = yN[1], y2 = yN[2];
-            if constexpr (ONCE) { // read again instead of held since phase A
+            if constexpr (STASH) { // left in LDS after phase 0
+                const float* t = lds + oT + 6 * g;
+                w0 = t[0]; w4 = t[1]; w8 = t[2]; y0 = t[3]; y1 = t[4]; y2 = t[5];
+            } else if constexpr (ONCE) { // read again instead of held since phase A
                 const float* gW = pb.WN + ((p.shared & ALORE_NMPC_SHARED_W) ? 0 : (size_t)prob * 9);
                 const float* gy = pb.yN + (size_t)prob * 3;
                 w0 = gW[0]; w4 = gW[4]; w8 = gW[8]; y0 = gy[0]; y1 = gy[1]; y2 = gy[2];

@@ -21,7 +21,8 @@
 //
 // Builds: DIAG (KKT value and objective wanted), STAMP (phase stamps, diagnostic), ONCE (n_sqp = 1, the control tick: no
 // iteration loop, so od / the raw bounds die after the linearisation and the iterate, WN, yN are read again at the end
-// instead of held -- (4, 5) 435 registers instead of 512 + scratch, (16, 2) 252: two wavefronts per SIMD).
+// instead of held -- (4, 5) 435 registers instead of 512 + scratch, (16, 2) 252: two wavefronts per SIMD; the N = 20 grid builds
+// (FULLN) read them again from LDS, where they wait in the padding and in dead entries of the W image: nmpc_block_body.inc).
 // Which (L, S) runs: block_geometry() (nmpc_launch_plan.h) -- the widest L whose wavefronts, over ALL launches in flight
 // (alore_nmpc_rti_many, nmpc_capi.hip), still fit one per SIMD.
 //
@@ -219,6 +220,27 @@ __device__ __forceinline__ void g_store(float* g, const float* l, int total, int
         if (i < n4) reinterpret_cast<float4*>(g)[i] = reinterpret_cast<const float4*>(l)[i];
     }
     if (lane < rem) g[n4 * 4 + lane] = l[n4 * 4 + lane];
+}
+
+// ---- global -> LDS by DMA, TOTAL contiguous floats (known when the kernel is compiled), issued in a straight line: piece U moves the
+// 1 KB at byte 1024 U of the source to byte 1024 U of the image.  `gl` is the source advanced by the lane's 16 bytes, `l3` the image (a
+// pointer of the LDS address space: nothing is tested or cast per piece).  Two consecutive pieces share one global address and one
+// LDS base: the instruction's immediate offset advances both by the same 1 KB.  (Four per base, which the offset field would reach,
+// cost the traced persistent build five spills; pairs cost no build any.)  Only the last piece can be short: its lanes past the
+// end re-read the last 16 bytes of the source (their LDS slots are padding of the image, which is a whole number of pieces).
+typedef __attribute__((address_space(3))) float* lds_f32_ptr;
+template <int TOTAL, int U = 0>
+__device__ __forceinline__ void dma_full_block(const float* gsrc, const float* gl, lds_f32_ptr l3, int lane)
+{
+    static_assert(TOTAL % 4 == 0, "16 bytes per lane");
+    constexpr int N4 = TOTAL / 4, PIECES = (N4 + 63) / 64;
+    if constexpr (U < PIECES) {
+        constexpr int BASE = (U & ~1) * 256, OFF = (U & 1) * 1024; // floats, bytes
+        const float* gp = gl + BASE;
+        if constexpr ((U + 1) * 64 > N4) gp = gsrc + 4 * min(U * 64 + lane, N4 - 1) - OFF / 4;
+        __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)gp, (void __attribute__((address_space(3)))*)(l3 + BASE), 16, OFF, 0);
+        dma_full_block<TOTAL, U + 1>(gsrc, gl, l3, lane);
+    }
 }
 
 // ---- packed float32 (v_pk_fma_f32 / v_pk_mul_f32, gfx90a+: two multiply-adds per issue slot of a wavefront) ------------
