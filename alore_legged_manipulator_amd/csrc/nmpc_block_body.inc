@@ -386,6 +386,9 @@ next_item:
     }
     auto body = [&](auto diagw_tag, auto clean_tag) __attribute__((always_inline)) { // (a body past the inliner's size limit would become a call, with every capture in scratch: seen with a 7-stages-per-lane build)
     constexpr bool DIAGW = decltype(diagw_tag)::value;
+    // L = 4: scans, sums and maxima over the problem's lanes stay inside the DPP quad (nmpc_group_ops.h: the same bits in fewer issue
+    // slots).  The diagonal-weights body only: the general-weights body keeps the generic forms and with them its register allocation
+    constexpr bool QUAD = (L == 4) && DIAGW;
     constexpr bool CLEAN = decltype(clean_tag)::value; // first pass of a two-phase grid: no prediction, one sweep, problems whose working set moves are queued
     // Diagonal weights, single-iteration grid builds: once a stage's cost is formed, the off-diagonal entries of its W record in LDS are
     // dead (tested +-0 above, never read again), so the iterate -- needed again only in phase C -- is parked there by the lane that owns
@@ -555,7 +558,7 @@ next_item:
                     float acc = 0.0f;
 #pragma unroll
                     for (int s = 0; s < S; ++s) { acc += BP2[s].x * (v[s].x - v[s].y) + d2[s]; X2[s] = acc; }
-                    const float ex2 = gprefix<L>(acc, j) - acc + Dx2; // psi entering the block
+                    const float ex2 = gprefix1<L, QUAD>(acc, j) - acc + Dx2; // psi entering the block
 #pragma unroll
                     for (int s = 0; s < S; ++s) { in2[s] = (s == 0) ? ex2 : X2[(s > 0) ? s - 1 : 0] + ex2; }
 #pragma unroll
@@ -568,7 +571,9 @@ next_item:
                         a += pfma(Bc0, bc2(v[s].x), pfma(Bc1, bc2(v[s].y), t));
                         X01[s] = a;
                     }
-                    const v2f ex01 = mk2(gprefix<L>(a.x, j) - a.x + Dx0, gprefix<L>(a.y, j) - a.y + Dx1);
+                    float pa0 = a.x, pa1 = a.y;
+                    gprefix2<L, QUAD>(pa0, pa1, j);
+                    const v2f ex01 = mk2(pa0 - a.x + Dx0, pa1 - a.y + Dx1);
                     v2f y01[S];
                     float y2[S];
 #pragma unroll
@@ -584,8 +589,9 @@ next_item:
                     v2f b = bc2(0.0f); // (b0, b1)
 #pragma unroll
                     for (int s = S - 1; s >= 0; --s) { b += y01[s]; Lxy[s] = b; }
-                    const float pr0 = gprefix<L>(b.x, j), pr1 = gprefix<L>(b.y, j);
-                    const v2f es01 = mk2(glast<L>(pr0, lane) - pr0, glast<L>(pr1, lane) - pr1); // sum over the lanes above
+                    float es0 = b.x, es1 = b.y;
+                    gabove2<L, QUAD>(es0, es1, j, lane); // sum over the lanes above
+                    const v2f es01 = mk2(es0, es1);
 #pragma unroll
                     for (int s = 0; s < S; ++s) Lxy[s] += es01;
                     // adjoint at node k + 2: the next slot's, the next lane's first, zero past the end of the group
@@ -599,8 +605,7 @@ next_item:
                         b2 += y2[s] + sa[s + 1] * nxs + sb[s + 1] * nys;
                         Lp[s] = b2;
                     }
-                    const float pr2 = gprefix<L>(b2, j);
-                    const float es2 = glast<L>(pr2, lane) - pr2;
+                    const float es2 = gabove<L, QUAD>(b2, j, lane);
 #pragma unroll
                     for (int s = 0; s < S; ++s) {
                         const float Lps = Lp[s] + es2;
@@ -652,8 +657,8 @@ next_item:
                             nd = pfma(RD[s] * e, e, nd);
                             dd = pfma(e, cg[s] - qg[s], dd);
                         }
-                        const float num = gtotal<L>(nd.x + nd.y, j, lane);
-                        const float den = gtotal<L>(dd.x + dd.y, j, lane);
+                        float num = nd.x + nd.y, den = dd.x + dd.y;
+                        gtotal2<L, QUAD>(num, den, j, lane);
                         alpha = (den > 1e-30f) ? fminf(fmaxf(num * __builtin_amdgcn_rcpf(den), 1e-3f), 1.0f) : alpha;
                         const v2f na = bc2(-alpha);
                         int moved = 0;
@@ -708,7 +713,7 @@ next_item:
                     float acc = 0.0f;
 #pragma unroll
                     for (int s = 0; s < S; ++s) { acc += BP2[s].x * (v0[s] - v1[s]) + d2[s]; X2[s] = acc; }
-                    const float ex2 = gprefix<L>(acc, j) - acc + Dx2; // psi entering the block
+                    const float ex2 = gprefix1<L, QUAD>(acc, j) - acc + Dx2; // psi entering the block
 #pragma unroll
                     for (int s = 0; s < S; ++s) { in2[s] = (s == 0) ? ex2 : X2[(s > 0) ? s - 1 : 0] + ex2; }
 #pragma unroll
@@ -719,7 +724,9 @@ next_item:
                         a0 += sa[s] * in2[s] + BP0[s].x * v0[s] + BP0[s].y * v1[s] + d0[s]; X0[s] = a0;
                         a1 += sb[s] * in2[s] + BP1[s].x * v0[s] + BP1[s].y * v1[s] + d1[s]; X1[s] = a1;
                     }
-                    const float ex0 = gprefix<L>(a0, j) - a0 + Dx0, ex1 = gprefix<L>(a1, j) - a1 + Dx1;
+                    float pa0 = a0, pa1 = a1;
+                    gprefix2<L, QUAD>(pa0, pa1, j);
+                    const float ex0 = pa0 - a0 + Dx0, ex1 = pa1 - a1 + Dx1;
                     float y0[S], y1[S], y2[S];
 #pragma unroll
                     for (int s = 0; s < S; ++s) {
@@ -733,8 +740,8 @@ next_item:
                     float b0 = 0.0f, b1 = 0.0f;
 #pragma unroll
                     for (int s = S - 1; s >= 0; --s) { b0 += y0[s]; Lx[s] = b0; b1 += y1[s]; Ly[s] = b1; }
-                    const float pr0 = gprefix<L>(b0, j), pr1 = gprefix<L>(b1, j);
-                    const float es0 = glast<L>(pr0, lane) - pr0, es1 = glast<L>(pr1, lane) - pr1; // sum over the lanes above
+                    float es0 = b0, es1 = b1;
+                    gabove2<L, QUAD>(es0, es1, j, lane); // sum over the lanes above
 #pragma unroll
                     for (int s = 0; s < S; ++s) { Lx[s] += es0; Ly[s] += es1; }
                     // adjoint at node k + 2: the next slot's, the next lane's first, zero past the end of the group
@@ -748,8 +755,7 @@ next_item:
                         b2 += y2[s] + sa[s + 1] * nxs + sb[s + 1] * nys;
                         Lp[s] = b2;
                     }
-                    const float pr2 = gprefix<L>(b2, j);
-                    const float es2 = glast<L>(pr2, lane) - pr2;
+                    const float es2 = gabove<L, QUAD>(b2, j, lane);
 #pragma unroll
                     for (int s = 0; s < S; ++s) {
                         const float Lps = Lp[s] + es2;
@@ -801,8 +807,7 @@ next_item:
                             num += RD[s].x * e0 * e0 + RD[s].y * e1 * e1;
                             den += e0 * (cg0[s] - qg0[s]) + e1 * (cg1[s] - qg1[s]);
                         }
-                        num = gtotal<L>(num, j, lane);
-                        den = gtotal<L>(den, j, lane);
+                        gtotal2<L, QUAD>(num, den, j, lane);
                         alpha = (den > 1e-30f) ? fminf(fmaxf(num * __builtin_amdgcn_rcpf(den), 1e-3f), 1.0f) : alpha;
                         int moved = 0;
 #pragma unroll
@@ -910,9 +915,18 @@ next_item:
                 constexpr int ROWS = decltype(rows)::value;
                 const bool has = (L >= 16) || (j >= dist);
                 auto fetch = [&](float v, float ident) { const float r = dppr<CTRL, ROWS>(ident, v); return has ? r : ident; };
-                const float g00 = fetch(m00, 1.f), g01 = fetch(m01, 0.f), g02 = fetch(m02, 0.f), g10 = fetch(m10, 0.f),
-                            g11 = fetch(m11, 1.f), g12 = fetch(m12, 0.f), g20 = fetch(m20, 0.f), g21 = fetch(m21, 0.f),
-                            g22 = fetch(m22, 1.f), gc0 = fetch(k0, 0.f), gc1 = fetch(k1, 0.f), gc2 = fetch(k2, 0.f);
+                float g00, g01, g02, g10, g11, g12, g20, g21, g22, gc0, gc1, gc2;
+                if constexpr (QUAD) { // the twelve values inside the quad, in one block (nmpc_group_ops.h): the same bits
+                    const float mm[12] = {m00, m01, m02, m10, m11, m12, m20, m21, m22, k0, k1, k2};
+                    float gg[12];
+                    quad_fetch_map<(CTRL == 0x111) ? 1 : 2>(mm, gg, j);
+                    g00 = gg[0]; g01 = gg[1]; g02 = gg[2]; g10 = gg[3]; g11 = gg[4]; g12 = gg[5];
+                    g20 = gg[6]; g21 = gg[7]; g22 = gg[8]; gc0 = gg[9]; gc1 = gg[10]; gc2 = gg[11];
+                } else {
+                    g00 = fetch(m00, 1.f); g01 = fetch(m01, 0.f); g02 = fetch(m02, 0.f); g10 = fetch(m10, 0.f);
+                    g11 = fetch(m11, 1.f); g12 = fetch(m12, 0.f); g20 = fetch(m20, 0.f); g21 = fetch(m21, 0.f);
+                    g22 = fetch(m22, 1.f); gc0 = fetch(k0, 0.f); gc1 = fetch(k1, 0.f); gc2 = fetch(k2, 0.f);
+                }
                 const float n00 = m00 * g00 + m01 * g10 + m02 * g20, n01 = m00 * g01 + m01 * g11 + m02 * g21,
                             n02 = m00 * g02 + m01 * g12 + m02 * g22;
                 const float n10 = m10 * g00 + m11 * g10 + m12 * g20, n11 = m10 * g01 + m11 * g11 + m12 * g21,
@@ -1180,7 +1194,7 @@ next_item:
                     e0 = n0; e1 = n1; e2 = n2;
                 }
                 if (active) { dxo[0] = e0; dxo[1] = e1; dxo[2] = e2; }
-                new_khi = gmax<L>(new_khi, j, lane);
+                new_khi = gmax1<L, QUAD>(new_khi, j, lane);
             }
             ++it;
             if (active) {
@@ -1303,7 +1317,7 @@ next_item:
             float loc[S], acc = 0.0f;
 #pragma unroll
             for (int s = 0; s < S; ++s) { loc[s] = acc; acc += d2[s]; }
-            const float ex2 = gprefix<L>(acc, j) - acc + Dx2;
+            const float ex2 = gprefix1<L, QUAD>(acc, j) - acc + Dx2;
 #pragma unroll
             for (int s = 0; s < S; ++s) sbs[s][2] = loc[s] + ex2;
             sbo[2] = acc + ex2;
@@ -1313,7 +1327,9 @@ next_item:
                 l0[s] = a0; a0 += sa[s] * sbs[s][2] + d0[s];
                 l1[s] = a1; a1 += sb[s] * sbs[s][2] + d1[s];
             }
-            const float ex0 = gprefix<L>(a0, j) - a0 + Dx0, ex1 = gprefix<L>(a1, j) - a1 + Dx1;
+            float pa0 = a0, pa1 = a1;
+            gprefix2<L, QUAD>(pa0, pa1, j);
+            const float ex0 = pa0 - a0 + Dx0, ex1 = pa1 - a1 + Dx1;
 #pragma unroll
             for (int s = 0; s < S; ++s) { sbs[s][0] = l0[s] + ex0; sbs[s][1] = l1[s] + ex1; }
             sbo[0] = a0 + ex0; sbo[1] = a1 + ex1;
@@ -1397,7 +1413,7 @@ next_item:
 #pragma unroll
             for (int c = 0; c < 3; ++c) xN[c] = __int_as_float(__builtin_amdgcn_ds_bpermute((gbase + top) * 4, __float_as_int(xN[c])));
         }
-        if (DIAG) kkt = fabsf(gtotal<L>(gd, j, lane)) + gtotal<L>(comp, j, lane);
+        if (DIAG) { gtotal2<L, QUAD>(gd, comp, j, lane); kkt = fabsf(gd) + comp; }
         if constexpr (CONV) {
             // the results of the iteration that met the tolerance stay
             status_c = done ? status_c : status; n_iter_c = done ? n_iter_c : n_iter; kkt_c = done ? kkt_c : kkt;
@@ -1445,7 +1461,7 @@ next_item:
             const float e0 = xN[0] - y0, e1 = xN[1] - y1, e2 = xN[2] - y2;
             part += e0 * e0 * w0 + e1 * e1 * w4 + e2 * e2 * w8;
         }
-        obj = 0.5f * gtotal<L>(part, j, lane);
+        obj = 0.5f * gtotal1<L, QUAD>(part, j, lane);
     }
     // problems the caller masked out (alore_nmpc_set_problem_mask: idle robots of a fleet) go back exactly as they came: their
     // lanes ran along on whatever the members hold (results of a group never reach another group), now they fetch the

@@ -40,6 +40,7 @@
 
 #include "nmpc_core.h"
 #include "nmpc_scan.h"
+#include "nmpc_group_ops.h" // DPP moves, scans and reductions over the lanes of a problem; the quad-native forms of L = 4
 
 // -DALORE_PHASE_MARKERS (tools/asm_phases.py, never the shipped build): every phase boundary leaves `; @phase <name>` in the assembly
 #ifdef ALORE_PHASE_MARKERS
@@ -56,129 +57,6 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// DPP move inside a row of 16 lanes; lanes without a source keep `old`
-template <int CTRL>
-__device__ __forceinline__ float dppk(float old, float x)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(x), CTRL, 0xF, 0xF, false));
-}
-template <int CTRL>
-__device__ __forceinline__ int dppk_i(int old, int x)
-{
-    return __builtin_amdgcn_update_dpp(old, x, CTRL, 0xF, 0xF, false);
-}
-// DPP move with a row mask: rows outside the mask keep `old`
-template <int CTRL, int ROWS>
-__device__ __forceinline__ float dppr(float old, float x)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(x), CTRL, ROWS, 0xF, false));
-}
-template <int CTRL, int ROWS>
-__device__ __forceinline__ int dppr_i(int old, int x)
-{
-    return __builtin_amdgcn_update_dpp(old, x, CTRL, ROWS, 0xF, false);
-}
-// lane i <- lane i + 1 / lane i - 1.  Groups of up to 16 lanes sit inside a DPP row (row_shl / row_shr: the lane at the
-// end of a row keeps its value); a group of 32 spans two rows and uses the wavefront shifts of gfx9 (the lane at the end
-// of a group then sees its neighbour group's value: every caller treats the edge lanes separately).
-template <int L>
-__device__ __forceinline__ float lane_next(float x)
-{
-    if constexpr (L == 32) return dppk<0x130>(x, x); // wave_shl:1
-    else return dppk<0x101>(x, x);                    // row_shl:1
-}
-template <int L>
-__device__ __forceinline__ float lane_prev(float x)
-{
-    if constexpr (L == 32) return dppk<0x138>(x, x); // wave_shr:1
-    else return dppk<0x111>(x, x);                    // row_shr:1
-}
-
-// value of the first / last lane of the group of L lanes (L = 4: quad_perm; 8, 16: row_newbcast, gfx90a+; 32: the two
-// group ends through scalar registers)
-template <int L>
-__device__ __forceinline__ float gfirst(float x, int lane)
-{
-    if constexpr (L == 4) return dppk<0x00>(x, x);
-    else if constexpr (L == 16) return dppk<0x150>(x, x);
-    else if constexpr (L == 32) {
-        const int lo = __builtin_amdgcn_readlane(__float_as_int(x), 0), hi = __builtin_amdgcn_readlane(__float_as_int(x), 32);
-        return __int_as_float((lane & 32) ? hi : lo);
-    } else { const float lo = dppk<0x150>(x, x), hi = dppk<0x158>(x, x); return (lane & 8) ? hi : lo; }
-}
-template <int L>
-__device__ __forceinline__ float glast(float x, int lane)
-{
-    if constexpr (L == 4) return dppk<0xFF>(x, x);
-    else if constexpr (L == 16) return dppk<0x15F>(x, x);
-    else if constexpr (L == 32) {
-        const int lo = __builtin_amdgcn_readlane(__float_as_int(x), 31), hi = __builtin_amdgcn_readlane(__float_as_int(x), 63);
-        return __int_as_float((lane & 32) ? hi : lo);
-    } else { const float lo = dppk<0x157>(x, x), hi = dppk<0x15F>(x, x); return (lane & 8) ? hi : lo; }
-}
-// inclusive prefix sum over the lanes of a group (row_shr:1, 2, 4, 8; groups are aligned inside DPP rows; a group of 32
-// adds the total of its first row to its second: row_bcast:15 into rows 1 and 3)
-template <int L>
-__device__ __forceinline__ float gprefix(float x, int j)
-{
-    float v;
-    v = dppk<0x111>(0.0f, x); if (L < 16) v = (j >= 1) ? v : 0.0f; x += v;
-    v = dppk<0x112>(0.0f, x); if (L < 16) v = (j >= 2) ? v : 0.0f; x += v;
-    if constexpr (L >= 8) { v = dppk<0x114>(0.0f, x); if (L < 16) v = (j >= 4) ? v : 0.0f; x += v; }
-    if constexpr (L >= 16) { v = dppk<0x118>(0.0f, x); x += v; }
-    if constexpr (L >= 32) { v = dppr<0x142, 0xA>(0.0f, x); x += v; }
-    return x;
-}
-template <int L>
-__device__ __forceinline__ int gprefix_max(int x, int j)
-{
-    constexpr int NEG = -2147483647 - 1;
-    int v;
-    v = dppk_i<0x111>(NEG, x); if (L < 16) v = (j >= 1) ? v : NEG; x = max(x, v);
-    v = dppk_i<0x112>(NEG, x); if (L < 16) v = (j >= 2) ? v : NEG; x = max(x, v);
-    if constexpr (L >= 8) { v = dppk_i<0x114>(NEG, x); if (L < 16) v = (j >= 4) ? v : NEG; x = max(x, v); }
-    if constexpr (L >= 16) { v = dppk_i<0x118>(NEG, x); x = max(x, v); }
-    if constexpr (L >= 32) { v = dppr_i<0x142, 0xA>(NEG, x); x = max(x, v); }
-    return x;
-}
-template <int L>
-__device__ __forceinline__ float gtotal(float x, int j, int lane) { return glast<L>(gprefix<L>(x, j), lane); }
-template <int L>
-__device__ __forceinline__ int gmax(int x, int j, int lane)
-{
-    return __float_as_int(glast<L>(__int_as_float(gprefix_max<L>(x, j)), lane));
-}
-// lexicographic minimum of (v, key) over the lanes of a group, in every lane
-template <int L>
-__device__ __forceinline__ void gmin_pair(float& v, int& key, int j, int lane)
-{
-    auto step = [&](auto tag, auto rows, int dist) {
-        constexpr int CTRL = decltype(tag)::value;
-        constexpr int ROWS = decltype(rows)::value;
-        const float pv = dppr<CTRL, ROWS>(v, v);
-        const int pk = dppr_i<CTRL, ROWS>(key, key);
-        const bool has = (L >= 16) || (j >= dist);
-        const bool take = has && ((pv < v) || (pv == v && pk < key));
-        v = take ? pv : v;
-        key = take ? pk : key;
-    };
-    using all = std::integral_constant<int, 0xF>;
-    step(std::integral_constant<int, 0x111>{}, all{}, 1);
-    step(std::integral_constant<int, 0x112>{}, all{}, 2);
-    if constexpr (L >= 8) step(std::integral_constant<int, 0x114>{}, all{}, 4);
-    if constexpr (L >= 16) step(std::integral_constant<int, 0x118>{}, all{}, 8);
-    if constexpr (L >= 32) step(std::integral_constant<int, 0x142>{}, std::integral_constant<int, 0xA>{}, 16);
-    v = glast<L>(v, lane);
-    key = __float_as_int(glast<L>(__int_as_float(key), lane));
-}
-template <int L>
-__device__ __forceinline__ bool gany(bool pred, int base)
-{
-    const unsigned long long m = __ballot(pred);
-    constexpr unsigned long long MASK = (L >= 64) ? ~0ull : ((1ull << (L & 63)) - 1ull);
-    return ((m >> base) & MASK) != 0ull;
 }
 
 // ---- global <-> LDS, coalesced: all loads of a launch are issued before the first LDS store ---------------------

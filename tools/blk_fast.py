@@ -11,7 +11,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "alore_legged_manipulator_amd", "csrc", "nmpc_block_kernel.hip")
-OUT = "/tmp/blk/fast"
+OUT = os.environ.get("BLK_FAST_OUT", "/tmp/blk/fast")  # one directory per run when several run at a time
 
 
 def main():
@@ -28,7 +28,7 @@ def main():
     os.makedirs(OUT, exist_ok=True)
     open(os.path.join(OUT, "fast.hip"), "w").write(head + tail)
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp",
-           "-fPIC", "-save-temps=obj", "-c", os.path.join(OUT, "fast.hip"), "-o", os.path.join(OUT, "fast.o")] + extra
+           "-fPIC", "-I", os.path.dirname(SRC), "-save-temps=obj", "-c",os.path.join(OUT, "fast.hip"), "-o", os.path.join(OUT, "fast.o")] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=OUT)
     if r.returncode != 0:
         sys.exit(r.stderr[-3000:])
