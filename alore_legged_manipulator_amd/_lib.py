@@ -57,6 +57,17 @@ class PlantParams(C.Structure):
                 ("state_propa_period", C.c_double), ("substeps", C.c_int)]
 
 
+class EkfParams(C.Structure):
+    """alore_ekf_params (include/alore_nmpc.h): the reference's icrekf node parameters"""
+    _fields_ = [("q", C.c_double * 6), ("r", C.c_double * 3), ("init_icr", C.c_double * 3), ("standard", C.c_double * 3),
+                ("odom_every", C.c_int)]
+
+
+class EkfView(C.Structure):
+    """alore_ekf_view (include/alore_nmpc.h): device pointers of the filter"""
+    _fields_ = [("x", C.c_void_p), ("P", C.c_void_p), ("est_pose", C.c_void_p), ("est_icr", C.c_void_p), ("status", C.c_void_p)]
+
+
 class LaunchInfo(C.Structure):
     _fields_ = [("lanes_per_problem", C.c_int), ("problems_per_block", C.c_int), ("threads_per_block", C.c_int),
                 ("grid", C.c_int), ("lds_bytes_per_block", C.c_int), ("last_kernel_ms", C.c_float)]
@@ -120,6 +131,16 @@ SYMBOLS = (
     ("alore_nmpc_closed_loop_run", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p]),
     ("alore_nmpc_refs_sample", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int,
                                          C.c_void_p, C.c_void_p]),
+    ("alore_nmpc_ekf_default_params", None, [C.POINTER(EkfParams)]),
+    ("alore_nmpc_ekf_init", C.c_int, [C.c_void_p, C.POINTER(EkfParams)]),
+    ("alore_nmpc_ekf_reset", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("alore_nmpc_ekf_set_state", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("alore_nmpc_ekf_step", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("alore_nmpc_ekf_get", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("alore_nmpc_ekf_device", C.c_int, [C.c_void_p, C.POINTER(EkfView)]),
+    ("alore_nmpc_ekf_closed_loop_tick", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p]),
+    ("alore_nmpc_ekf_closed_loop_run", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p,
+                                                 C.c_void_p]),
     ("alore_nmpc_set_linearization_point", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("alore_nmpc_get_launch_info", C.c_int, [C.c_void_p, C.POINTER(LaunchInfo)]),
     ("alore_nmpc_set_timing", C.c_int, [C.c_void_p, C.c_int]),

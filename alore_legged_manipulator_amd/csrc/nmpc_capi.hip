@@ -117,6 +117,7 @@ int alore_nmpc_destroy(alore_nmpc_handle h)
     h->poly.release();
     h->timing.release();
     h->pinned.release();
+    h->ekf.release();
     delete h;
     return ALORE_NMPC_OK;
 }

@@ -1,5 +1,5 @@
-// nmpc_solver.h -- the handle behind the C ABI of include/alore_nmpc.h and what its two implementation files (nmpc_capi.hip: the
-// solver; nmpc_refs_capi.hip: reference store, plant, closed loop) share (internal).
+// nmpc_solver.h -- the handle behind the C ABI of include/alore_nmpc.h and what its implementation files (nmpc_capi.hip: the
+// solver; nmpc_refs_capi.hip: reference store, plant, closed loop; icr_ekf.hip: the ICR EKF and the loop on its estimate) share (internal).
 #ifndef ALORE_NMPC_SOLVER_H
 #define ALORE_NMPC_SOLVER_H
 
@@ -243,6 +243,19 @@ struct alore_nmpc_solver {
             if (d_tickets) (void)hipFree(d_tickets);
         }
     } tickets;
+
+    // the ICR EKF on the device (alore_nmpc_ekf_*, icr_ekf.hip): one allocation for the capacity of the trajectory store, made by
+    // alore_nmpc_ekf_init and cut up there; the parameters as the caller gave them; the ticks of the EKF closed loop since the reset
+    struct Ekf {
+        char* d_block = nullptr;
+        int B = 0;
+        alore_ekf_params params{};
+        long ticks = 0;
+        void release()
+        {
+            if (d_block) (void)hipFree(d_block);
+        }
+    } ekf;
 };
 
 namespace nmpc_capi {

@@ -24,6 +24,15 @@ from . import _lib
 from ._lib import BATCH_FLOAT_MEMBERS, BATCH_MEMBERS, Batch, Config, LaunchInfo, LinOut, NmpcError
 
 NX, NU, NOD, NY, NYN = 3, 2, 3, 5, 3
+# statuses of the ICR EKF (include/alore_nmpc.h: ALORE_EKF_*)
+EKF_OK, EKF_MASKED, EKF_E_DEGENERATE, EKF_E_NONFINITE, EKF_E_SINGULAR, EKF_E_MEAS = 0, 1, -1, -2, -3, -4
+
+
+def ekf_default_params() -> "_lib.EkfParams":
+    """the icrekf node's parameters of planner_sim.launch (no GPU needed)"""
+    p = _lib.EkfParams()
+    _lib.load().alore_nmpc_ekf_default_params(C.byref(p))
+    return p
 
 
 def member_shapes(B: int, N: int) -> dict:
@@ -362,6 +371,83 @@ class BatchedNmpc:
         """n_ticks closed-loop ticks at t0, t0 + dt_tick, ... enqueued back to back by the library."""
         self._check(self.lib.alore_nmpc_closed_loop_run(self.h, C.byref(self._batches[slot]), self.B, float(t0), float(dt_tick),
                                                         int(n_ticks), int(delay_num), self._stream()))
+
+    # -- the ICR EKF on the device and the closed loop on its estimate (include/alore_nmpc.h: alore_nmpc_ekf_*)
+    def ekf_init(self, **params) -> None:
+        """params: fields of alore_ekf_params (q, r, init_icr as (yr, yl, xv), standard, odom_every); the rest are the launch file's"""
+        p = ekf_default_params()
+        for k, v in params.items():
+            if k == "odom_every":
+                p.odom_every = int(v)
+            else:
+                arr = getattr(p, k)
+                for i, a in enumerate(np.asarray(v, np.float64).reshape(len(arr))):
+                    arr[i] = float(a)
+        self._check(self.lib.alore_nmpc_ekf_init(self.h, C.byref(p)))
+        self.ekf_params = p
+        self._ekf_ticks = 0   # mirrors the handle's count: sizes the noise a run reads
+
+    def ekf_reset(self, pose=None, icr0=None, mask=None) -> None:
+        """x <- (pose, icr0), P <- 0, held wheel speeds <- 0, flags cleared; pose None: the plant's pose; icr0 None: init_icr"""
+        pose = None if pose is None else np.ascontiguousarray(pose, np.float64).reshape(self.B, 3)
+        icr0 = None if icr0 is None else np.ascontiguousarray(icr0, np.float64).reshape(self.B, 3)
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.B)
+        self._check(self.lib.alore_nmpc_ekf_reset(self.h, self.B, None if pose is None else pose.ctypes.data,
+                                                  None if icr0 is None else icr0.ctypes.data, None if m is None else m.ctypes.data,
+                                                  self._stream()))
+        self._ekf_ticks = 0
+
+    def _ekf_updates(self, n_ticks: int) -> int:
+        """pose updates that fall into the next n_ticks ticks"""
+        e = self.ekf_params.odom_every
+        return (self._ekf_ticks + int(n_ticks)) // e - self._ekf_ticks // e
+
+    def ekf_set_state(self, x=None, P=None, u=None) -> None:
+        a = [None if v is None else np.ascontiguousarray(v, np.float64).reshape(self.B, n) for v, n in ((x, 6), (P, 36), (u, 2))]
+        self._check(self.lib.alore_nmpc_ekf_set_state(self.h, self.B, *[None if v is None else v.ctypes.data for v in a], self._stream()))
+
+    def _ekf_dev(self, t, shape, dtype):
+        if t is None:
+            return None
+        if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"expected a contiguous {dtype} device tensor of shape {shape}")
+        return t.data_ptr()
+
+    def ekf_step(self, wheel, dt: float, meas=None, mask=None) -> None:
+        """one filter step from torch DEVICE tensors: wheel (B, 2) float64 = (left, right), meas (B, 3) float64 or None, mask (B,)
+        uint8 or None.  Asynchronous: the tensors must stay alive and unchanged until the stream has passed the call."""
+        f64, u8 = self.torch.float64, self.torch.uint8
+        self._check(self.lib.alore_nmpc_ekf_step(self.h, self.B, self._ekf_dev(wheel, (self.B, 2), f64), float(dt),
+                                                 self._ekf_dev(meas, (self.B, 3), f64), self._ekf_dev(mask, (self.B,), u8), self._stream()))
+
+    def ekf_get(self) -> dict:
+        """x (B, 6), P (B, 6, 6), status (B,), conv_step (B, 3).  Synchronises."""
+        x = np.zeros((self.B, 6)); P = np.zeros((self.B, 6, 6)); st = np.zeros(self.B, np.int32); cs = np.zeros((self.B, 3), np.int32)
+        self._check(self.lib.alore_nmpc_ekf_get(self.h, self.B, x.ctypes.data, P.ctypes.data, st.ctypes.data, cs.ctypes.data))
+        return {"x": x, "P": P, "status": st, "conv_step": cs}
+
+    def ekf_view(self) -> "_lib.EkfView":
+        v = _lib.EkfView()
+        self._check(self.lib.alore_nmpc_ekf_device(self.h, C.byref(v)))
+        return v
+
+    def ekf_closed_loop_tick(self, now: float, dt_tick: float = 0.01, delay_num: int = 1, noise=None, slot: int = 0) -> None:
+        """References from the ESTIMATE -> one real-time iteration -> plant on the true state, ControlPub, filter step; noise: device
+        tensor (B, 3) float64 added to the measured pose on update ticks, or None.  No host sync."""
+        self._check(self.lib.alore_nmpc_ekf_closed_loop_tick(self.h, C.byref(self._batches[slot]), self.B, float(now), float(dt_tick),
+                                                             int(delay_num), self._ekf_dev(noise, (self.B, 3), self.torch.float64),
+                                                             self._stream()))
+        self._ekf_ticks += 1
+
+    def ekf_closed_loop_run(self, t0: float, dt_tick: float, n_ticks: int, delay_num: int = 1, noise=None, slot: int = 0) -> None:
+        """n_ticks of ekf_closed_loop_tick back to back; noise: device tensor (updates, B, 3) float64, one slice per update of the run"""
+        if noise is not None and not (noise.is_cuda and noise.dtype == self.torch.float64 and noise.is_contiguous() and noise.dim() == 3
+                                      and tuple(noise.shape[1:]) == (self.B, 3) and noise.shape[0] >= self._ekf_updates(n_ticks)):
+            raise ValueError("noise: a contiguous float64 device tensor (updates, B, 3) with a slice for every update of the run")
+        self._check(self.lib.alore_nmpc_ekf_closed_loop_run(self.h, C.byref(self._batches[slot]), self.B, float(t0), float(dt_tick),
+                                                            int(n_ticks), int(delay_num), None if noise is None else noise.data_ptr(),
+                                                            self._stream()))
+        self._ekf_ticks += int(n_ticks)
 
     def set_shared_members(self, W: bool = False, bounds: bool = False, od: bool = False) -> None:
         """Members that are ONE copy for the whole batch (row 0 of the corresponding tensors is what every problem reads)."""

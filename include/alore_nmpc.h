@@ -393,6 +393,76 @@ int alore_nmpc_closed_loop_tick(alore_nmpc_handle h, const alore_nmpc_batch *dev
 int alore_nmpc_closed_loop_run(alore_nmpc_handle h, const alore_nmpc_batch *dev, int B, double t0, double dt_tick,
                                int n_ticks, int delay_num, void *stream);
 
+/* ---- the ICR EKF on the device, and the closed loop on its estimate ------------------------------------------------
+ * The reference's controllers do not read the true pose: ~odom is /ICREKF/EKF_XYTheta and the od of every stage is
+ * ~EKF_ICR (planner_sim.launch:118, 186-214; nmpc_controller/src/mpc.cpp:124-128, 305-310).  This is that node
+ * (planning_ddr_opt/icrekf/src/icrekf.cpp) for B robots: an extended Kalman filter over x = (X, Y, psi, yr, yl, xv) that
+ * forecasts with the wheel speeds of /simulation/ControlPub (left, right) and is corrected by the poses of
+ * /simulation/PoseOdomPub.  The arithmetic, its order, the statuses and the deviations from the reference are stated once,
+ * in csrc/icr_ekf.h; the kernels run that header.  A robot whose step fails (status < 0) keeps x, P and the held wheel speeds
+ * exactly as they were; a robot with mask[b] == 0 gets status 1 and nothing else.
+ * Ownership and ordering: alore_nmpc_ekf_init allocates everything once, for the robot capacity of alore_nmpc_refs_init
+ * (call that first); nothing is allocated later and alore_nmpc_destroy frees it.  ekf_step, ekf_closed_loop_tick and
+ * ekf_closed_loop_run only enqueue on `stream` and return: nothing crosses the bus but the arguments, and device buffers
+ * handed in must stay alive and unchanged until the stream has passed the call.  ekf_reset and ekf_set_state copy from HOST
+ * pointers and return when the host buffers may go; ekf_get synchronises the device.  Calls on one handle are ordered by
+ * the stream they are given; use one stream, or order them yourself. */
+#define ALORE_EKF_OK 0
+#define ALORE_EKF_MASKED 1
+#define ALORE_EKF_E_DEGENERATE (-1) /* yl == yr in the estimate, or a non-finite input */
+#define ALORE_EKF_E_NONFINITE (-2)  /* an output would not be finite */
+#define ALORE_EKF_E_SINGULAR (-3)   /* det S of the update is not a finite positive number */
+#define ALORE_EKF_E_MEAS (-4)       /* the measured pose is not finite, or more than 64 turns from the estimate's heading */
+typedef struct alore_ekf_params {
+    double q[6];        /* standard deviations of the process noise: Q_x, Q_y, Q_psi, Q_yr, Q_yl, Q_xv */
+    double r[3];        /* ... of the measurement: R_x, R_y, R_psi */
+    double init_icr[3]; /* (yr, yl, xv) a reset starts from: init_x_yr, init_x_yl, init_x_xv */
+    double standard[3]; /* (yr, yl, xv) the convergence flags compare the estimate with: *_standard */
+    int odom_every;     /* closed loop: a pose update on every odom_every-th tick since the reset */
+} alore_ekf_params;
+/* planner_sim.launch:186-206: q = 0.5, 0.5, 1.14, 0.1, 0.1, 0.1; r = 0.1, 0.1, 0.1; init_icr = -0.25, 0.25, 0.1; standard =
+ * -0.3, 0.3, 0.2 (:41-43); odom_every = 10 (Pose_odom_pub_rate 10 Hz against the 100 Hz ControlPub, :99-100) */
+void alore_nmpc_ekf_default_params(alore_ekf_params *p);
+int alore_nmpc_ekf_init(alore_nmpc_handle h, const alore_ekf_params *params);
+/* x <- (pose, icr0), P <- 0, held wheel speeds <- 0, flags cleared, status 0, for every robot with mask[b] != 0 (NULL = all):
+ * the state after the reference's first two messages (icrekf.cpp:45-55, 79-85).  pose [B][3] (NULL: the plant's pose, on the
+ * device), icr0 [B][3] as (yr, yl, xv) (NULL: init_icr), mask [B]: HOST pointers.  The tick count of the closed loop restarts. */
+int alore_nmpc_ekf_reset(alore_nmpc_handle h, int B, const double *pose, const double *icr0, const unsigned char *mask, void *stream);
+/* overwrite parts of the filter state (restoring a saved filter, tests): x [B][6], P [B][36], u [B][2] as (vl, vr); HOST
+ * pointers, any may be NULL (left as it is) */
+int alore_nmpc_ekf_set_state(alore_nmpc_handle h, int B, const double *x, const double *P, const double *u, void *stream);
+/* one step of the stand-alone filter: forecast over dt with the held wheel speeds, hold d_wheel [B][2] = (left, right), update
+ * with d_meas [B][3] (NULL: no update), convergence flags.  DEVICE pointers; d_mask [B] bytes or NULL.  Asynchronous. */
+int alore_nmpc_ekf_step(alore_nmpc_handle h, int B, const double *d_wheel, double dt, const double *d_meas,
+                        const unsigned char *d_mask, void *stream);
+/* x [B][6], P [B][36], status [B], conv_step [B][3] (the step at which yr, yl, xv were first flagged converged, -1 before):
+ * HOST pointers, any may be NULL.  Synchronises the device. */
+int alore_nmpc_ekf_get(alore_nmpc_handle h, int B, double *x, double *P, int *status, int *conv_step);
+typedef struct alore_ekf_view { /* device pointers, valid until alore_nmpc_destroy */
+    double *x;        /* [capacity][6] */
+    double *P;        /* [capacity][36] */
+    double *est_pose; /* [capacity][3]: (X, Y, psi), what EKF_XYTheta carries */
+    double *est_icr;  /* [capacity][3]: (xv, yr, yl), EKF_ICR in the controller's order */
+    int *status;      /* [capacity] */
+} alore_ekf_view;
+int alore_nmpc_ekf_device(alore_nmpc_handle h, alore_ekf_view *out);
+/* One period of the reference system with the filter in it, at most three launches, no host synchronisation:
+ *   1. references, x0 and od from the ESTIMATE (est_pose, est_icr; smooth_yaw on),
+ *   2. one real-time iteration (alore_nmpc_rti),
+ *   3. the plant step of alore_nmpc_closed_loop_tick on the TRUE state (alore_nmpc_plant_set_state), the simulator's ControlPub
+ *      message from its result (left = v - omega yl, right = v - omega yr with the true ICR, simulator.h:342-347), and the
+ *      filter step over dt_tick with that message -- with an update, on every odom_every-th tick since the reset, by the true
+ *      pose plus d_noise [B][3] (DEVICE pointer the caller fills; NULL: none).
+ * Needs plant_init and ekf_init; alore_nmpc_closed_loop_reset is used unchanged (after ekf_reset with pose = NULL estimate and
+ * truth coincide).  The handle counts the ticks. */
+int alore_nmpc_ekf_closed_loop_tick(alore_nmpc_handle h, const alore_nmpc_batch *dev, int B, double now, double dt_tick,
+                                    int delay_num, const double *d_noise, void *stream);
+/* n_ticks of them at t0, t0 + dt_tick, ... back to back; d_noise [updates][B][3], one slice per update that falls into the run
+ * (NULL: none).  The results are exactly those of n_ticks calls of the tick.  (The one-launch-per-tick fusion of
+ * alore_nmpc_closed_loop_run lives in the solver's grid and is deliberately not extended to this loop.) */
+int alore_nmpc_ekf_closed_loop_run(alore_nmpc_handle h, const alore_nmpc_batch *dev, int B, double t0, double dt_tick,
+                                   int n_ticks, int delay_num, const double *d_noise, void *stream);
+
 /* ---- introspection ------------------------------------------------------- */
 typedef struct {
     int lanes_per_problem;  /* of the last alore_nmpc_rti launch */
