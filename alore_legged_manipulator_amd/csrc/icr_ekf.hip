@@ -3,40 +3,11 @@
 // One thread per robot: the 6 x 6 covariance, the state and the flags of a robot live in that thread's registers from the load to
 // the store; no LDS, no scratch (registers: profiles/icr_ekf.txt).  The arithmetic is the header's, nothing is restated here.
 #include "nmpc_solver.h" // (before icr_ekf.h: that header switches contraction off for what follows it)
-#include "icr_ekf.h"
+#include "icr_ekf_device.h" // icr_ekf.h, icrekf::Dev and step_robot: load -> step_one -> store for one robot
 
 using namespace nmpc_capi;
 
 namespace icrekf {
-
-struct Dev { // the filter's device arrays, [capacity] robots each
-    double *x, *P, *u, *est_pose, *est_icr;
-    Flags* f;
-    int* status;
-};
-
-// load -> step_one -> store for robot r; wheel and z (read when has_z) in registers of the caller
-__device__ __forceinline__ void step_robot(const Dev& d, const Params& p, int r, const double* wheel, double dt, const double* z, bool has_z)
-{
-    double x[6], P[36], u[2];
-    const double2* gx = reinterpret_cast<const double2*>(d.x + (size_t)r * 6);   // 48-, 288- and 16-byte records: 16-byte aligned
-    const double2* gP = reinterpret_cast<const double2*>(d.P + (size_t)r * 36);
-    IE_UNROLL for (int i = 0; i < 3; ++i) { const double2 v = gx[i]; x[2 * i] = v.x; x[2 * i + 1] = v.y; }
-    IE_UNROLL for (int i = 0; i < 18; ++i) { const double2 v = gP[i]; P[2 * i] = v.x; P[2 * i + 1] = v.y; }
-    { const double2 v = *reinterpret_cast<const double2*>(d.u + (size_t)r * 2); u[0] = v.x; u[1] = v.y; }
-    Flags f = d.f[r];
-    const int st = step_one(p, x, P, u, f, wheel, dt, z, has_z, nullptr);
-    d.status[r] = st;
-    if (st != OK) return; // x, P, u, flags and the published estimate stay exactly as they were
-    double2* sx = reinterpret_cast<double2*>(d.x + (size_t)r * 6);
-    double2* sP = reinterpret_cast<double2*>(d.P + (size_t)r * 36);
-    IE_UNROLL for (int i = 0; i < 3; ++i) sx[i] = make_double2(x[2 * i], x[2 * i + 1]);
-    IE_UNROLL for (int i = 0; i < 18; ++i) sP[i] = make_double2(P[2 * i], P[2 * i + 1]);
-    *reinterpret_cast<double2*>(d.u + (size_t)r * 2) = make_double2(u[0], u[1]);
-    d.f[r] = f;
-    d.est_pose[(size_t)r * 3] = x[0]; d.est_pose[(size_t)r * 3 + 1] = x[1]; d.est_pose[(size_t)r * 3 + 2] = x[2];
-    d.est_icr[(size_t)r * 3] = x[5]; d.est_icr[(size_t)r * 3 + 1] = x[3]; d.est_icr[(size_t)r * 3 + 2] = x[4]; // (xv, yr, yl)
-}
 
 // forecast with the held u over dt, u <- wheel, update where meas is given, flags
 __global__ void __launch_bounds__(64) step_kernel(Dev d, Params p, int B, const double* wheel, double dt, const double* meas,
@@ -277,6 +248,20 @@ int alore_nmpc_ekf_closed_loop_run(alore_nmpc_handle h, const alore_nmpc_batch* 
         if (upd) ++updates;
     }
     return ALORE_NMPC_OK;
+}
+
+// internal (not in the public header): the filter of a handle, for the LTV-MPC closed loop on its estimate (ltv_mpc_capi.hip)
+int alore_nmpc_internal_ekf(void* nmpc_handle, icrekf::Access* out)
+{
+    alore_nmpc_handle h = static_cast<alore_nmpc_handle>(nmpc_handle);
+    if (!h || !h->ekf.d_block || !out) return -1;
+    out->d = ekf_layout(h->ekf.d_block, h->ekf.B).d;
+    out->p = ekf_params(h->ekf.params);
+    out->odom_every = h->ekf.params.odom_every;
+    out->ticks = &h->ekf.ticks;
+    out->capacity = h->ekf.B;
+    out->device = h->cfg.device;
+    return 0;
 }
 
 } // extern "C"

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "ltv_ekf_loop.h"
 #include "ltv_mpc.h"
 #include "ltv_plant.h"
 #include "minco_spline.h"
@@ -234,6 +235,13 @@ struct alore_ltv_solver {
     long long trace_total = 0;          // plant steps recorded since the trace was emptied
     double* d_tr_pose = nullptr;        // per tick of the ring: pose [B][3], then cmd [B][2]
     int* d_tr_status = nullptr;         // per tick of the ring: status [B], then at_goal [B]
+    // the loop on the ICR EKF's estimate (alore_ltv_ekf_closed_loop_run and its pieces, kernels in ltv_ekf_loop.hip)
+    double* d_icr = nullptr;            // [B][3] the true (xv, yr, yl), for the ControlPub message
+    double noise_stddev = 0.0, meas_stddev[3] = {0.0, 0.0, 0.0};
+    unsigned long long noise_seed = 0;
+    unsigned long long noise_event = 0; // plant + filter steps since alore_ltv_plant_set_noise / _set_state
+    double* d_tr_est = nullptr;         // per tick of the ring: est [B][3]
+    int* d_tr_ekf = nullptr;            // per tick of the ring: the filter's status [B]
 };
 
 namespace {
@@ -256,11 +264,12 @@ hipError_t zalloc(T** p, size_t n)
 }
 void plant_free(alore_ltv_handle h)
 {
-    void* ptrs[] = {h->d_pose, h->d_tr_pose, h->d_tr_status};
+    void* ptrs[] = {h->d_pose, h->d_tr_pose, h->d_tr_status, h->d_icr, h->d_tr_est, h->d_tr_ekf};
     for (void* p : ptrs) if (p) (void)hipFree(p);
-    h->d_pose = h->d_vw = h->d_des = h->d_tr_pose = nullptr;
-    h->d_tr_status = nullptr;
+    h->d_pose = h->d_vw = h->d_des = h->d_tr_pose = h->d_icr = h->d_tr_est = nullptr;
+    h->d_tr_status = h->d_tr_ekf = nullptr;
     h->plant_ready = false; h->trace_cap = 0; h->trace_total = 0; h->plant_meta = nullptr;
+    h->noise_stddev = 0.0; h->meas_stddev[0] = h->meas_stddev[1] = h->meas_stddev[2] = 0.0; h->noise_seed = 0; h->noise_event = 0;
 }
 void lfree(alore_ltv_handle h)
 {
@@ -581,6 +590,13 @@ int alore_ltv_plant_init(alore_ltv_handle h, const alore_ltv_plant_params* p, in
     auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
     A(zalloc(&h->d_pose, B * 7));
     if (M > 0) { A(zalloc(&h->d_tr_pose, M * B * 5)); A(zalloc(&h->d_tr_status, M * B * 2)); }
+    A(zalloc(&h->d_icr, B * 3));
+    if (M > 0) { A(zalloc(&h->d_tr_est, M * B * 3)); A(zalloc(&h->d_tr_ekf, M * B)); }
+    if (e == hipSuccess) { // the true ICR of planner_sim.launch:41-43 as (xv, yr, yl)
+        std::vector<double> icr(B * 3);
+        for (size_t b = 0; b < B; ++b) { icr[b * 3] = 0.2; icr[b * 3 + 1] = -0.3; icr[b * 3 + 2] = 0.3; }
+        e = hipMemcpy(h->d_icr, icr.data(), sizeof(double) * B * 3, hipMemcpyHostToDevice);
+    }
     if (e == hipSuccess) { h->d_vw = h->d_pose + B * 3; h->d_des = h->d_pose + B * 5; }
     if (e != hipSuccess) { plant_free(h); return lfail(h, e == hipErrorOutOfMemory ? ALORE_LTV_E_NOMEM : ALORE_LTV_E_HIP, "plant_init: allocation", e); }
     h->plant = *p;
@@ -634,6 +650,7 @@ int alore_ltv_plant_set_state(alore_ltv_handle h, int B, const double* pose, con
     LTV_TRY(h, hipMemcpyAsync(h->d_des, sd, sizeof(double) * B * 2, hipMemcpyHostToDevice, s));
     LTV_TRY(h, hipStreamSynchronize(s)); // the slab is reused
     h->trace_total = 0;
+    h->noise_event = 0;
     return ALORE_LTV_OK;
 }
 
@@ -699,11 +716,12 @@ hipError_t enq_pre_tick(alore_ltv_handle h, const nmpc::RefStore& rs, int B, dou
     hipLaunchKernelGGL(ltv::pre_tick_kernel, dim3(B), dim3(64), 0, s, a);
     return hipGetLastError();
 }
-hipError_t enq_solve(alore_ltv_handle h, int B, int n_relin, double du_th, int reset, hipStream_t s)
+// now: the states [B][3] the solve starts from, on the device; null: the plant's pose
+hipError_t enq_solve(alore_ltv_handle h, int B, int n_relin, double du_th, int reset, hipStream_t s, const double* now = nullptr)
 {
     ltv::DevConv d{};
     d.c = h->cfg; d.B = B; d.stride = h->B;
-    d.now = h->d_pose;
+    d.now = now ? now : h->d_pose;
     d.xref = h->d_xref; d.dref = h->d_dref; d.output = h->d_out; d.buff = h->d_buff; d.xopt = h->d_xopt;
     d.ws = h->d_ws; d.st = h->d_st; d.sweeps = h->d_sweeps; d.status = h->d_status; d.cmd = h->d_cmd;
     d.n_relin = n_relin; d.reset = reset;
@@ -718,6 +736,38 @@ hipError_t enq_plant(alore_ltv_handle h, int B, hipStream_t s)
     const ltv::PreTick a = tick_args(h, B, true);
     hipLaunchKernelGGL(ltv::plant_step_kernel, dim3((B + 63) / 64), dim3(64), 0, s, a);
     return hipGetLastError();
+}
+// ---- the pieces of the loop on the ICR EKF's estimate
+// getRefPoints + smooth_yaw against est_pose: pre_tick_kernel without its plant step reads nothing of `pose` but the heading
+hipError_t enq_refs_est(alore_ltv_handle h, const nmpc::RefStore& rs, int B, double now, const double* est_pose, hipStream_t s)
+{
+    h->plant_meta = rs.meta;
+    ltv::PreTick a = tick_args(h, B, false);
+    a.s = rs; a.now = now; a.do_plant = 0;
+    a.pose = const_cast<double*>(est_pose);
+    hipLaunchKernelGGL(ltv::pre_tick_kernel, dim3(B), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+// plant on the true state, ControlPub, filter step, trace record (ltv::plant_ekf_kernel); takes the next slot of the trace ring,
+// the next noise event and the next tick of the filter's count
+hipError_t enq_plant_ekf(alore_ltv_handle h, void* nmpc, const ltv::EkfInfo& ei, int B, double dt_tick, hipStream_t s)
+{
+    const ltv::PreTick t = tick_args(h, B, true);
+    ltv::PlantEkf a{};
+    a.p = h->plant; a.meta = h->plant_meta; a.B = B; a.stride = h->B;
+    a.goal = h->d_goal; a.pose = h->d_pose; a.cmd = h->d_cmd; a.status = h->d_status; a.icr = h->d_icr;
+    a.tr_pose = t.tr_pose; a.tr_status = t.tr_status;
+    if (t.tr_pose) {
+        const size_t slot = (size_t)((h->trace_total - 1) % h->trace_cap) * h->B;
+        a.tr_est = h->d_tr_est + slot * 3; a.tr_ekf_status = h->d_tr_ekf + slot;
+    }
+    a.dt = dt_tick;
+    *ei.ticks += 1;
+    a.do_update = (*ei.ticks % ei.odom_every == 0) ? 1 : 0;
+    a.noise_stddev = h->noise_stddev;
+    for (int i = 0; i < 3; ++i) a.meas_stddev[i] = h->meas_stddev[i];
+    a.seed = h->noise_seed; a.event = h->noise_event++;
+    return ltv::launch_plant_ekf(a, nmpc, s);
 }
 } // namespace
 
@@ -804,6 +854,152 @@ int alore_ltv_plant_get_trace(alore_ltv_handle h, int B, int max_ticks, double* 
         if (cmd) LTV_TRY(h, hipMemcpy2DAsync(cmd + (size_t)done * B * 2, sizeof(double) * B * 2, td + HB * 3, sizeof(double) * HB * 5, sizeof(double) * B * 2, rows, hipMemcpyDeviceToHost, s));
         if (status) LTV_TRY(h, hipMemcpy2DAsync(status + (size_t)done * B, sizeof(int) * B, ti, sizeof(int) * HB * 2, sizeof(int) * B, rows, hipMemcpyDeviceToHost, s));
         if (at_goal) LTV_TRY(h, hipMemcpy2DAsync(at_goal + (size_t)done * B, sizeof(int) * B, ti + HB, sizeof(int) * HB * 2, sizeof(int) * B, rows, hipMemcpyDeviceToHost, s));
+        done += (long long)rows;
+    }
+    LTV_TRY(h, hipStreamSynchronize(s));
+    return ALORE_LTV_OK;
+}
+
+// ---- the closed loop on the ICR EKF's estimate
+
+// the filter of the NMPC handle: there, large enough, on this device; null: fine
+static const char* ekf_bad(alore_ltv_handle h, void* nmpc, int B, ltv::EkfInfo* ei)
+{
+    if (!ltv::ekf_info(nmpc, ei)) return "no NMPC handle on which alore_nmpc_ekf_init has been called";
+    if (ei->capacity < B || ei->device != h->device) return "the NMPC handle's filter is too small for B robots or on another device";
+    return nullptr;
+}
+
+int alore_ltv_plant_set_icr(alore_ltv_handle h, int B, const double* icr, void* stream)
+{
+    if (!h) return ALORE_LTV_E_INVALID;
+    LTV_ARGS(h, "plant_set_icr", plant_args_bad(h, B));
+    if (!icr) return lfail(h, ALORE_LTV_E_INVALID, "plant_set_icr: icr is null");
+    for (int b = 0; b < B; ++b) {
+        const double* c = icr + (size_t)b * 3;
+        if (!std::isfinite(c[0]) || !std::isfinite(c[1]) || !std::isfinite(c[2]) || c[1] == c[2])
+            return lfail(h, ALORE_LTV_E_INVALID, "plant_set_icr: every (xv, yr, yl) must be finite with yl != yr");
+    }
+    LTV_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    double* sp = (double*)h->h_stage;
+    std::memcpy(sp, icr, sizeof(double) * B * 3);
+    LTV_TRY(h, hipMemcpyAsync(h->d_icr, sp, sizeof(double) * B * 3, hipMemcpyHostToDevice, s));
+    LTV_TRY(h, hipStreamSynchronize(s)); // the slab is reused
+    return ALORE_LTV_OK;
+}
+
+int alore_ltv_plant_set_noise(alore_ltv_handle h, double noise_stddev, const double* meas_stddev, unsigned long long seed)
+{
+    if (!h) return ALORE_LTV_E_INVALID;
+    if (!h->plant_ready) return lfail(h, ALORE_LTV_E_INVALID, "plant_set_noise: alore_ltv_plant_init has not been called");
+    bool ok = std::isfinite(noise_stddev) && noise_stddev >= 0.0;
+    for (int i = 0; meas_stddev && i < 3; ++i) ok = ok && std::isfinite(meas_stddev[i]) && meas_stddev[i] >= 0.0;
+    if (!ok) return lfail(h, ALORE_LTV_E_INVALID, "plant_set_noise: a standard deviation is negative or not finite");
+    h->noise_stddev = noise_stddev;
+    for (int i = 0; i < 3; ++i) h->meas_stddev[i] = meas_stddev ? meas_stddev[i] : 0.0;
+    h->noise_seed = seed;
+    h->noise_event = 0;
+    return ALORE_LTV_OK;
+}
+
+int alore_ltv_plant_noise_draws(alore_ltv_handle h, int B, unsigned long long event0, int n_events, int noise_stream, double* out, void* stream)
+{
+    if (!h) return ALORE_LTV_E_INVALID;
+    LTV_ARGS(h, "plant_noise_draws", plant_args_bad(h, B));
+    if (n_events < 1 || (long long)n_events * B > (1ll << 24) || noise_stream < 0 || noise_stream > 2 || !out)
+        return lfail(h, ALORE_LTV_E_INVALID, "plant_noise_draws: n_events >= 1, at most 2^24 draws, noise_stream 0..2, out not null");
+    LTV_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = (size_t)n_events * B * 2;
+    double* d = nullptr;
+    LTV_TRY(h, hipMalloc((void**)&d, sizeof(double) * n));
+    hipError_t e = ltv::launch_noise_draws(h->noise_seed, B, event0, n_events, noise_stream, d, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d, sizeof(double) * n, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(d);
+    if (e != hipSuccess) return lfail(h, ALORE_LTV_E_HIP, "plant_noise_draws", e);
+    return ALORE_LTV_OK;
+}
+
+int alore_ltv_refs_from_store_est(alore_ltv_handle h, void* nmpc, int B, double now, void* stream)
+{
+    if (!h) return ALORE_LTV_E_INVALID;
+    nmpc::RefStore rs;
+    ltv::EkfInfo ei;
+    LTV_ARGS(h, "refs_from_store_est", plant_args_bad(h, B));
+    if (!std::isfinite(now)) return lfail(h, ALORE_LTV_E_INVALID, "refs_from_store_est: now is not finite");
+    LTV_ARGS(h, "refs_from_store_est", store_bad(h, nmpc, B, &rs));
+    LTV_ARGS(h, "refs_from_store_est", ekf_bad(h, nmpc, B, &ei));
+    LTV_TRY(h, hipSetDevice(h->device));
+    LTV_TRY(h, enq_refs_est(h, rs, B, now, ei.est_pose, (hipStream_t)stream));
+    return ALORE_LTV_OK;
+}
+
+int alore_ltv_get_cmd_est(alore_ltv_handle h, void* nmpc, int B, int n_relin, double du_th, int reset, void* stream)
+{
+    if (!h) return ALORE_LTV_E_INVALID;
+    ltv::EkfInfo ei;
+    LTV_ARGS(h, "get_cmd_est", plant_args_bad(h, B));
+    LTV_ARGS(h, "get_cmd_est", solve_args_bad(n_relin, du_th));
+    LTV_ARGS(h, "get_cmd_est", ekf_bad(h, nmpc, B, &ei));
+    LTV_TRY(h, hipSetDevice(h->device));
+    LTV_TRY(h, enq_solve(h, B, n_relin, du_th, reset ? 1 : 0, (hipStream_t)stream, ei.est_pose));
+    return ALORE_LTV_OK;
+}
+
+int alore_ltv_plant_ekf_step(alore_ltv_handle h, void* nmpc, int B, double dt_tick, void* stream)
+{
+    if (!h) return ALORE_LTV_E_INVALID;
+    ltv::EkfInfo ei;
+    LTV_ARGS(h, "plant_ekf_step", plant_args_bad(h, B));
+    if (!std::isfinite(dt_tick) || !(dt_tick > 0.0)) return lfail(h, ALORE_LTV_E_INVALID, "plant_ekf_step: dt_tick must be finite and positive");
+    LTV_ARGS(h, "plant_ekf_step", ekf_bad(h, nmpc, B, &ei));
+    LTV_TRY(h, hipSetDevice(h->device));
+    LTV_TRY(h, enq_plant_ekf(h, nmpc, ei, B, dt_tick, (hipStream_t)stream));
+    return ALORE_LTV_OK;
+}
+
+int alore_ltv_ekf_closed_loop_run(alore_ltv_handle h, void* nmpc, int B, double t0, double dt_tick, int n_ticks, int n_relin, double du_th,
+                                  int reset, void* stream)
+{
+    if (!h) return ALORE_LTV_E_INVALID;
+    nmpc::RefStore rs;
+    ltv::EkfInfo ei;
+    LTV_ARGS(h, "ekf_closed_loop_run", plant_args_bad(h, B));
+    if (n_ticks < 1) return lfail(h, ALORE_LTV_E_INVALID, "ekf_closed_loop_run: n_ticks must be at least 1");
+    if (!std::isfinite(t0) || !std::isfinite(dt_tick) || !(dt_tick > 0.0))
+        return lfail(h, ALORE_LTV_E_INVALID, "ekf_closed_loop_run: t0 must be finite, dt_tick finite and positive");
+    LTV_ARGS(h, "ekf_closed_loop_run", solve_args_bad(n_relin, du_th));
+    LTV_ARGS(h, "ekf_closed_loop_run", store_bad(h, nmpc, B, &rs));
+    LTV_ARGS(h, "ekf_closed_loop_run", ekf_bad(h, nmpc, B, &ei));
+    LTV_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    for (int k = 0; k < n_ticks; ++k) {
+        if (k > 0) LTV_TRY(h, enq_plant_ekf(h, nmpc, ei, B, dt_tick, s));
+        LTV_TRY(h, enq_refs_est(h, rs, B, t0 + k * dt_tick, ei.est_pose, s));
+        LTV_TRY(h, enq_solve(h, B, n_relin, du_th, (k == 0 && reset) ? 1 : 0, s, ei.est_pose));
+    }
+    LTV_TRY(h, enq_plant_ekf(h, nmpc, ei, B, dt_tick, s));
+    return ALORE_LTV_OK;
+}
+
+int alore_ltv_plant_get_trace_est(alore_ltv_handle h, int B, int max_ticks, double* est, int* ekf_status, int* n_ticks_out, void* stream)
+{
+    if (!h) return ALORE_LTV_E_INVALID;
+    LTV_ARGS(h, "plant_get_trace_est", plant_args_bad(h, B));
+    if (max_ticks < 0 || !n_ticks_out) return lfail(h, ALORE_LTV_E_INVALID, "plant_get_trace_est: bad argument");
+    LTV_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    long long n = h->trace_total < h->trace_cap ? h->trace_total : h->trace_cap;
+    if (n > max_ticks) n = max_ticks;
+    *n_ticks_out = (int)n;
+    const size_t HB = h->B, cap = h->trace_cap; // as alore_ltv_plant_get_trace walks the ring
+    for (long long done = 0; done < n;) {
+        const size_t slot = (size_t)((h->trace_total - n + done) % (long long)cap);
+        const size_t rows = std::min<size_t>(cap - slot, (size_t)(n - done));
+        if (est) LTV_TRY(h, hipMemcpy2DAsync(est + (size_t)done * B * 3, sizeof(double) * B * 3, h->d_tr_est + slot * HB * 3, sizeof(double) * HB * 3, sizeof(double) * B * 3, rows, hipMemcpyDeviceToHost, s));
+        if (ekf_status) LTV_TRY(h, hipMemcpy2DAsync(ekf_status + (size_t)done * B, sizeof(int) * B, h->d_tr_ekf + slot * HB, sizeof(int) * HB, sizeof(int) * B, rows, hipMemcpyDeviceToHost, s));
         done += (long long)rows;
     }
     LTV_TRY(h, hipStreamSynchronize(s));

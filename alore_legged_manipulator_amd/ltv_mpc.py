@@ -56,6 +56,16 @@ def _bind(L):
     L.alore_ltv_plant_step.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.alore_ltv_closed_loop_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p]
     L.alore_ltv_plant_get_trace.argtypes = [C.c_void_p, C.c_int, C.c_int, DP, DP, IP, IP, IP, C.c_void_p]
+    # the closed loop on the ICR EKF's estimate, with the simulator's noise
+    L.alore_ltv_plant_set_icr.argtypes = [C.c_void_p, C.c_int, DP, C.c_void_p]
+    L.alore_ltv_plant_set_noise.argtypes = [C.c_void_p, C.c_double, DP, C.c_ulonglong]
+    L.alore_ltv_plant_noise_draws.argtypes = [C.c_void_p, C.c_int, C.c_ulonglong, C.c_int, C.c_int, DP, C.c_void_p]
+    L.alore_ltv_refs_from_store_est.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]
+    L.alore_ltv_get_cmd_est.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p]
+    L.alore_ltv_plant_ekf_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]
+    L.alore_ltv_ekf_closed_loop_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int,
+                                                C.c_void_p]
+    L.alore_ltv_plant_get_trace_est.argtypes = [C.c_void_p, C.c_int, C.c_int, DP, IP, IP, C.c_void_p]
     L._ltv_bound = True
 
 
@@ -224,6 +234,55 @@ class BatchedLtvMpc:
                                                      C.byref(k), None))
         k = k.value
         return {"pose": pose[:k], "cmd": cmd[:k], "status": st[:k], "at_goal": goal[:k]}
+
+    # ---- the loop planner_sim.launch runs: the plant with the simulator's noise, the ICR EKF of `nmpc_engine` (the BatchedNmpc
+    # that holds the trajectory store: ekf_init / ekf_reset / ekf_get there), sampling and the solve on the filter's estimate
+    def plant_set_icr(self, icr):
+        """the true (xv, yr, yl) per robot, (n, 3): what the simulator's ControlPub message is formed with"""
+        icr = np.ascontiguousarray(icr, np.float64)
+        self._check(self.L.alore_ltv_plant_set_icr(self.h, icr.shape[0], _dp(icr), None))
+
+    def plant_set_noise(self, noise_stddev=0.0, meas_stddev=None, seed=0):
+        """noise_stddev: the simulator's multiplicative noise on (v, omega) of every PoseSub (the launch file: 0.01); meas_stddev
+        (3,): noise on the pose that updates the filter; seed: draws are a pure function of (seed, robot, event, stream).
+        Restarts the event count."""
+        m = None if meas_stddev is None else np.ascontiguousarray(meas_stddev, np.float64).reshape(3)
+        self._check(self.L.alore_ltv_plant_set_noise(self.h, float(noise_stddev), _dp(m), int(seed) & (2 ** 64 - 1)))
+
+    def plant_noise_draws(self, event0, n_events, stream=0, n=None):
+        """the standard normals (n_events, n, 2) of the handle's seed for events event0 ..., drawn on the device.  Synchronises."""
+        n = self._n if n is None else n
+        out = np.zeros((max(int(n_events), 0), max(n, 0), 2))
+        self._check(self.L.alore_ltv_plant_noise_draws(self.h, n, int(event0), int(n_events), int(stream), _dp(out), None))
+        return out
+
+    def refs_from_store_est(self, nmpc_engine, now, n=None):
+        n = self._n if n is None else n
+        self._check(self.L.alore_ltv_refs_from_store_est(self.h, nmpc_engine.h, n, float(now), None))
+
+    def get_cmd_est(self, nmpc_engine, n_relin=5, du_th=None, reset=False, n=None):
+        n = self._n if n is None else n
+        self._check(self.L.alore_ltv_get_cmd_est(self.h, nmpc_engine.h, n, int(n_relin), self._du(du_th), 1 if reset else 0, None))
+
+    def plant_ekf_step(self, nmpc_engine, dt_tick=0.01, n=None):
+        """plant on the true state (noisy PoseSub), ControlPub, the filter step, the trace record: one launch"""
+        n = self._n if n is None else n
+        self._check(self.L.alore_ltv_plant_ekf_step(self.h, nmpc_engine.h, n, float(dt_tick), None))
+
+    def ekf_closed_loop_run(self, nmpc_engine, t0, dt_tick, n_ticks, n_relin=5, du_th=None, reset=False, n=None):
+        """n_ticks control periods of the loop on the estimate, enqueued back to back; returns without waiting"""
+        n = self._n if n is None else n
+        self._check(self.L.alore_ltv_ekf_closed_loop_run(self.h, nmpc_engine.h, n, float(t0), float(dt_tick), int(n_ticks), int(n_relin),
+                                                         self._du(du_th), 1 if reset else 0, None))
+
+    def plant_trace_est(self, max_ticks, n=None):
+        """per tick of plant_trace: est (k, n, 3), the estimate after the filter step; ekf_status (k, n).  Synchronises."""
+        n = self._n if n is None else n
+        m = max(int(max_ticks), 0)
+        est = np.zeros((m, max(n, 0), 3)); st = np.zeros((m, max(n, 0)), np.int32)
+        k = C.c_int(0)
+        self._check(self.L.alore_ltv_plant_get_trace_est(self.h, n, m, _dp(est), st.ctypes.data_as(IP), C.byref(k), None))
+        return {"est": est[:k.value], "ekf_status": st[:k.value]}
 
     def results(self, n=None):
         """alore_ltv_results: the stored output, xopt, sweeps and status as they lie on the device.  Synchronises."""

@@ -156,6 +156,51 @@ int alore_ltv_closed_loop_run(alore_ltv_handle h, void *nmpc, int B, double t0, 
  * than B robots leaves the records of the others as they were.  Synchronises. */
 int alore_ltv_plant_get_trace(alore_ltv_handle h, int B, int max_ticks, double *pose, double *cmd, int *status, int *at_goal, int *n_ticks_out, void *stream);
 
+/* ---- The loop planner_sim.launch runs, on the device: the `mpc` node takes its ~odom from the ICR EKF (/ICREKF/EKF_XYTheta,
+ * :118), the filter is fed by the simulator's ControlPub and PoseOdomPub (:186-214), and the simulator perturbs the velocities
+ * of every PoseSub (if_add_noise, noise_stddev = 0.01, :96-97).  The filter is the one of the NMPC handle passed as `nmpc`, the
+ * handle that holds the trajectory store: alore_nmpc_ekf_init / _reset / _get / _set_state / _device (include/alore_nmpc.h)
+ * prepare and read it; its state exists once.  Sampling, smooth_yaw and the solve read the ESTIMATE (est_pose); the plant moves
+ * the TRUE state.  With the options below at their defaults the calls above leave the bits they always left.
+ * Noise draws are counter-based (csrc/sim_noise.h): a pure function of (seed, robot, event, stream), event = the plant + filter
+ * steps since the last alore_ltv_plant_set_noise / _set_state.  They do not depend on B or on how a run is cut into calls. */
+/* the true ICR (xv, yr, yl) of each robot, HOST [B][3], used for the ControlPub message only: the plant of this loop keeps vy = 0
+ * (nothing publishes ControlSub in that launch file).  After plant_init: (0.2, -0.3, 0.3) (planner_sim.launch:41-43).
+ * yl == yr or a value that is not finite: ALORE_LTV_E_INVALID, nothing changed.  Synchronises. */
+int alore_ltv_plant_set_icr(alore_ltv_handle h, int B, const double *icr, void *stream);
+/* noise_stddev: the simulator's multiplicative noise on (v, omega) of every PoseSub: v += (v noise_stddev) z0, omega likewise
+ * with z1 (simulator.h:222-229; the launch file's value is 0.01).  meas_stddev [3] (NULL: zeros): standard deviations of the noise
+ * added to the pose (x, y, theta) that updates the filter; the reference adds none, this replaces the caller-filled buffer of the
+ * NMPC loop.  After plant_init: all 0, seed 0.  A negative or non-finite value: ALORE_LTV_E_INVALID.  Resets the event counter;
+ * alore_ltv_plant_set_state resets it too. */
+int alore_ltv_plant_set_noise(alore_ltv_handle h, double noise_stddev, const double *meas_stddev, unsigned long long seed);
+/* the standard normals of the handle's seed: out HOST [n_events][B][2] = (z0, z1) of stream `noise_stream` (0: the velocity noise of v, omega;
+ * 1: the measurement noise of x, y; 2: z0 is the measurement noise of theta, z1 is not used) for events event0 .. event0 + n_events - 1, drawn on the device.
+ * Synchronises. */
+int alore_ltv_plant_noise_draws(alore_ltv_handle h, int B, unsigned long long event0, int n_events, int noise_stream, double *out,
+                                void *stream);
+/* the pieces, each asynchronous on `stream`, nothing crosses the bus */
+/* getRefPoints + smooth_yaw against the filter's est_pose */
+int alore_ltv_refs_from_store_est(alore_ltv_handle h, void *nmpc, int B, double now, void *stream);
+/* alore_ltv_get_cmd_device with now_state = est_pose */
+int alore_ltv_get_cmd_est(alore_ltv_handle h, void *nmpc, int B, int n_relin, double du_th, int reset, void *stream);
+/* one launch, one thread per robot: (1) the plant step on the TRUE state with the noisy PoseSub, (2) ControlPub = (v - omega yl,
+ * v - omega yr) from the true ICR and the velocities after the step (simulator.h:342-347), (3) the filter step over dt_tick with
+ * that message, (4) on every odom_every-th such step since alore_nmpc_ekf_reset an update by the true pose plus meas_stddev * z,
+ * (5) the trace record.  A robot whose filter step fails keeps its estimate and gets the filter's status; its plant moves on. */
+int alore_ltv_plant_ekf_step(alore_ltv_handle h, void *nmpc, int B, double dt_tick, void *stream);
+/* n_ticks control periods at now = t0 + k * dt_tick: per tick, without any synchronisation, plant + filter of the tick before (not
+ * on the first tick), sampling from the estimate, the solve; one plant + filter step closes the run -- three launches per tick.
+ * What a run leaves (plant, filter, trace, solver state) is bit for bit what the three pieces above leave, tick by tick, and
+ * what n calls of one tick leave.  ALORE_LTV_E_INVALID, with nothing enqueued: the cases of alore_ltv_closed_loop_run, no
+ * alore_nmpc_ekf_init on `nmpc`, a filter that is too small or on another device, dt_tick <= 0. */
+int alore_ltv_ekf_closed_loop_run(alore_ltv_handle h, void *nmpc, int B, double t0, double dt_tick, int n_ticks, int n_relin,
+                                  double du_th, int reset, void *stream);
+/* per tick of the ring, laid out and ordered as alore_ltv_plant_get_trace: est [ticks][B][3], the estimate after the filter step;
+ * ekf_status [ticks][B], the filter's status of that step.  alore_ltv_plant_step and alore_ltv_closed_loop_run (no filter) do not write
+ * their ticks' records here.  Either may be NULL.  Synchronises. */
+int alore_ltv_plant_get_trace_est(alore_ltv_handle h, int B, int max_ticks, double *est, int *ekf_status, int *n_ticks_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,168 @@
+"""csrc/sim_noise.h (Philox4x32-10, uniforms, Box-Muller) and ltv_plant::step_noisy (the simulator's noisy PoseSub) on the CPU
+against their oracle, tests/sim_noise_cases.py, and the build side of the feature: the calls of the closed loop on the ICR EKF's
+estimate are declared, exported and bound.
+
+tests/harness/sim_noise_check.cpp includes the headers, is compiled with g++ (once more with the address and undefined-behaviour
+sanitizers) as a stand-alone program and answers one request per line.  Words and uniforms are exact.  Normals: 1e-13 absolute
+(|z| <= sqrt(-2 ln 2^-53) < 8.6; the argument 2 pi u2 <= 6.3 carries one rounding of 9e-16, cos and sin are within about 1e-16, r
+within a few ulp: |dz| < 1e-14, with a tenfold margin).  The noisy step: 1e-12, as tests/test_ltv_plant_cpu.py derives it.
+
+The uniforms use 52 bits and a half, not the 53 the feature's first description had: (k + 0.5) with k up to 2^53 - 1 does not fit a
+double, and all-one words round to u = 1.0 (test_uniforms_..., uniform_53bit); with 52 bits every term is exact and u stays
+strictly inside (0, 1), which is the property asked for."""
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import ltv_plant_cases as plant
+from tests import sim_noise_cases as cases
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "alore_legged_manipulator_amd", "csrc")
+SRC = os.path.join(ROOT, "tests", "harness", "sim_noise_check.cpp")
+FLAGS = {"plain": ["-O2"], "asan_ubsan": ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]}
+CALLS = ("alore_ltv_plant_set_icr", "alore_ltv_plant_set_noise", "alore_ltv_plant_noise_draws", "alore_ltv_refs_from_store_est",
+         "alore_ltv_get_cmd_est", "alore_ltv_plant_ekf_step", "alore_ltv_ekf_closed_loop_run", "alore_ltv_plant_get_trace_est")
+METHODS = ("plant_set_icr", "plant_set_noise", "plant_noise_draws", "refs_from_store_est", "get_cmd_est", "plant_ekf_step",
+           "ekf_closed_loop_run", "plant_trace_est")
+
+
+@pytest.fixture(scope="module")
+def exes(tmp_path_factory):
+    d = tmp_path_factory.mktemp("sim_noise_check")
+    out = {}
+    for name, flags in FLAGS.items():
+        out[name] = str(d / name)
+        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", *flags, "-I", CSRC, SRC, "-o", out[name]])
+    return out
+
+
+def run(exe, lines, path):
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    r = subprocess.run([exe, path], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    rows = [ln.split() for ln in r.stdout.strip().split("\n")]
+    assert len(rows) == len(lines)
+    return rows
+
+
+def hexes(ws):
+    return ["%08x" % w for w in ws]
+
+
+def test_the_oracle_gives_the_known_answers():
+    for ctr, key, want in cases.KNOWN:
+        assert cases.philox4x32(ctr, key) == want
+
+
+@pytest.mark.parametrize("build", list(FLAGS))
+def test_philox_known_answers_and_random_keys_are_exact(exes, tmp_path, build):
+    keys = cases.random_keys()
+    assert len(keys) == 64 and {k[3] for k in keys} == {0, 1, 2} and any(k[2] >= 2 ** 32 for k in keys) and any(k[0] >= 2 ** 32 for k in keys)
+    lines = ["P " + " ".join(hexes(ctr) + hexes(key)) for ctr, key, _ in cases.KNOWN]
+    lines += ["W %d %d %d %d" % k for k in keys]
+    rows = run(exes[build], lines, str(tmp_path / "philox.txt"))
+    for (ctr, key, want), row in zip(cases.KNOWN, rows):
+        assert row == hexes(want), (ctr, key)
+    for k, row in zip(keys, rows[len(cases.KNOWN):]):
+        w = cases.words(*k)
+        assert row[:4] == hexes(w), k
+        # uniforms exact, normals within the derived bound
+        assert float(row[4]) == cases.uniform(w[0], w[1]) and float(row[5]) == cases.uniform(w[2], w[3]), k
+        z = cases.normal2(*k)
+        err = max(abs(float(row[6]) - z[0]), abs(float(row[7]) - z[1]))
+        assert err <= cases.TOL_NORMAL, (k, err)
+
+
+def test_uniforms_are_exact_and_strictly_inside_the_unit_interval(exes, tmp_path):
+    M = cases.MASK
+    pairs = [(0, 0), (M, M), (0, M), (M, 0), (1 << 6, 0), (0, 1 << 6), (M, M - 63), (0x80000000, 0)]
+    rows = run(exes["asan_ubsan"], ["U %08x %08x" % p for p in pairs], str(tmp_path / "uniform.txt"))
+    got = [float(r[0]) for r in rows]
+    for p, g in zip(pairs, got):
+        assert g == cases.uniform(*p) and 0.0 < g < 1.0, (p, g)
+    assert got[0] == 2.0 ** -53 and got[1] == 1.0 - 2.0 ** -53 and got[7] == 0.5 + 2.0 ** -53
+    # every value is on the grid (k + 1/2) 2^-52: the largest |z| is sqrt(106 ln 2)
+    assert math.sqrt(-2.0 * math.log(got[0])) < 8.58
+    # ... and why it is not 53 bits: the half falls off the significand and all-one words give exactly 1
+    assert cases.uniform_53bit(M, M) == 1.0
+
+
+def test_normals_have_the_moments_of_a_standard_normal():
+    """the oracle itself, 4096 draws of one seed: mean and variance within four standard errors, both outputs, uncorrelated"""
+    z = np.array([cases.normal2(2024, r, e, 0) for r in range(64) for e in range(64)])
+    n = len(z)
+    assert np.all(np.abs(z.mean(0)) < 4.0 / math.sqrt(n)) and np.all(np.abs(z.var(0) - 1.0) < 4.0 * math.sqrt(2.0 / n))
+    assert abs(np.mean(z[:, 0] * z[:, 1])) < 4.0 / math.sqrt(n)
+
+
+def scene_line(s):
+    p = s.params
+    return " ".join(["S", repr(float(p.max_acc)), repr(float(p.max_domega)), repr(float(p.pose_pub_period)), repr(float(p.state_propa_period)),
+                     str(p.substeps), str(p.follow), str(int(s.has_traj)), str(int(s.at_goal)), repr(float(s.cmd[0])), repr(float(s.cmd[1])),
+                     *[repr(float(v)) for v in s.state], repr(float(s.stddev)), str(s.seed), str(s.robot), str(s.event), str(s.ticks)])
+
+
+@pytest.mark.parametrize("build", list(FLAGS))
+def test_noisy_step_matches_the_python_plant(exes, tmp_path, build):
+    rows = run(exes[build], [scene_line(s) for s in cases.SCENES], str(tmp_path / "scenes.txt"))
+    assert len({s.name for s in cases.SCENES}) == len(cases.SCENES)
+    for s, row in zip(cases.SCENES, rows):
+        st = np.array([float(v) for v in row[:7]])
+        err = float(np.max(np.abs(st - np.array(s.want))))
+        assert err <= cases.TOL, (s.name, err, st, s.want)
+        # sigma = 0: the bits of ltv_plant::step, compared inside the harness
+        assert int(row[7]) == (1 if s.stddev == 0.0 else -1), s.name
+
+
+def test_the_scenes_cover_what_they_claim():
+    by = {s.name: s for s in cases.SCENES}
+    for follow in (0, 1):
+        tag = f"follow{follow}_"
+        p = by[tag + "sigma0"].params
+        assert p.follow == follow
+        # sigma = 0 is the un-noised plant of tests/ltv_plant_cases.py
+        s = by[tag + "sigma0"]
+        assert s.want == plant.plant_step(p, True, False, s.cmd, s.state)
+        # noise on: pose and velocity differ from the un-noised plant's, the velocity by no more than 8.6 sigma of the command
+        s = by[tag + "launch_noise"]
+        clean = plant.plant_step(p, True, False, s.cmd, s.state)
+        assert s.want[:3] != clean[:3]
+        assert 0.0 < abs(s.want[3] - clean[3]) <= 8.6 * 0.01 * 0.5 and 0.0 < abs(s.want[4] - clean[4]) <= 8.6 * 0.01 * 0.3
+        if follow:
+            assert s.want[5:] == [0.5, 0.3]                       # desired takes the un-noised command
+        # at a goal the command is (0, 0) and so is its noise; without a trajectory nothing is drawn
+        s = by[tag + "at_goal"]
+        assert s.want == plant.plant_step(p, True, True, s.cmd, s.state)
+        s = by[tag + "no_trajectory"]
+        assert s.want == plant.plant_step(p, False, False, s.cmd, s.state)
+        # v < 0: defined as the product, finite, and perturbed
+        s = by[tag + "v_negative"]
+        assert all(math.isfinite(v) for v in s.want) and s.want != plant.plant_step(p, True, False, s.cmd, s.state)
+        # two events of one robot, two robots at one event
+        assert by[tag + "event_a"].want != by[tag + "event_b"].want and by[tag + "robot_a"].want != by[tag + "robot_b"].want
+    assert cases.normal2(5, 1, 2, 0) != cases.normal2(5, 1, 2, 1) and cases.normal2(5, 1, 2, 0) != cases.normal2(6, 1, 2, 0)
+
+
+def test_calls_are_declared_exported_and_bound():
+    """the feature through every layer that needs no GPU: header, library symbols, ctypes bindings, the Python methods"""
+    hdr = open(os.path.join(ROOT, "include", "alore_ltv_mpc.h")).read()
+    for c in CALLS:
+        assert re.search(r"\b%s\s*\(" % c, hdr), c
+    lib = os.path.join(ROOT, "alore_legged_manipulator_amd", "libalore_nmpc.so")
+    syms = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
+    for c in CALLS + ("alore_nmpc_internal_ekf",):
+        assert re.search(r" T %s$" % c, syms, re.M), c
+    assert "plant_ekf_kernel" in syms and "ltv16plant_ekf_kernel" in syms            # the new kernel's host stub, in namespace ltv
+    from alore_legged_manipulator_amd import _lib, ltv_mpc
+    L = _lib.load()
+    ltv_mpc._bind(L)
+    for c in CALLS:
+        assert getattr(L, c).argtypes is not None, c
+    for m in METHODS:
+        assert callable(getattr(ltv_mpc.BatchedLtvMpc, m)), m
