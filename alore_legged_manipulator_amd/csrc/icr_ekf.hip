@@ -2,6 +2,7 @@
 // drives it (alore_nmpc_ekf_*): the stand-alone filter step, and the closed loop of the NMPC on the filter's estimate.
 // One thread per robot: the 6 x 6 covariance, the state and the flags of a robot live in that thread's registers from the load to
 // the store; no LDS, no scratch (registers: profiles/icr_ekf.txt).  The arithmetic is the header's, nothing is restated here.
+#include "ltv_host_plan.h" // the update schedule, shared with the LTV-MPC loop on this filter
 #include "nmpc_solver.h" // (before icr_ekf.h: that header switches contraction off for what follows it)
 #include "icr_ekf_device.h" // icr_ekf.h, icrekf::Dev and step_robot: load -> step_one -> store for one robot
 
@@ -22,8 +23,8 @@ __global__ void __launch_bounds__(64) step_kernel(Dev d, Params p, int B, const 
     step_robot(d, p, r, w, dt, z, meas != nullptr);
 }
 
-// The third launch of the EKF closed loop: the simulator's plant on the TRUE state (the command decoding of nmpc::plant_kernel,
-// ControlSubCallback simulator.h:234-242, then nmpc::plant_substeps), its ControlPub message (simulator.h:342-347), the filter step.
+// The third launch of the EKF closed loop: the simulator's plant on the TRUE state (nmpc::wheel_plant_step, as nmpc::plant_kernel
+// runs it), its ControlPub message (simulator.h:342-347), the filter step.
 __global__ void __launch_bounds__(64) plant_ekf_kernel(alore_nmpc_batch b, int B, int N, int node, const double* icr, const int* at_goal,
                                                        double* pose, double* vw, nmpc::PlantParams pp, Dev d, Params p, double dt,
                                                        int do_update, const double* noise)
@@ -33,12 +34,9 @@ __global__ void __launch_bounds__(64) plant_ekf_kernel(alore_nmpc_batch b, int B
     double right = (double)b.u[((size_t)r * N + node) * 2], left = (double)b.u[((size_t)r * N + node) * 2 + 1];
     if (at_goal && at_goal[r]) { right = 0.0; left = 0.0; }
     const double xv = icr[(size_t)r * 3], yr = icr[(size_t)r * 3 + 1], yl = icr[(size_t)r * 3 + 2];
-    const double desired_v = (left + right) / 2.0 - (right - left) / (yl - yr) * (yl + yr) / 2.0;
-    const double vy = -(right - left) / (yl - yr) * xv;
-    const double desired_w = (right - left) / (yl - yr);
     double x = pose[(size_t)r * 3], y = pose[(size_t)r * 3 + 1], th = pose[(size_t)r * 3 + 2];
     double v = vw[(size_t)r * 2], w = vw[(size_t)r * 2 + 1];
-    nmpc::plant_substeps(pp, desired_v, desired_w, vy, x, y, th, v, w);
+    nmpc::wheel_plant_step(pp, right, left, xv, yr, yl, x, y, th, v, w);
     pose[(size_t)r * 3] = x; pose[(size_t)r * 3 + 1] = y; pose[(size_t)r * 3 + 2] = th;
     vw[(size_t)r * 2] = v; vw[(size_t)r * 2 + 1] = w;
     const double wheel[2] = {v - w * yl, v - w * yr}; // (left, right)
@@ -114,7 +112,7 @@ int ekf_tick(alore_nmpc_handle h, const alore_nmpc_batch* dev, int B, double now
     const int rc = alore_nmpc_rti(h, dev, B, 1, stream);
     if (rc != ALORE_NMPC_OK) return rc;
     h->ekf.ticks += 1;
-    const int do_update = h->ekf.ticks % h->ekf.params.odom_every == 0;
+    const int do_update = ltv_plan::is_update_tick(h->ekf.ticks, h->ekf.params.odom_every) ? 1 : 0;
     hipLaunchKernelGGL(icrekf::plant_ekf_kernel, dim3((B + 63) / 64), dim3(64), 0, s, *dev, B, N, delay_num < N ? delay_num : N - 1,
                        h->refs.d_icr, h->refs.d_goal, h->refs.d_est, h->refs.d_vw, h->refs.plant, L.d, ekf_params(h->ekf.params), dt_tick,
                        do_update, d_noise);
@@ -240,12 +238,11 @@ int alore_nmpc_ekf_closed_loop_run(alore_nmpc_handle h, const alore_nmpc_batch* 
     if (!ekf_ready(h, B) || !h->refs.has_plant || !dev || B > h->refs.B || delay_num < 0 || !(dt_tick > 0.0) || n_ticks < 0)
         return fail(h, ALORE_NMPC_E_INVALID, "ekf_closed_loop_run: bad argument (needs plant_init and ekf_init)");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    size_t updates = 0;
+    const long first = h->ekf.ticks; // ekf_tick counts on; update number k of the run reads d_noise [k]
     for (int t = 0; t < n_ticks; ++t) {
-        const bool upd = (h->ekf.ticks + 1) % h->ekf.params.odom_every == 0; // what this tick will decide
+        const size_t updates = (size_t)ltv_plan::updates_within(first, h->ekf.ticks, h->ekf.params.odom_every);
         const int rc = ekf_tick(h, dev, B, t0 + dt_tick * t, dt_tick, delay_num, d_noise ? d_noise + updates * (size_t)B * 3 : nullptr, stream);
         if (rc != ALORE_NMPC_OK) return rc;
-        if (upd) ++updates;
     }
     return ALORE_NMPC_OK;
 }

@@ -6,7 +6,7 @@
 // ltv_mpc.hip, handed est_pose where they take the plant's pose.
 // Three launches per tick on purpose: see DESIGN 7c.
 #include "ltv_ekf_loop.h"
-#include "ltv_plant.h"
+#include "ltv_plant_device.h" // ltv::plant_robot: load -> ltv_plant::step_noisy -> store and trace record for one robot
 #include "icr_ekf_device.h" // last: icr_ekf.h switches contraction off for what follows it
 
 namespace ltv {
@@ -16,30 +16,12 @@ __global__ void __launch_bounds__(64) plant_ekf_kernel(PlantEkf a, icrekf::Dev d
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= a.B) return;
     const bool has = a.meta ? a.meta[(size_t)r * 8 + 6] != 0.0 : true;
-    const int goal = a.goal[r];
-    double* const vwp = a.pose + (size_t)a.stride * 3;
-    double* const desp = a.pose + (size_t)a.stride * 5;
-    // 1. the plant step on the true state, PoseSub with the noise
-    ltv_plant::State st;
-    st.x = a.pose[(size_t)r * 3]; st.y = a.pose[(size_t)r * 3 + 1]; st.th = a.pose[(size_t)r * 3 + 2];
-    st.v = vwp[(size_t)r * 2]; st.w = vwp[(size_t)r * 2 + 1];
-    st.dv = desp[(size_t)r * 2]; st.dw = desp[(size_t)r * 2 + 1];
-    const double cv = a.cmd[(size_t)r * 2], cw = a.cmd[(size_t)r * 2 + 1];
-    const int status = a.status[r];
+    // 1. the plant step on the true state, PoseSub with the noise (and 5., the plant's part of the trace record, as
+    // plant_step_kernel writes it: here, so that its pointers are not held in scalar registers across the filter step)
     ltv_plant::Noise nz;
     nz.stddev = a.noise_stddev; nz.seed = a.seed; nz.event = a.event; nz.robot = (uint32_t)r;
-    ltv_plant::step_noisy(a.p, has, goal != 0, cv, cw, nz, st);
-    a.pose[(size_t)r * 3] = st.x; a.pose[(size_t)r * 3 + 1] = st.y; a.pose[(size_t)r * 3 + 2] = st.th;
-    vwp[(size_t)r * 2] = st.v; vwp[(size_t)r * 2 + 1] = st.w;
-    desp[(size_t)r * 2] = st.dv; desp[(size_t)r * 2 + 1] = st.dw;
-    // (5. the plant's part of the trace record, as plant_step_kernel writes it: here, so that its pointers are not held in
-    // scalar registers across the filter step)
-    if (a.tr_pose) {
-        a.tr_pose[(size_t)r * 3] = st.x; a.tr_pose[(size_t)r * 3 + 1] = st.y; a.tr_pose[(size_t)r * 3 + 2] = st.th;
-        double* const tc = a.tr_pose + (size_t)a.stride * 3;
-        tc[(size_t)r * 2] = (has && goal) ? 0.0 : cv; tc[(size_t)r * 2 + 1] = (has && goal) ? 0.0 : cw;
-        a.tr_status[r] = status; a.tr_status[(size_t)a.stride + r] = goal;
-    }
+    ltv_plant::State st;
+    plant_robot(a, r, has, a.goal[r], nz, true, st);
     // 2. ControlPub from the true ICR and the velocities after the step: (left, right)
     const double yr = a.icr[(size_t)r * 3 + 1], yl = a.icr[(size_t)r * 3 + 2];
     const double wheel[2] = {st.v - st.w * yl, st.v - st.w * yr};

@@ -14,8 +14,9 @@
 #include <vector>
 
 #include "ltv_ekf_loop.h"
+#include "ltv_host_plan.h"
 #include "ltv_mpc.h"
-#include "ltv_plant.h"
+#include "ltv_plant_device.h"
 #include "minco_spline.h"
 #include "nmpc_kernels.h"
 
@@ -61,13 +62,20 @@ __device__ __forceinline__ void ltv_ref_node(const nmpc::RefStore& s, const doub
     o.w = v3[0];
     goal = (t_cur > duration + 1.0) ? 1 : 0;
 }
-// one step of smooth_yaw: `cur` moved by whole turns until it is within a quarter turn of `prev` (pre_tick_kernel; the loops of
-// ltv_unwrap_kernel below, which keeps its own text so that its code object stays what it was)
+// one step of smooth_yaw: `cur` moved by whole turns until it is within a quarter turn of `prev`
 __device__ __forceinline__ void ltv_unwrap_step(double& cur, double prev)
 {
     double dy = cur - prev;
     while (dy >= M_PI / 2) { cur -= 2 * M_PI; dy = cur - prev; }
     while (dy <= -M_PI / 2) { cur += 2 * M_PI; dy = cur - prev; }
+}
+// node i of robot r as the solve reads it: xref [B][T][3] with the heading `psi` (normalised or unwrapped), dref [B][T][2]
+__device__ __forceinline__ void ltv_store_node(double* xref, double* dref, int T, int r, int i, const RefNode& n, double psi)
+{
+    double* xo = xref + ((size_t)r * T + i) * 3;
+    xo[0] = n.X; xo[1] = n.Y; xo[2] = psi;
+    dref[((size_t)r * T + i) * 2] = n.v;
+    dref[((size_t)r * T + i) * 2 + 1] = n.w;
 }
 
 // getRefPoints of the `mpc` node on the trajectory store: thread = (robot, i), then smooth_yaw per robot
@@ -81,10 +89,7 @@ __global__ void ltv_refs_kernel(nmpc::RefStore s, int B, int T, double dt, doubl
     RefNode n;
     int goal;
     ltv_ref_node(s, m, r, i, dt, now, n, goal);
-    double* xo = xref + ((size_t)r * T + i) * 3;
-    xo[0] = n.X; xo[1] = n.Y; xo[2] = n.psi;
-    dref[((size_t)r * T + i) * 2] = n.v;
-    dref[((size_t)r * T + i) * 2 + 1] = n.w;
+    ltv_store_node(xref, dref, T, r, i, n, n.psi);
     if (i == 0 && at_goal) at_goal[r] = goal;
 }
 __global__ void ltv_unwrap_kernel(nmpc::RefStore s, int B, int T, const double* est, double* xref)
@@ -96,16 +101,12 @@ __global__ void ltv_unwrap_kernel(nmpc::RefStore s, int B, int T, const double* 
     if (!std::isfinite(th) || !std::isfinite(x[2])) return; // an Inf heading would never leave the loops below; get_cmd flags the robot (status 2)
     // the walk in registers (the headings were read, changed and read again in memory: several dependent round trips per node)
     double prev = x[2];
-    double dy = prev - th;
-    while (dy >= M_PI / 2) { prev -= 2 * M_PI; dy = prev - th; }
-    while (dy <= -M_PI / 2) { prev += 2 * M_PI; dy = prev - th; }
+    ltv_unwrap_step(prev, th);
     x[2] = prev;
     for (int i = 0; i + 1 < T; ++i) {
         double cur = x[3 * (i + 1) + 2];
         if (!std::isfinite(cur)) return;
-        dy = cur - prev;
-        while (dy >= M_PI / 2) { cur -= 2 * M_PI; dy = cur - prev; }
-        while (dy <= -M_PI / 2) { cur += 2 * M_PI; dy = cur - prev; }
+        ltv_unwrap_step(cur, prev);
         x[3 * (i + 1) + 2] = cur;
         prev = cur;
     }
@@ -129,39 +130,14 @@ struct PreTick {
     int do_plant;           // pre_tick_kernel: 0 on the first tick of a run
 };
 
-// the plant step of robot r (ltv_plant.h) and its trace record; every calling lane computes, `writer` lanes store.  Returns the pose.
-__device__ __forceinline__ void plant_robot(const PreTick& a, int r, bool has, int goal, bool writer, double& th_out)
-{
-    double* const vwp = a.pose + (size_t)a.stride * 3;
-    double* const desp = a.pose + (size_t)a.stride * 5;
-    ltv_plant::State st;
-    st.x = a.pose[(size_t)r * 3]; st.y = a.pose[(size_t)r * 3 + 1]; st.th = a.pose[(size_t)r * 3 + 2];
-    st.v = vwp[(size_t)r * 2]; st.w = vwp[(size_t)r * 2 + 1];
-    st.dv = desp[(size_t)r * 2]; st.dw = desp[(size_t)r * 2 + 1];
-    const double cv = a.cmd[(size_t)r * 2], cw = a.cmd[(size_t)r * 2 + 1];
-    const int status = a.status[r];
-    ltv_plant::step(a.p, has, goal != 0, cv, cw, st);
-    th_out = st.th;
-    if (!writer) return;
-    a.pose[(size_t)r * 3] = st.x; a.pose[(size_t)r * 3 + 1] = st.y; a.pose[(size_t)r * 3 + 2] = st.th;
-    vwp[(size_t)r * 2] = st.v; vwp[(size_t)r * 2 + 1] = st.w;
-    desp[(size_t)r * 2] = st.dv; desp[(size_t)r * 2 + 1] = st.dw;
-    if (a.tr_pose) {
-        a.tr_pose[(size_t)r * 3] = st.x; a.tr_pose[(size_t)r * 3 + 1] = st.y; a.tr_pose[(size_t)r * 3 + 2] = st.th;
-        double* const tc = a.tr_pose + (size_t)a.stride * 3;
-        tc[(size_t)r * 2] = (has && goal) ? 0.0 : cv; tc[(size_t)r * 2 + 1] = (has && goal) ? 0.0 : cw;
-        a.tr_status[r] = status; a.tr_status[(size_t)a.stride + r] = goal;
-    }
-}
-
-// alore_ltv_plant_step: thread = robot
+// alore_ltv_plant_step: thread = robot (plant_robot: ltv_plant_device.h)
 __global__ void plant_step_kernel(PreTick a)
 {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= a.B) return;
     const bool has = a.meta ? a.meta[(size_t)r * 8 + 6] != 0.0 : true;
-    double th;
-    plant_robot(a, r, has, a.goal[r], true, th);
+    ltv_plant::State st;
+    plant_robot(a, r, has, a.goal[r], ltv_plant::noise_off(), true, st);
 }
 
 // One launch in front of the solve of tick t: the plant step and trace record of tick t - 1, getRefPoints of tick t and smooth_yaw
@@ -179,7 +155,9 @@ __global__ __launch_bounds__(64) void pre_tick_kernel(PreTick a)
     if (a.do_plant) {
         // the flag of tick t - 1: read and (below) overwritten by lane 0, handed to the others in registers
         const int gp = __shfl((i == 0) ? a.goal[r] : 0, 0);
-        plant_robot(a, r, has, gp, i == 0, th);
+        ltv_plant::State st;
+        plant_robot(a, r, has, gp, ltv_plant::noise_off(), i == 0, st);
+        th = st.th;
     } else {
         th = a.pose[(size_t)r * 3 + 2];
     }
@@ -202,10 +180,7 @@ __global__ __launch_bounds__(64) void pre_tick_kernel(PreTick a)
         if (i == k + 1) prev = __hiloint2double(chi, clo);
     }
     if (!in) return;
-    double* xo = a.xref + ((size_t)r * a.T + i) * 3;
-    xo[0] = n.X; xo[1] = n.Y; xo[2] = cur;
-    a.dref[((size_t)r * a.T + i) * 2] = n.v;
-    a.dref[((size_t)r * a.T + i) * 2 + 1] = n.w;
+    ltv_store_node(a.xref, a.dref, a.T, r, i, n, cur);
     if (i == 0) a.goal[r] = goal;
 }
 
@@ -254,6 +229,11 @@ int lfail(alore_ltv_handle h, int code, const char* what, hipError_t e = hipSucc
     do {                                                                  \
         hipError_t e_ = (call);                                           \
         if (e_ != hipSuccess) return lfail(h, ALORE_LTV_E_HIP, #call, e_); \
+    } while (0)
+// after the carves of an entry point (ltv_plan::StageCursor over the pinned slab): one that did not fit is refused
+#define LTV_STAGE(h, who, cursor)                                                                                 \
+    do {                                                                                                          \
+        if (!(cursor).ok()) return lfail(h, ALORE_LTV_E_INVALID, who ": the staging slab of the handle is too small"); \
     } while (0)
 template <class T>
 hipError_t zalloc(T** p, size_t n)
@@ -324,7 +304,7 @@ int alore_ltv_create(const alore_ltv_config* cfg, int device, int max_robots, al
     if (std::getenv("ALORE_LTV_STAMPS")) A(zalloc(&h->d_stamps, (size_t)8));
     A(zalloc(&h->d_st, T * 2 * B)); A(zalloc(&h->d_sweeps, B)); A(zalloc(&h->d_status, B)); A(zalloc(&h->d_goal, B)); A(zalloc(&h->d_cmd, B * 2));
     A(zalloc(&h->d_relin, B)); A(zalloc(&h->d_du, B));
-    h->stage_bytes = sizeof(double) * B * ((T + 1) * 3 + T * 5 + 8) + sizeof(int) * B * 4 + 1024;
+    h->stage_bytes = ltv_plan::stage_bytes(B, T);
     if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_stage, h->stage_bytes, hipHostMallocDefault);
     if (e != hipSuccess) { lfree(h); delete h; return e == hipErrorOutOfMemory ? ALORE_LTV_E_NOMEM : ALORE_LTV_E_HIP; }
     *out = h;
@@ -353,8 +333,10 @@ int alore_ltv_set_refs(alore_ltv_handle h, int B, const double* xref, const doub
     LTV_TRY(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     const size_t T = h->cfg.predict_steps;
-    double* hx = (double*)h->h_stage;
-    double* hd = hx + (size_t)B * T * 3;
+    ltv_plan::StageCursor stage(h->h_stage, h->stage_bytes);
+    double* hx = stage.take<double>((size_t)B * T * 3);
+    double* hd = stage.take<double>((size_t)B * T * 2);
+    LTV_STAGE(h, "set_refs", stage);
     std::memcpy(hx, xref, sizeof(double) * B * T * 3);
     std::memcpy(hd, dref, sizeof(double) * B * T * 2);
     LTV_TRY(h, hipMemcpyAsync(h->d_xref, hx, sizeof(double) * B * T * 3, hipMemcpyHostToDevice, s));
@@ -373,7 +355,9 @@ int alore_ltv_refs_from_store(alore_ltv_handle h, void* nmpc, int B, double now,
     LTV_TRY(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     const int T = h->cfg.predict_steps;
-    double* he = (double*)h->h_stage;
+    ltv_plan::StageCursor stage(h->h_stage, h->stage_bytes);
+    double* he = stage.take<double>((size_t)B * 3);
+    LTV_STAGE(h, "refs_from_store", stage);
     std::memcpy(he, est, sizeof(double) * B * 3);
     LTV_TRY(h, hipMemcpyAsync(h->d_est, he, sizeof(double) * B * 3, hipMemcpyHostToDevice, s));
     const long total = (long)B * T;
@@ -386,37 +370,55 @@ int alore_ltv_refs_from_store(alore_ltv_handle h, void* nmpc, int B, double now,
     return ALORE_LTV_OK;
 }
 
-// du_th: null for the fixed count; else the converged build (n_relin is its cap), which is always the lanes kernel
-static int ltv_enqueue(alore_ltv_handle h, int B, const double* now_state, int n_relin, int reset, hipStream_t s,
-                       double* cmd_host = nullptr, int* status_host = nullptr, const double* du_th = nullptr, int* iters_host = nullptr)
+// What every solve launch takes of the handle.  now: the states [B][3] as the device reads them.  du_th < 0: the fixed count of
+// n_relin passes; else the converged build (n_relin is its cap), which is always the lanes kernel.
+static ltv::DevConv solve_args(alore_ltv_handle h, int B, const double* now, int n_relin, double du_th, int reset)
 {
-    double* hn = (double*)h->h_stage;
-    std::memcpy(hn, now_state, sizeof(double) * B * 3);
     ltv::DevConv d{};
     d.c = h->cfg; d.B = B; d.stride = h->B;
-    static const char* which = std::getenv("ALORE_LTV_KERNEL");
-    const bool thread_kernel = !du_th && which && which[0] == 't';
-    if (cmd_host && !thread_kernel) { // tick path: the lanes kernel reads the states once, straight from the pinned slab
-        void* dn = nullptr;
-        LTV_TRY(h, hipHostGetDevicePointer(&dn, hn, 0));
-        d.now = (const double*)dn;
-    } else {
-        LTV_TRY(h, hipMemcpyAsync(h->d_now, hn, sizeof(double) * B * 3, hipMemcpyHostToDevice, s));
-        d.now = h->d_now;
-    }
+    d.now = now;
     d.xref = h->d_xref; d.dref = h->d_dref; d.output = h->d_out; d.buff = h->d_buff; d.xopt = h->d_xopt;
     d.ws = h->d_ws; d.st = h->d_st; d.sweeps = h->d_sweeps; d.status = h->d_status; d.cmd = h->d_cmd;
     d.n_relin = n_relin; d.reset = reset;
-    d.cmd_host = cmd_host; d.status_host = status_host;
     d.stamps = h->d_stamps;
+    if (du_th < 0.0) return d;
+    d.du_th = std::isinf(du_th) ? 1.7976931348623157e308 : du_th; // "always met": the kernel compares finite numbers only
+    d.relin_iters = h->d_relin; d.du = h->d_du;
+    return d;
+}
+static hipError_t launch_solve(const ltv::DevConv& d, double du_th, bool thread_kernel, hipStream_t s)
+{
+    return du_th < 0.0 ? ltv::launch_get_cmd(d, thread_kernel, s) : ltv::launch_get_cmd_converge(d, s);
+}
+
+// the host regions of the pinned slab that the kernel of a tick writes straight into (device alias of the host pointer), behind
+// the states: commands [B][2], status [B], pass counts [B]
+struct TickOut { double* cmd; int *status, *iters; };
+
+// a solve on host states (du_th: see solve_args); tick: the kernel also writes what a tick returns into the slab
+static int ltv_enqueue(alore_ltv_handle h, int B, const double* now_state, int n_relin, double du_th, int reset, hipStream_t s, TickOut* tick = nullptr)
+{
+    ltv_plan::StageCursor stage(h->h_stage, h->stage_bytes);
+    double* hn = stage.take<double>((size_t)B * 3);
+    if (tick) { tick->cmd = stage.take<double>((size_t)B * 2); tick->status = stage.take<int>(B); tick->iters = stage.take<int>(B); }
+    LTV_STAGE(h, "solve", stage);
+    std::memcpy(hn, now_state, sizeof(double) * B * 3);
     // 16 lanes per robot (stages in registers, sweeps lane by lane) unless ALORE_LTV_KERNEL=thread asks for the
     // one-thread-per-robot kernel (diagnostic A/B)
-    if (du_th) {
-        d.du_th = *du_th; d.relin_iters = h->d_relin; d.du = h->d_du; d.iters_host = iters_host;
-        LTV_TRY(h, ltv::launch_get_cmd_converge(d, s));
-        return ALORE_LTV_OK;
+    static const char* which = std::getenv("ALORE_LTV_KERNEL");
+    const bool thread_kernel = du_th < 0.0 && which && which[0] == 't';
+    void* dn = h->d_now;
+    if (tick && !thread_kernel) // tick path: the lanes kernel reads the states once, straight from the pinned slab
+        LTV_TRY(h, hipHostGetDevicePointer(&dn, hn, 0));
+    else
+        LTV_TRY(h, hipMemcpyAsync(h->d_now, hn, sizeof(double) * B * 3, hipMemcpyHostToDevice, s));
+    ltv::DevConv d = solve_args(h, B, (const double*)dn, n_relin, du_th, reset);
+    if (tick) {
+        LTV_TRY(h, hipHostGetDevicePointer((void**)&d.cmd_host, tick->cmd, 0));
+        LTV_TRY(h, hipHostGetDevicePointer((void**)&d.status_host, tick->status, 0));
+        if (du_th >= 0.0) LTV_TRY(h, hipHostGetDevicePointer((void**)&d.iters_host, tick->iters, 0));
     }
-    LTV_TRY(h, ltv::launch_get_cmd(d, thread_kernel, s));
+    LTV_TRY(h, launch_solve(d, du_th, thread_kernel, s));
     return ALORE_LTV_OK;
 }
 
@@ -425,7 +427,7 @@ int alore_ltv_get_cmd(alore_ltv_handle h, int B, const double* now_state, int n_
     if (!h || B < 1 || B > h->B || !now_state || n_relin < 1) return lfail(h, ALORE_LTV_E_INVALID, "get_cmd: bad argument");
     LTV_TRY(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    const int rc = ltv_enqueue(h, B, now_state, n_relin, reset, s);
+    const int rc = ltv_enqueue(h, B, now_state, n_relin, -1.0, reset, s);
     if (rc != ALORE_LTV_OK) return rc;
     LTV_TRY(h, hipStreamSynchronize(s)); // the staging slab is reused by the next call
     return ALORE_LTV_OK;
@@ -437,18 +439,14 @@ int alore_ltv_tick(alore_ltv_handle h, int B, const double* now_state, int n_rel
     if (!h || B < 1 || B > h->B || !now_state || n_relin < 1 || !cmd) return lfail(h, ALORE_LTV_E_INVALID, "tick: bad argument");
     LTV_TRY(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    // the kernel writes the 20 bytes per robot a tick returns straight into the pinned slab (device alias of the host
-    // pointer): two copy commands and their completion signals less on the critical path of the tick
-    double* sc = (double*)h->h_stage + (size_t)B * 3;
-    int* st = (int*)(sc + (size_t)B * 2);
-    void *dsc = nullptr, *dst = nullptr;
-    LTV_TRY(h, hipHostGetDevicePointer(&dsc, sc, 0));
-    LTV_TRY(h, hipHostGetDevicePointer(&dst, st, 0));
-    const int rc = ltv_enqueue(h, B, now_state, n_relin, reset, s, (double*)dsc, (int*)dst);
+    // the kernel writes the 20 bytes per robot a tick returns straight into the pinned slab: two copy commands and their
+    // completion signals less on the critical path of the tick
+    TickOut t;
+    const int rc = ltv_enqueue(h, B, now_state, n_relin, -1.0, reset, s, &t);
     if (rc != ALORE_LTV_OK) return rc;
     LTV_TRY(h, hipStreamSynchronize(s));
-    std::memcpy(cmd, sc, sizeof(double) * B * 2);
-    if (status) std::memcpy(status, st, sizeof(int) * B);
+    std::memcpy(cmd, t.cmd, sizeof(double) * B * 2);
+    if (status) std::memcpy(status, t.status, sizeof(int) * B);
     return ALORE_LTV_OK;
 }
 
@@ -467,8 +465,7 @@ int alore_ltv_get_cmd_converge(alore_ltv_handle h, int B, const double* now_stat
     if (const char* why = converge_args_bad(max_relin, du_th)) return lfail(h, ALORE_LTV_E_INVALID, (std::string("get_cmd_converge: ") + why).c_str());
     LTV_TRY(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    if (std::isinf(du_th)) du_th = 1.7976931348623157e308; // "always met": the kernel compares finite numbers only
-    const int rc = ltv_enqueue(h, B, now_state, max_relin, reset, s, nullptr, nullptr, &du_th);
+    const int rc = ltv_enqueue(h, B, now_state, max_relin, du_th, reset, s);
     if (rc != ALORE_LTV_OK) return rc;
     LTV_TRY(h, hipStreamSynchronize(s)); // the staging slab is reused by the next call
     return ALORE_LTV_OK;
@@ -481,21 +478,13 @@ int alore_ltv_tick_converge(alore_ltv_handle h, int B, const double* now_state, 
     if (const char* why = converge_args_bad(max_relin, du_th)) return lfail(h, ALORE_LTV_E_INVALID, (std::string("tick_converge: ") + why).c_str());
     LTV_TRY(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    if (std::isinf(du_th)) du_th = 1.7976931348623157e308;
-    // as alore_ltv_tick: commands, status and the pass counts land in the pinned slab, behind the states
-    double* sc = (double*)h->h_stage + (size_t)B * 3;
-    int* st = (int*)(sc + (size_t)B * 2);
-    int* it = st + B;
-    void *dsc = nullptr, *dst = nullptr, *dit = nullptr;
-    LTV_TRY(h, hipHostGetDevicePointer(&dsc, sc, 0));
-    LTV_TRY(h, hipHostGetDevicePointer(&dst, st, 0));
-    LTV_TRY(h, hipHostGetDevicePointer(&dit, it, 0));
-    const int rc = ltv_enqueue(h, B, now_state, max_relin, reset, s, (double*)dsc, (int*)dst, &du_th, (int*)dit);
+    TickOut t; // as alore_ltv_tick, and the pass counts
+    const int rc = ltv_enqueue(h, B, now_state, max_relin, du_th, reset, s, &t);
     if (rc != ALORE_LTV_OK) return rc;
     LTV_TRY(h, hipStreamSynchronize(s));
-    std::memcpy(cmd, sc, sizeof(double) * B * 2);
-    if (status) std::memcpy(status, st, sizeof(int) * B);
-    if (relin_iters) std::memcpy(relin_iters, it, sizeof(int) * B);
+    std::memcpy(cmd, t.cmd, sizeof(double) * B * 2);
+    if (status) std::memcpy(status, t.status, sizeof(int) * B);
+    if (relin_iters) std::memcpy(relin_iters, t.iters, sizeof(int) * B);
     return ALORE_LTV_OK;
 }
 
@@ -504,8 +493,10 @@ int alore_ltv_relin_info(alore_ltv_handle h, int B, int* relin_iters, double* du
     if (!h || B < 1 || B > h->B) return lfail(h, ALORE_LTV_E_INVALID, "relin_info: bad argument");
     LTV_TRY(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    double* sd = (double*)h->h_stage;
-    int* si = (int*)(sd + (size_t)B);
+    ltv_plan::StageCursor stage(h->h_stage, h->stage_bytes);
+    double* sd = stage.take<double>(B);
+    int* si = stage.take<int>(B);
+    LTV_STAGE(h, "relin_info", stage);
     if (du) LTV_TRY(h, hipMemcpyAsync(sd, h->d_du, sizeof(double) * B, hipMemcpyDeviceToHost, s));
     if (relin_iters) LTV_TRY(h, hipMemcpyAsync(si, h->d_relin, sizeof(int) * B, hipMemcpyDeviceToHost, s));
     LTV_TRY(h, hipStreamSynchronize(s));
@@ -522,11 +513,12 @@ int alore_ltv_results(alore_ltv_handle h, int B, double* output, double* xopt, i
     const size_t T = h->cfg.predict_steps;
     // through the pinned slab of the handle (a device-to-pageable copy is staged by the runtime in small pieces with a host
     // wait per piece): layout  output | xopt | sweeps | status
-    char* base = h->h_stage;
-    double* so = (double*)base;
-    double* sx = so + (size_t)B * T * 2;
-    int* ss = (int*)(sx + (size_t)B * (T + 1) * 3);
-    int* st = ss + B;
+    ltv_plan::StageCursor stage(h->h_stage, h->stage_bytes);
+    double* so = stage.take<double>((size_t)B * T * 2);
+    double* sx = stage.take<double>((size_t)B * (T + 1) * 3);
+    int* ss = stage.take<int>(B);
+    int* st = stage.take<int>(B);
+    LTV_STAGE(h, "results", stage);
     if (output) LTV_TRY(h, hipMemcpyAsync(so, h->d_out, sizeof(double) * B * T * 2, hipMemcpyDeviceToHost, s));
     if (xopt) LTV_TRY(h, hipMemcpyAsync(sx, h->d_xopt, sizeof(double) * B * (T + 1) * 3, hipMemcpyDeviceToHost, s));
     if (sweeps) LTV_TRY(h, hipMemcpyAsync(ss, h->d_sweeps, sizeof(int) * B, hipMemcpyDeviceToHost, s));
@@ -544,9 +536,10 @@ int alore_ltv_commands(alore_ltv_handle h, int B, double* cmd, int* status, void
     if (!h || B < 1 || B > h->B || !cmd) return lfail(h, ALORE_LTV_E_INVALID, "commands: bad argument");
     LTV_TRY(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    const size_t T = h->cfg.predict_steps, dl = h->cfg.delay_num;
-    double* sc = (double*)h->h_stage;
-    int* st = (int*)(sc + (size_t)B * 2);
+    ltv_plan::StageCursor stage(h->h_stage, h->stage_bytes);
+    double* sc = stage.take<double>((size_t)B * 2);
+    int* st = stage.take<int>(B);
+    LTV_STAGE(h, "commands", stage);
     // column delay_num of every robot's output, packed by the kernel (16 bytes per robot)
     LTV_TRY(h, hipMemcpyAsync(sc, h->d_cmd, sizeof(double) * B * 2, hipMemcpyDeviceToHost, s));
     if (status) LTV_TRY(h, hipMemcpyAsync(st, h->d_status, sizeof(int) * B, hipMemcpyDeviceToHost, s));
@@ -627,6 +620,15 @@ static const char* solve_args_bad(int n_relin, double du_th)
     if (std::isnan(du_th)) return "du_th is NaN";
     return nullptr;
 }
+// n_ticks, t0, dt_tick and the solve's arguments of a run; dt_positive: dt_tick is the filter's step too
+static const char* run_args_bad(int n_ticks, double t0, double dt_tick, bool dt_positive, int n_relin, double du_th)
+{
+    if (n_ticks < 1) return "n_ticks must be at least 1";
+    const bool finite = std::isfinite(t0) && std::isfinite(dt_tick);
+    if (!dt_positive && !finite) return "t0 and dt_tick must be finite";
+    if (dt_positive && (!finite || !(dt_tick > 0.0))) return "t0 must be finite, dt_tick finite and positive";
+    return solve_args_bad(n_relin, du_th);
+}
 #define LTV_ARGS(h, who, expr)                                                                          \
     do {                                                                                                \
         if (const char* why_ = (expr)) return lfail(h, ALORE_LTV_E_INVALID, (std::string(who ": ") + why_).c_str()); \
@@ -639,9 +641,11 @@ int alore_ltv_plant_set_state(alore_ltv_handle h, int B, const double* pose, con
     if (!pose) return lfail(h, ALORE_LTV_E_INVALID, "plant_set_state: pose is null");
     LTV_TRY(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    double* sp = (double*)h->h_stage;
-    double* sv = sp + (size_t)B * 3;
-    double* sd = sv + (size_t)B * 2;
+    ltv_plan::StageCursor stage(h->h_stage, h->stage_bytes);
+    double* sp = stage.take<double>((size_t)B * 3);
+    double* sv = stage.take<double>((size_t)B * 2);
+    double* sd = stage.take<double>((size_t)B * 2);
+    LTV_STAGE(h, "plant_set_state", stage);
     std::memcpy(sp, pose, sizeof(double) * B * 3);
     if (vw) std::memcpy(sv, vw, sizeof(double) * B * 2); else std::memset(sv, 0, sizeof(double) * B * 2);
     if (desired) std::memcpy(sd, desired, sizeof(double) * B * 2); else std::memset(sd, 0, sizeof(double) * B * 2);
@@ -660,9 +664,11 @@ int alore_ltv_plant_get_state(alore_ltv_handle h, int B, double* pose, double* v
     LTV_ARGS(h, "plant_get_state", plant_args_bad(h, B));
     LTV_TRY(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    double* sp = (double*)h->h_stage;
-    double* sv = sp + (size_t)B * 3;
-    int* sg = (int*)(sv + (size_t)B * 2);
+    ltv_plan::StageCursor stage(h->h_stage, h->stage_bytes);
+    double* sp = stage.take<double>((size_t)B * 3);
+    double* sv = stage.take<double>((size_t)B * 2);
+    int* sg = stage.take<int>(B);
+    LTV_STAGE(h, "plant_get_state", stage);
     if (pose) LTV_TRY(h, hipMemcpyAsync(sp, h->d_pose, sizeof(double) * B * 3, hipMemcpyDeviceToHost, s));
     if (vw) LTV_TRY(h, hipMemcpyAsync(sv, h->d_vw, sizeof(double) * B * 2, hipMemcpyDeviceToHost, s));
     if (at_goal) LTV_TRY(h, hipMemcpyAsync(sg, h->d_goal, sizeof(int) * B, hipMemcpyDeviceToHost, s));
@@ -683,18 +689,21 @@ int alore_ltv_plant_device(alore_ltv_handle h, alore_ltv_plant_view* out)
 }
 
 namespace {
-// what the kernels of a tick take; record: this launch does a plant step, which takes the next slot of the trace ring
-ltv::PreTick tick_args(alore_ltv_handle h, int B, bool record)
+// what the kernels of a tick take; record: this launch does a plant step, which takes the next slot of the trace ring (*slot: that
+// slot, -1 where nothing is recorded)
+ltv::PreTick tick_args(alore_ltv_handle h, int B, bool record, long long* slot = nullptr)
 {
     ltv::PreTick a{};
     a.p = h->plant; a.meta = h->plant_meta; a.B = B; a.T = h->cfg.predict_steps; a.dt = h->cfg.dt;
     a.xref = h->d_xref; a.dref = h->d_dref; a.goal = h->d_goal;
     a.pose = h->d_pose; a.stride = h->B; a.cmd = h->d_cmd; a.status = h->d_status;
-    if (record && h->trace_cap > 0) {
-        const size_t slot = (size_t)(h->trace_total % h->trace_cap) * h->B; // a record is laid out for max_robots robots
-        a.tr_pose = h->d_tr_pose + slot * 5; a.tr_status = h->d_tr_status + slot * 2;
+    const long long at = record ? ltv_plan::ring_next_slot(h->trace_total, h->trace_cap) : -1;
+    if (at >= 0) {
+        const size_t row = (size_t)at * h->B; // a record is laid out for max_robots robots
+        a.tr_pose = h->d_tr_pose + row * 5; a.tr_status = h->d_tr_status + row * 2;
     }
     if (record) ++h->trace_total;
+    if (slot) *slot = at;
     return a;
 }
 // the enqueue of each piece; the arguments have been checked
@@ -719,17 +728,7 @@ hipError_t enq_pre_tick(alore_ltv_handle h, const nmpc::RefStore& rs, int B, dou
 // now: the states [B][3] the solve starts from, on the device; null: the plant's pose
 hipError_t enq_solve(alore_ltv_handle h, int B, int n_relin, double du_th, int reset, hipStream_t s, const double* now = nullptr)
 {
-    ltv::DevConv d{};
-    d.c = h->cfg; d.B = B; d.stride = h->B;
-    d.now = now ? now : h->d_pose;
-    d.xref = h->d_xref; d.dref = h->d_dref; d.output = h->d_out; d.buff = h->d_buff; d.xopt = h->d_xopt;
-    d.ws = h->d_ws; d.st = h->d_st; d.sweeps = h->d_sweeps; d.status = h->d_status; d.cmd = h->d_cmd;
-    d.n_relin = n_relin; d.reset = reset;
-    d.stamps = h->d_stamps;
-    if (du_th < 0.0) return ltv::launch_get_cmd(d, false, s);
-    d.du_th = std::isinf(du_th) ? 1.7976931348623157e308 : du_th; // "always met": the kernel compares finite numbers only
-    d.relin_iters = h->d_relin; d.du = h->d_du;
-    return ltv::launch_get_cmd_converge(d, s);
+    return launch_solve(solve_args(h, B, now ? now : h->d_pose, n_relin, du_th, reset), du_th, false, s);
 }
 hipError_t enq_plant(alore_ltv_handle h, int B, hipStream_t s)
 {
@@ -752,18 +751,19 @@ hipError_t enq_refs_est(alore_ltv_handle h, const nmpc::RefStore& rs, int B, dou
 // the next noise event and the next tick of the filter's count
 hipError_t enq_plant_ekf(alore_ltv_handle h, void* nmpc, const ltv::EkfInfo& ei, int B, double dt_tick, hipStream_t s)
 {
-    const ltv::PreTick t = tick_args(h, B, true);
+    long long slot = -1;
+    const ltv::PreTick t = tick_args(h, B, true, &slot);
     ltv::PlantEkf a{};
     a.p = h->plant; a.meta = h->plant_meta; a.B = B; a.stride = h->B;
     a.goal = h->d_goal; a.pose = h->d_pose; a.cmd = h->d_cmd; a.status = h->d_status; a.icr = h->d_icr;
     a.tr_pose = t.tr_pose; a.tr_status = t.tr_status;
-    if (t.tr_pose) {
-        const size_t slot = (size_t)((h->trace_total - 1) % h->trace_cap) * h->B;
-        a.tr_est = h->d_tr_est + slot * 3; a.tr_ekf_status = h->d_tr_ekf + slot;
+    if (slot >= 0) {
+        const size_t row = (size_t)slot * h->B;
+        a.tr_est = h->d_tr_est + row * 3; a.tr_ekf_status = h->d_tr_ekf + row;
     }
     a.dt = dt_tick;
     *ei.ticks += 1;
-    a.do_update = (*ei.ticks % ei.odom_every == 0) ? 1 : 0;
+    a.do_update = ltv_plan::is_update_tick(*ei.ticks, ei.odom_every) ? 1 : 0;
     a.noise_stddev = h->noise_stddev;
     for (int i = 0; i < 3; ++i) a.meas_stddev[i] = h->meas_stddev[i];
     a.seed = h->noise_seed; a.event = h->noise_event++;
@@ -808,9 +808,7 @@ int alore_ltv_closed_loop_run(alore_ltv_handle h, void* nmpc, int B, double t0, 
     if (!h) return ALORE_LTV_E_INVALID;
     nmpc::RefStore rs;
     LTV_ARGS(h, "closed_loop_run", plant_args_bad(h, B));
-    if (n_ticks < 1) return lfail(h, ALORE_LTV_E_INVALID, "closed_loop_run: n_ticks must be at least 1");
-    if (!std::isfinite(t0) || !std::isfinite(dt_tick)) return lfail(h, ALORE_LTV_E_INVALID, "closed_loop_run: t0 and dt_tick must be finite");
-    LTV_ARGS(h, "closed_loop_run", solve_args_bad(n_relin, du_th));
+    LTV_ARGS(h, "closed_loop_run", run_args_bad(n_ticks, t0, dt_tick, false, n_relin, du_th));
     LTV_ARGS(h, "closed_loop_run", store_bad(h, nmpc, B, &rs));
     LTV_TRY(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
@@ -832,6 +830,30 @@ int alore_ltv_closed_loop_run(alore_ltv_handle h, void* nmpc, int B, double t0, 
     return ALORE_LTV_OK;
 }
 
+// One column of the trace ring.  host: [ticks][B][width], or null (not asked for); dev: slot 0 of the array the column lies in,
+// whose slots are `pitch` elements apart (laid out for max_robots robots); the column starts `first` elements into a slot.
+struct TraceCol { void* host; const void* dev; size_t elem, first, width, pitch; };
+// the newest min(recorded, capacity, max_ticks) ticks of the columns, oldest first (ltv_plan::ring_newest: one or two runs of slots)
+static int get_trace_cols(alore_ltv_handle h, int B, int max_ticks, const TraceCol* cols, int n_cols, int* n_ticks_out, hipStream_t s)
+{
+    const ltv_plan::RingRuns runs = ltv_plan::ring_newest(h->trace_total, h->trace_cap, max_ticks);
+    *n_ticks_out = (int)runs.count;
+    size_t done = 0;
+    for (int k = 0; k < runs.n; ++k) {
+        const size_t slot = (size_t)runs.run[k].slot, rows = (size_t)runs.run[k].rows;
+        for (int c = 0; c < n_cols; ++c) {
+            const TraceCol& t = cols[c];
+            if (!t.host) continue;
+            const size_t row = t.elem * B * t.width;
+            LTV_TRY(h, hipMemcpy2DAsync((char*)t.host + done * row, row, (const char*)t.dev + (slot * t.pitch + t.first) * t.elem, t.pitch * t.elem, row,
+                                        rows, hipMemcpyDeviceToHost, s));
+        }
+        done += rows;
+    }
+    LTV_TRY(h, hipStreamSynchronize(s));
+    return ALORE_LTV_OK;
+}
+
 int alore_ltv_plant_get_trace(alore_ltv_handle h, int B, int max_ticks, double* pose, double* cmd, int* status, int* at_goal, int* n_ticks_out,
                               void* stream)
 {
@@ -839,25 +861,10 @@ int alore_ltv_plant_get_trace(alore_ltv_handle h, int B, int max_ticks, double* 
     LTV_ARGS(h, "plant_get_trace", plant_args_bad(h, B));
     if (max_ticks < 0 || !n_ticks_out) return lfail(h, ALORE_LTV_E_INVALID, "plant_get_trace: bad argument");
     LTV_TRY(h, hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    long long n = h->trace_total < h->trace_cap ? h->trace_total : h->trace_cap;
-    if (n > max_ticks) n = max_ticks;
-    *n_ticks_out = (int)n;
-    // rows of the ring are max_robots apart; the oldest returned tick is `first`, and the ring may wrap once inside the range
-    const size_t HB = h->B, cap = h->trace_cap;
-    for (long long done = 0; done < n;) {
-        const size_t slot = (size_t)((h->trace_total - n + done) % (long long)cap);
-        const size_t rows = std::min<size_t>(cap - slot, (size_t)(n - done));
-        const double* td = h->d_tr_pose + slot * HB * 5;
-        const int* ti = h->d_tr_status + slot * HB * 2;
-        if (pose) LTV_TRY(h, hipMemcpy2DAsync(pose + (size_t)done * B * 3, sizeof(double) * B * 3, td, sizeof(double) * HB * 5, sizeof(double) * B * 3, rows, hipMemcpyDeviceToHost, s));
-        if (cmd) LTV_TRY(h, hipMemcpy2DAsync(cmd + (size_t)done * B * 2, sizeof(double) * B * 2, td + HB * 3, sizeof(double) * HB * 5, sizeof(double) * B * 2, rows, hipMemcpyDeviceToHost, s));
-        if (status) LTV_TRY(h, hipMemcpy2DAsync(status + (size_t)done * B, sizeof(int) * B, ti, sizeof(int) * HB * 2, sizeof(int) * B, rows, hipMemcpyDeviceToHost, s));
-        if (at_goal) LTV_TRY(h, hipMemcpy2DAsync(at_goal + (size_t)done * B, sizeof(int) * B, ti + HB, sizeof(int) * HB * 2, sizeof(int) * B, rows, hipMemcpyDeviceToHost, s));
-        done += (long long)rows;
-    }
-    LTV_TRY(h, hipStreamSynchronize(s));
-    return ALORE_LTV_OK;
+    const size_t HB = h->B;
+    const TraceCol cols[] = {{pose, h->d_tr_pose, sizeof(double), 0, 3, HB * 5}, {cmd, h->d_tr_pose, sizeof(double), HB * 3, 2, HB * 5},
+                             {status, h->d_tr_status, sizeof(int), 0, 1, HB * 2}, {at_goal, h->d_tr_status, sizeof(int), HB, 1, HB * 2}};
+    return get_trace_cols(h, B, max_ticks, cols, 4, n_ticks_out, (hipStream_t)stream);
 }
 
 // ---- the closed loop on the ICR EKF's estimate
@@ -882,7 +889,9 @@ int alore_ltv_plant_set_icr(alore_ltv_handle h, int B, const double* icr, void* 
     }
     LTV_TRY(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    double* sp = (double*)h->h_stage;
+    ltv_plan::StageCursor stage(h->h_stage, h->stage_bytes);
+    double* sp = stage.take<double>((size_t)B * 3);
+    LTV_STAGE(h, "plant_set_icr", stage);
     std::memcpy(sp, icr, sizeof(double) * B * 3);
     LTV_TRY(h, hipMemcpyAsync(h->d_icr, sp, sizeof(double) * B * 3, hipMemcpyHostToDevice, s));
     LTV_TRY(h, hipStreamSynchronize(s)); // the slab is reused
@@ -967,10 +976,7 @@ int alore_ltv_ekf_closed_loop_run(alore_ltv_handle h, void* nmpc, int B, double 
     nmpc::RefStore rs;
     ltv::EkfInfo ei;
     LTV_ARGS(h, "ekf_closed_loop_run", plant_args_bad(h, B));
-    if (n_ticks < 1) return lfail(h, ALORE_LTV_E_INVALID, "ekf_closed_loop_run: n_ticks must be at least 1");
-    if (!std::isfinite(t0) || !std::isfinite(dt_tick) || !(dt_tick > 0.0))
-        return lfail(h, ALORE_LTV_E_INVALID, "ekf_closed_loop_run: t0 must be finite, dt_tick finite and positive");
-    LTV_ARGS(h, "ekf_closed_loop_run", solve_args_bad(n_relin, du_th));
+    LTV_ARGS(h, "ekf_closed_loop_run", run_args_bad(n_ticks, t0, dt_tick, true, n_relin, du_th));
     LTV_ARGS(h, "ekf_closed_loop_run", store_bad(h, nmpc, B, &rs));
     LTV_ARGS(h, "ekf_closed_loop_run", ekf_bad(h, nmpc, B, &ei));
     LTV_TRY(h, hipSetDevice(h->device));
@@ -990,20 +996,9 @@ int alore_ltv_plant_get_trace_est(alore_ltv_handle h, int B, int max_ticks, doub
     LTV_ARGS(h, "plant_get_trace_est", plant_args_bad(h, B));
     if (max_ticks < 0 || !n_ticks_out) return lfail(h, ALORE_LTV_E_INVALID, "plant_get_trace_est: bad argument");
     LTV_TRY(h, hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    long long n = h->trace_total < h->trace_cap ? h->trace_total : h->trace_cap;
-    if (n > max_ticks) n = max_ticks;
-    *n_ticks_out = (int)n;
-    const size_t HB = h->B, cap = h->trace_cap; // as alore_ltv_plant_get_trace walks the ring
-    for (long long done = 0; done < n;) {
-        const size_t slot = (size_t)((h->trace_total - n + done) % (long long)cap);
-        const size_t rows = std::min<size_t>(cap - slot, (size_t)(n - done));
-        if (est) LTV_TRY(h, hipMemcpy2DAsync(est + (size_t)done * B * 3, sizeof(double) * B * 3, h->d_tr_est + slot * HB * 3, sizeof(double) * HB * 3, sizeof(double) * B * 3, rows, hipMemcpyDeviceToHost, s));
-        if (ekf_status) LTV_TRY(h, hipMemcpy2DAsync(ekf_status + (size_t)done * B, sizeof(int) * B, h->d_tr_ekf + slot * HB, sizeof(int) * HB, sizeof(int) * B, rows, hipMemcpyDeviceToHost, s));
-        done += (long long)rows;
-    }
-    LTV_TRY(h, hipStreamSynchronize(s));
-    return ALORE_LTV_OK;
+    const size_t HB = h->B;
+    const TraceCol cols[] = {{est, h->d_tr_est, sizeof(double), 0, 3, HB * 3}, {ekf_status, h->d_tr_ekf, sizeof(int), 0, 1, HB}};
+    return get_trace_cols(h, B, max_ticks, cols, 2, n_ticks_out, (hipStream_t)stream);
 }
 
 } // extern "C"

@@ -1,6 +1,7 @@
-// plant_substeps.h -- the propagation steps of the simulator's plant, the arithmetic once (internal).
-// Plain C++17: __host__ __device__ under hipcc, no HIP dependency otherwise.  Read by the NMPC closed loop (ref_sampler_device.h,
-// through nmpc_kernels.h) and by the plant of the `mpc` node (ltv_plant.h).
+// plant_substeps.h -- the propagation steps of the simulator's plant and its wheel-speed command decode, the arithmetic once
+// (internal).  Plain C++17: __host__ __device__ under hipcc, no HIP dependency otherwise.  Read by the NMPC closed loops
+// (nmpc::plant_kernel, nmpc::plant_ahead_one, icrekf::plant_ekf_kernel: wheel_plant_step, through nmpc_kernels.h) and by the plant
+// of the `mpc` node (ltv_plant.h: plant_substeps).
 #ifndef ALORE_PLANT_SUBSTEPS_H
 #define ALORE_PLANT_SUBSTEPS_H
 
@@ -50,6 +51,25 @@ PLANT_HD void plant_substeps(const PlantParams& p, double desired_v, double desi
         x -= vy * p.propa_period * sn;
         y += vy * p.propa_period * cs;
     }
+}
+
+// One control tick of one robot's plant under a wheel-speed command (right, left): ControlSubCallback (simulator.h:234-242) turns
+// it into (v, vy, omega) through the robot's ICR (xv, yr, yl), then the substeps above.  Pose and velocities in and out in the
+// caller's registers.  The decode is compiled without contraction wherever it is read, so that it is the same instructions in
+// every kernel.
+PLANT_HD void wheel_plant_step(const PlantParams& p, double right, double left, double xv, double yr, double yl, double& x, double& y,
+                               double& th, double& v, double& w)
+{
+    double desired_v, vy, desired_w;
+    {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+        desired_v = (left + right) / 2.0 - (right - left) / (yl - yr) * (yl + yr) / 2.0;
+        vy = -(right - left) / (yl - yr) * xv;
+        desired_w = (right - left) / (yl - yr);
+    }
+    plant_substeps(p, desired_v, desired_w, vy, x, y, th, v, w);
 }
 
 } // namespace nmpc

@@ -261,12 +261,9 @@ __global__ void plant_kernel(alore_nmpc_batch b, int B, int N, int node, const d
     double right = (double)b.u[((size_t)r * N + node) * 2], left = (double)b.u[((size_t)r * N + node) * 2 + 1];
     if (at_goal && at_goal[r]) { right = 0.0; left = 0.0; }
     const double xv = icr[(size_t)r * 3], yr = icr[(size_t)r * 3 + 1], yl = icr[(size_t)r * 3 + 2];
-    const double desired_v = (left + right) / 2.0 - (right - left) / (yl - yr) * (yl + yr) / 2.0;
-    const double vy = -(right - left) / (yl - yr) * xv;
-    const double desired_w = (right - left) / (yl - yr);
     double x = pose[(size_t)r * 3], y = pose[(size_t)r * 3 + 1], th = pose[(size_t)r * 3 + 2];
     double v = vw[(size_t)r * 2], w = vw[(size_t)r * 2 + 1];
-    plant_substeps(p, desired_v, desired_w, vy, x, y, th, v, w);
+    wheel_plant_step(p, right, left, xv, yr, yl, x, y, th, v, w);
     pose[(size_t)r * 3] = x; pose[(size_t)r * 3 + 1] = y; pose[(size_t)r * 3 + 2] = th;
     vw[(size_t)r * 2] = v; vw[(size_t)r * 2 + 1] = w;
 }

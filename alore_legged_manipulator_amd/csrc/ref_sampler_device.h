@@ -120,7 +120,7 @@ __device__ __forceinline__ void ref_sample_smooth_body(const RefStore& s, const 
     }
 }
 
-// plant_substeps (StatePropaCallback, simulator.h:234-275): plant_substeps.h, through nmpc_kernels.h
+// wheel_plant_step (ControlSubCallback and StatePropaCallback, simulator.h:234-275): plant_substeps.h, through nmpc_kernels.h
 
 // The plant step of tick t for robot r and what the sampler of tick t + 1 could not do without the pose it produces: the at-goal
 // flag of tick t (getRefPoints' test, from `now` of tick t), the plant (simulator.h:234-275, see plant_kernel), then x0 <- pose
@@ -137,12 +137,9 @@ __device__ __forceinline__ void plant_ahead_one(const PlantAhead& a, int r)
     const double c0 = (valid && a.psi_rel) ? a.psi_rel[(size_t)r * (N + 1)] : 0.0;
     if (goal) { right = 0.0; left = 0.0; }
     const double xv = a.icr[(size_t)r * 3], yr = a.icr[(size_t)r * 3 + 1], yl = a.icr[(size_t)r * 3 + 2];
-    const double desired_v = (left + right) / 2.0 - (right - left) / (yl - yr) * (yl + yr) / 2.0;
-    const double vy = -(right - left) / (yl - yr) * xv;
-    const double desired_w = (right - left) / (yl - yr);
     double x = a.pose[(size_t)r * 3], y = a.pose[(size_t)r * 3 + 1], th = a.pose[(size_t)r * 3 + 2];
     double v = a.vw[(size_t)r * 2], w = a.vw[(size_t)r * 2 + 1];
-    plant_substeps(a.p, desired_v, desired_w, vy, x, y, th, v, w);
+    wheel_plant_step(a.p, right, left, xv, yr, yl, x, y, th, v, w);
     a.pose[(size_t)r * 3] = x; a.pose[(size_t)r * 3 + 1] = y; a.pose[(size_t)r * 3 + 2] = th;
     a.vw[(size_t)r * 2] = v; a.vw[(size_t)r * 2 + 1] = w;
     a.at_goal[r] = goal;

@@ -7,6 +7,8 @@
 //   S max_acc max_domega pose_pub_period state_propa_period substeps follow  has_traj at_goal  cmd_v cmd_w  x y th v w dv dw
 //     stddev seed robot event ticks            -> the state after `ticks` noisy control periods (event advances by one per period),
 //                                                 then 1 / 0: with stddev == 0, are these the bits of ltv_plant::step? (-1: not asked)
+//                                                 (step() is step_noisy with the noise off, so 1 by construction; what checks
+//                                                 sigma = 0 is the oracle's plain plant_step, which the test compares the state with)
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>

@@ -387,3 +387,42 @@ def test_bad_arguments_are_refused_and_change_nothing():
     want = run_route("one", fresh_store, pose0, B, ticks, 30, "du0.01cap20")
     assert got["tr_pose"].shape == (ticks, B, 3)
     assert_same_snapshot(got, want, "a run after the refused calls")
+
+
+# ---- 7. the trace ring wraps
+@gpu
+def test_a_trace_ring_that_wraps_returns_the_newest_ticks():
+    """B = 3 robots on a handle made for 5 (the slots of the ring are laid out for 5), T = 8, delay 1, noise and filter on: 3 ticks
+    and then 4 on a ring of 4 slots (the 7 records wrap it, and the second call starts in the middle of it) against the same run on
+    a ring of 8 that holds them all.  plant_trace(k) and plant_trace_est(k) of the small ring are the newest min(k, 4) rows of the
+    large one, bit for bit, for k below, at and above the capacity; a handle without a ring runs the same ticks and returns no rows."""
+    B, made_for, T = 3, 5, 8
+    msgs, pose0 = cl.golden_fleet(made_for)
+    n_relin, du_th = cl.MODES["fixed3"]
+
+    def run(trace):
+        store = ekf_store(msgs)
+        eng = cl.engine(made_for, T, 1, trace=trace)
+        eng.plant_set_state(pose0[:B])
+        eng.plant_set_noise(NOISE, MEAS, SEED)
+        store.ekf_reset(pose=pad(pose0[:B], store.B))
+        eng.ekf_closed_loop_run(store, cl.T0, cl.DT, 3, n_relin, du_th, reset=True)
+        eng.ekf_closed_loop_run(store, cl.T0 + 3 * cl.DT, cl.DT, 4, n_relin, du_th)
+        return eng, store                                                   # (the run is in flight on the store's filter)
+
+    (ring, _s4), (full, _s8), (none, _s0) = run(4), run(8), run(0)
+    want = {**full.plant_trace(8), **full.plant_trace_est(8)}
+    assert set(want) == {"pose", "cmd", "status", "at_goal", "est", "ekf_status"}
+    assert want["pose"].shape == (7, B, 3) and np.isfinite(want["pose"]).all() and np.any(want["cmd"] != 0.0)
+    assert not same(want["pose"][2], want["pose"][6]) and np.all(want["ekf_status"] == 0)
+    for k in (4, 3, 1, 10):
+        got = {**ring.plant_trace(k), **ring.plant_trace_est(k)}
+        rows = min(k, 4)
+        for name in want:
+            assert got[name].shape == want[name][7 - rows:].shape and same(got[name], want[name][7 - rows:]), (k, name)
+    for k in (4, 10):
+        got = {**none.plant_trace(k), **none.plant_trace_est(k)}
+        assert all(got[name].shape == (0,) + want[name].shape[1:] for name in want), k
+    assert same(none.plant_get_state()[0], full.plant_get_state()[0])       # the same ticks ran
+    for eng in (ring, full, none):
+        eng.close()

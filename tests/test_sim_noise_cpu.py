@@ -116,7 +116,8 @@ def test_noisy_step_matches_the_python_plant(exes, tmp_path, build):
         st = np.array([float(v) for v in row[:7]])
         err = float(np.max(np.abs(st - np.array(s.want))))
         assert err <= cases.TOL, (s.name, err, st, s.want)
-        # sigma = 0: the bits of ltv_plant::step, compared inside the harness
+        # sigma = 0: the bits of ltv_plant::step, compared inside the harness (step() calls step_noisy with the noise off; the
+        # sigma0 scenes' `want` above is the oracle's plain plant_step: test_the_scenes_cover_what_they_claim)
         assert int(row[7]) == (1 if s.stddev == 0.0 else -1), s.name
 
 
