@@ -68,6 +68,11 @@ class EkfView(C.Structure):
     _fields_ = [("x", C.c_void_p), ("P", C.c_void_p), ("est_pose", C.c_void_p), ("est_icr", C.c_void_p), ("status", C.c_void_p)]
 
 
+class RefsPendingView(C.Structure):
+    """alore_refs_pending_view (include/alore_nmpc.h): device pointers of the hand-over's per-robot words"""
+    _fields_ = [("status", C.c_void_p), ("promotions", C.c_void_p), ("pending_meta", C.c_void_p), ("active_meta", C.c_void_p)]
+
+
 class LaunchInfo(C.Structure):
     _fields_ = [("lanes_per_problem", C.c_int), ("problems_per_block", C.c_int), ("threads_per_block", C.c_int),
                 ("grid", C.c_int), ("lds_bytes_per_block", C.c_int), ("last_kernel_ms", C.c_float)]
@@ -121,6 +126,13 @@ SYMBOLS = (
     ("alore_nmpc_refs_set_polynomes", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p]),
     ("alore_nmpc_refs_set_from_backend", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p]),
     ("alore_nmpc_refs_download", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("alore_nmpc_refs_set_pending_polynomes", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p]),
+    ("alore_nmpc_refs_set_pending_from_backend", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double,
+                                                           C.c_double, C.c_int, C.c_void_p]),
+    ("alore_nmpc_refs_promote", C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_void_p]),
+    ("alore_nmpc_refs_pending_status", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("alore_nmpc_refs_pending_device", C.c_int, [C.c_void_p, C.POINTER(RefsPendingView)]),
+    ("alore_nmpc_refs_pending_download", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("alore_nmpc_plant_init", C.c_int, [C.c_void_p, C.c_void_p]),
     ("alore_nmpc_plant_set_state", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("alore_nmpc_plant_get_state", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

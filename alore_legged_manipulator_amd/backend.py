@@ -180,6 +180,7 @@ def _bind(L):
     L.alore_backend_get_problems.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), DP, DP, DP, DP, DP, DP, DP, C.POINTER(C.c_int)]
     L.alore_backend_predicted_state_device.argtypes = [C.c_void_p, C.c_int, C.c_double] + [C.c_void_p] * 8
     L.alore_backend_plan_masked.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.alore_backend_replan_mask.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.alore_backend_map_default_params.argtypes = [C.POINTER(MapParamsC)]
     L.alore_backend_map_default_params.restype = None
     L.alore_backend_map_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(MapParamsC)]
@@ -835,6 +836,12 @@ class BatchedMSPlanner:
             return
         mp, ms = _mask(mask, mask_stride)
         self._check(self.L.alore_backend_plan_masked(self.h, count or self.count, mp, ms, _stream(stream)))
+
+    def replan_mask(self, out_mask, count: int | None = None, stream=None):
+        """out_mask (int32 device tensor [count] or an address) <- 1 where the last check_plans flags a collision AND the slot was
+        searched, built and planned with success, else 0: the slots whose NEW plan may be delivered
+        (BatchedNmpc.refs_set_pending_from_backend takes it as its mask).  Nothing waits."""
+        self._check(self.L.alore_backend_replan_mask(self.h, int(count or self.count), _dev(out_mask), _stream(stream)))
 
     def last_plan_ms(self) -> float:
         ms = C.c_float()

@@ -689,6 +689,27 @@ int alore_backend_plan_masked(alore_backend_handle h, int count, const int* mask
     return ALORE_BE_OK;
 }
 
+// out[b] = 1 where the last check flags a collision AND the slot was searched, built and planned with success: the slots whose plan is
+// NEW and may be delivered.  (alore_backend_plan_masked plans a flagged slot whose search or build failed again from its old problem:
+// that plan must not go out under a new start time.)
+static __global__ void replan_mask_kernel(const alore_backend_check* check, const int* search_status, const int* build_status, const int* ok,
+                                          int count, int* out)
+{
+    const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (b >= count) return;
+    out[b] = (check[b].collision != 0 && search_status[b] == ALORE_BE_SEARCH_OK && build_status[b] == ALORE_BE_BUILD_OK && ok[b] != 0) ? 1 : 0;
+}
+
+int alore_backend_replan_mask(alore_backend_handle h, int count, int* out_mask, void* stream)
+{
+    if (!h || count < 1 || count > h->B || !out_mask) return fail(h, ALORE_BE_E_INVALID, "replan_mask: bad argument");
+    BE_TRY(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(replan_mask_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->d_check,
+                       h->d_search_status, h->d_build_status, h->r_ok, count, out_mask);
+    BE_TRY(h, hipGetLastError());
+    return ALORE_BE_OK;
+}
+
 int alore_backend_last_plan_ms(alore_backend_handle h, float* ms)
 {
     if (!h || !ms || !h->timed) return fail(h, ALORE_BE_E_INVALID, "last_plan_ms: no plan yet");

@@ -107,6 +107,7 @@ int ekf_tick(alore_nmpc_handle h, const alore_nmpc_batch* dev, int B, double now
     hipStream_t s = (hipStream_t)stream;
     const int N = h->cfg.N;
     const Layout L = ekf_layout(h->ekf.d_block, h->ekf.B);
+    if (int rc = nmpc_capi::promote_if_due(h, now, s)) return rc; // a pending trajectory whose start time has passed (mpc.cpp:177-182)
     // CmdCallback on the estimate: ~odom = EKF_XYTheta, od = EKF_ICR
     HIP_TRY(h, nmpc::launch_ref_sample(h->refs.store, *dev, B, N, (double)h->cfg.dt, now, L.d.est_pose, L.d.est_icr, h->refs.d_goal, h->refs.d_psi, 1, s));
     const int rc = alore_nmpc_rti(h, dev, B, 1, stream);

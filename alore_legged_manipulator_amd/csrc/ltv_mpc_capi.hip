@@ -19,6 +19,7 @@
 #include "ltv_plant_device.h"
 #include "minco_spline.h"
 #include "nmpc_kernels.h"
+#include "traj_handoff.h"
 
 namespace ltv {
 
@@ -188,6 +189,15 @@ __global__ __launch_bounds__(64) void pre_tick_kernel(PreTick a)
 
 // internal accessor of the NMPC handle's trajectory store (nmpc_capi.hip)
 extern "C" int alore_nmpc_internal_refstore(void* nmpc_handle, nmpc::RefStore* out, int* capacity, int* device);
+// ... and of its pending trajectories (nmpc_refs_capi.hip; traj_handoff.h): every sampler of the store below has the promotion for its
+// `now` in front, enqueued only while the NMPC handle has a pending start time outstanding
+extern "C" int alore_nmpc_internal_promote_if_due(void* nmpc_handle, double now, void* stream);
+extern "C" int alore_nmpc_internal_pending_times(void* nmpc_handle, const double** starts, size_t* n);
+#define LTV_PROMOTE(h, nmpc, now, stream)                                                                              \
+    do {                                                                                                               \
+        if (alore_nmpc_internal_promote_if_due(nmpc, now, stream) != 0)                                                \
+            return lfail(h, ALORE_LTV_E_HIP, "promotion of the pending trajectories (alore_nmpc_refs_promote) failed"); \
+    } while (0)
 
 struct alore_ltv_solver {
     alore_ltv_config cfg;
@@ -360,6 +370,7 @@ int alore_ltv_refs_from_store(alore_ltv_handle h, void* nmpc, int B, double now,
     LTV_STAGE(h, "refs_from_store", stage);
     std::memcpy(he, est, sizeof(double) * B * 3);
     LTV_TRY(h, hipMemcpyAsync(h->d_est, he, sizeof(double) * B * 3, hipMemcpyHostToDevice, s));
+    LTV_PROMOTE(h, nmpc, now, stream);
     const long total = (long)B * T;
     hipLaunchKernelGGL(ltv::ltv_refs_kernel, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, s, rs, B, T, h->cfg.dt, now, h->d_xref, h->d_dref,
                        h->d_goal);
@@ -779,6 +790,7 @@ int alore_ltv_refs_from_store_device(alore_ltv_handle h, void* nmpc, int B, doub
     if (!std::isfinite(now)) return lfail(h, ALORE_LTV_E_INVALID, "refs_from_store_device: now is not finite");
     LTV_ARGS(h, "refs_from_store_device", store_bad(h, nmpc, B, &rs));
     LTV_TRY(h, hipSetDevice(h->device));
+    LTV_PROMOTE(h, nmpc, now, stream);
     LTV_TRY(h, enq_refs(h, rs, B, now, (hipStream_t)stream));
     return ALORE_LTV_OK;
 }
@@ -814,19 +826,29 @@ int alore_ltv_closed_loop_run(alore_ltv_handle h, void* nmpc, int B, double t0, 
     hipStream_t s = (hipStream_t)stream;
     const char* env = std::getenv("ALORE_LTV_CLOSED_LOOP_SERIAL");
     const bool serial = env && env[0] == '1';
-    for (int k = 0; k < n_ticks; ++k) {
-        const double now = t0 + k * dt_tick;
-        const int rst = (k == 0 && reset) ? 1 : 0;
-        if (serial) {
-            LTV_TRY(h, enq_refs(h, rs, B, now, s));
-            LTV_TRY(h, enq_solve(h, B, n_relin, du_th, rst, s));
-            LTV_TRY(h, enq_plant(h, B, s));
-        } else {
-            LTV_TRY(h, enq_pre_tick(h, rs, B, now, k > 0, s));
-            LTV_TRY(h, enq_solve(h, B, n_relin, du_th, rst, s));
+    // pre_tick_kernel does the plant step of tick k - 1 and the sampling of tick k in one launch, and the plant step reads the store's
+    // meta rows: where a pending trajectory becomes due the run is cut (traj_handoff.h: split_run), the part in front ends with its own
+    // plant step like a complete run, and the promotion goes between the parts.  No pending start time outstanding: one part.
+    const double* starts = nullptr;
+    size_t n_starts = 0;
+    (void)alore_nmpc_internal_pending_times(nmpc, &starts, &n_starts);
+    const std::vector<double> pend(starts, starts + n_starts); // the promotions below shorten the handle's own list
+    for (const traj_handoff::Segment& g : traj_handoff::split_run(t0, dt_tick, n_ticks, pend.data(), pend.size())) {
+        if (g.promote) LTV_PROMOTE(h, nmpc, traj_handoff::tick_time(t0, dt_tick, g.first), stream);
+        for (int k = g.first; k < g.first + g.count; ++k) {
+            const double now = t0 + k * dt_tick;
+            const int rst = (k == 0 && reset) ? 1 : 0;
+            if (serial) {
+                LTV_TRY(h, enq_refs(h, rs, B, now, s));
+                LTV_TRY(h, enq_solve(h, B, n_relin, du_th, rst, s));
+                LTV_TRY(h, enq_plant(h, B, s));
+            } else {
+                LTV_TRY(h, enq_pre_tick(h, rs, B, now, k > g.first, s));
+                LTV_TRY(h, enq_solve(h, B, n_relin, du_th, rst, s));
+            }
         }
+        if (!serial) LTV_TRY(h, enq_plant(h, B, s));
     }
-    if (!serial) LTV_TRY(h, enq_plant(h, B, s));
     return ALORE_LTV_OK;
 }
 
@@ -941,6 +963,7 @@ int alore_ltv_refs_from_store_est(alore_ltv_handle h, void* nmpc, int B, double 
     LTV_ARGS(h, "refs_from_store_est", store_bad(h, nmpc, B, &rs));
     LTV_ARGS(h, "refs_from_store_est", ekf_bad(h, nmpc, B, &ei));
     LTV_TRY(h, hipSetDevice(h->device));
+    LTV_PROMOTE(h, nmpc, now, stream);
     LTV_TRY(h, enq_refs_est(h, rs, B, now, ei.est_pose, (hipStream_t)stream));
     return ALORE_LTV_OK;
 }
@@ -983,6 +1006,7 @@ int alore_ltv_ekf_closed_loop_run(alore_ltv_handle h, void* nmpc, int B, double 
     hipStream_t s = (hipStream_t)stream;
     for (int k = 0; k < n_ticks; ++k) {
         if (k > 0) LTV_TRY(h, enq_plant_ekf(h, nmpc, ei, B, dt_tick, s));
+        LTV_PROMOTE(h, nmpc, t0 + k * dt_tick, stream); // plant and sampler are launches of their own here: nothing to cut
         LTV_TRY(h, enq_refs_est(h, rs, B, t0 + k * dt_tick, ei.est_pose, s));
         LTV_TRY(h, enq_solve(h, B, n_relin, du_th, (k == 0 && reset) ? 1 : 0, s, ei.est_pose));
     }

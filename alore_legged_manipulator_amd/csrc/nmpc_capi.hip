@@ -114,6 +114,7 @@ int alore_nmpc_destroy(alore_nmpc_handle h)
     h->tp.release();
     h->forks.release();
     h->refs.release();
+    h->handoff.release();
     h->poly.release();
     h->timing.release();
     h->pinned.release();

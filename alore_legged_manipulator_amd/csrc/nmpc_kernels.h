@@ -129,8 +129,9 @@ struct PolyBatch {
 // workspace doubles per (message, dimension) thread of the spline kernel: knot positions P + 1, inverted Schur
 // blocks 3 P, right-hand side 2 P, coefficients 6 P
 inline __host__ __device__ int traj_ws_doubles(int P) { return 12 * P + 1; }
+// status: null, or the per-slot status slab of a pending store (traj_handoff.h: kWritten / kTooManyPieces / kTooManyCheckpoints)
 hipError_t launch_traj_build(const RefStore& s, const PolyBatch& m, int count, double res, int res_int, double* knot_ws,
-                             int* n_panels, double* inc, int* overflow, hipStream_t st);
+                             int* n_panels, double* inc, int* overflow, hipStream_t st, int* status = nullptr);
 hipError_t launch_iterate_reset(const alore_nmpc_batch& b, int B, int N, const double* pose, const unsigned char* mask, hipStream_t st);
 hipError_t launch_ref_eval(const RefStore& s, int B, double now, double* out /* [B][4] */, hipStream_t st);
 // the planner's device-resident results (mirror of alore_backend_device_view, include/alore_backend.h)
@@ -142,8 +143,24 @@ struct BackendView {
     const double* start_xytheta;
     const int* ok;
 };
+// mask: null, or DEVICE memory: slot t is written when the int at (char*)mask + t * mask_stride is not 0 (and the plan has ok != 0);
+// status: null, or the per-slot status slab (traj_handoff.h); overflow may be null when status is given
 hipError_t launch_traj_from_backend(const RefStore& s, const BackendView& v, int count, double t0, double res, int res_int, double xv,
-                                    int* n_panels, double* inc, int* overflow, hipStream_t st);
+                                    int* n_panels, double* inc, int* overflow, hipStream_t st, const int* mask = nullptr, int mask_stride = 0,
+                                    int* status = nullptr);
+// promotion of pending trajectories (traj_handoff.hip): active <- pending where traj_handoff::promote_due holds
+struct PromoteArgs {
+    RefStore act, pen;
+    int* promotions;     // [B] promotions of every robot so far
+    const int* robots;   // null: wavefront t works on slot t; else on slot robots[t] (device memory)
+    const int* mask;     // forced mode: null, or only the t whose int at (char*)mask + t * mask_stride is not 0 ...
+    const int* ok;       // ... and, where given, whose ok[t] is not 0
+    int mask_stride;
+    int count;           // wavefronts
+    int forced;          // 1: whatever the start time (mpc.cpp:151-156: a new message promotes the one still pending)
+    double now;
+};
+hipError_t launch_traj_promote(const PromoteArgs& a, hipStream_t st);
 // the plant step of tick t with the completion of tick t + 1's references (ref_sampler_device.h: plant_ahead_one)
 struct PlantAhead {
     const float* u;        // [B][N][2] inputs the solve of tick t left

@@ -12,6 +12,20 @@
 
 using namespace nmpc_capi;
 
+int nmpc_capi::promote_if_due(alore_nmpc_handle h, double now, hipStream_t s)
+{
+    if (!h->handoff.times.due(now)) return ALORE_NMPC_OK;
+    nmpc::PromoteArgs a{};
+    a.act = h->refs.store;
+    a.pen = h->handoff.pending;
+    a.promotions = h->handoff.d_promotions;
+    a.count = h->refs.B;
+    a.now = now;
+    HIP_TRY(h, nmpc::launch_traj_promote(a, s));
+    h->handoff.times.promoted(now);
+    return ALORE_NMPC_OK;
+}
+
 extern "C" {
 
 int alore_nmpc_refs_init(alore_nmpc_handle h, int B, int max_pieces, int max_checkpoints)
@@ -90,14 +104,69 @@ PolyLayout poly_layout(int chunk, int P)
     L.end = o;
     return L;
 }
-} // namespace
 
-int alore_nmpc_refs_set_polynomes(alore_nmpc_handle h, int count, const int* robots, const alore_polynome* msgs,
-                                  double state_seq_res, int integral_res_int, void* stream)
+// the pending store, its status slab and the promotion counters: allocated by the first call that needs them
+int ensure_pending(alore_nmpc_handle h)
 {
+    if (h->handoff.pending.dur) return ALORE_NMPC_OK;
+    const int B = h->refs.B, P = h->refs.store.P, Cn = h->refs.store.C;
+    nmpc::RefStore& p = h->handoff.pending;
+    struct Want { void** p; size_t bytes; };
+    const Want want[] = {
+        {(void**)&p.dur, sizeof(double) * B * P},
+        {(void**)&p.coef, sizeof(double) * B * P * 12},
+        {(void**)&p.ckpt, sizeof(double) * B * Cn * 2},
+        {(void**)&p.meta, sizeof(double) * B * 8},
+        {(void**)&h->handoff.d_promotions, sizeof(int) * B},
+        {(void**)&h->handoff.d_status, sizeof(int) * B},
+    };
+    hipError_t e = hipSuccess;
+    for (const Want& w : want) { // zeroed: every pending entry invalid, no promotion yet
+        e = hipMalloc(w.p, w.bytes);
+        if (e == hipSuccess) e = hipMemset(*w.p, 0, w.bytes);
+        if (e != hipSuccess) break;
+    }
+    if (e == hipSuccess) {
+        const std::vector<int> ones((size_t)B, traj_handoff::kNotAddressed);
+        e = hipMemcpy(h->handoff.d_status, ones.data(), sizeof(int) * B, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) { // a retry must see "not allocated"
+        for (const Want& w : want) {
+            if (*w.p) (void)hipFree(*w.p);
+            *w.p = nullptr;
+        }
+        return fail(h, ALORE_NMPC_E_NOMEM, "pending trajectory store: hipMalloc", e);
+    }
+    p.P = P;
+    p.C = Cn;
+    return ALORE_NMPC_OK;
+}
+
+nmpc::PromoteArgs promote_args(alore_nmpc_handle h, int count, double now, bool forced)
+{
+    nmpc::PromoteArgs a{};
+    a.act = h->refs.store;
+    a.pen = h->handoff.pending;
+    a.promotions = h->handoff.d_promotions;
+    a.count = count;
+    a.now = now;
+    a.forced = forced ? 1 : 0;
+    return a;
+}
+
+// alore_nmpc_refs_set_polynomes (pending = false) and alore_nmpc_refs_set_pending_polynomes: the same staging and the same three
+// kernels; the pending route targets the pending store, has the forced promotion of the addressed slots in front (mpc.cpp:151-156)
+// and reports per slot through the status slab instead of one synchronised flag
+int set_polynomes(alore_nmpc_handle h, int count, const int* robots, const alore_polynome* msgs, double state_seq_res, int integral_res_int,
+                  void* stream, bool pending)
+{
+    const char* who = pending ? "refs_set_pending_polynomes: bad argument" : "refs_set_polynomes: bad argument";
     if (!h || !h->refs.store.dur || count < 0 || (count > 0 && (!robots || !msgs)) || !(state_seq_res > 0.0) || integral_res_int < 1)
-        return fail(h, ALORE_NMPC_E_INVALID, "refs_set_polynomes: bad argument");
+        return fail(h, ALORE_NMPC_E_INVALID, who);
     HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (pending)
+        if (int rc = ensure_pending(h)) return rc;
+    const nmpc::RefStore& store = pending ? h->handoff.pending : h->refs.store;
     hipStream_t s = (hipStream_t)stream;
     const int P = h->refs.store.P, CH = alore_nmpc_solver::PolyStaging::kChunk, Pi = (P > 1 ? P - 1 : 1);
     const PolyLayout Lmax = poly_layout(CH, P);
@@ -163,16 +232,36 @@ int alore_nmpc_refs_set_polynomes(alore_nmpc_handle h, int count, const int* rob
         pb.icr = reinterpret_cast<const double*>(h->poly.d_poly + L.icr);
         pb.t0 = reinterpret_cast<const double*>(h->poly.d_poly + L.t0);
         pb.P = P;
-        HIP_TRY(h, nmpc::launch_traj_build(h->refs.store, pb, n, state_seq_res, integral_res_int, h->poly.d_knot, h->poly.d_panels,
-                                           h->poly.d_inc, h->poly.d_overflow, s));
+        if (pending) {
+            nmpc::PromoteArgs pa = promote_args(h, n, 0.0, true);
+            pa.robots = pb.robot;
+            HIP_TRY(h, nmpc::launch_traj_promote(pa, s));
+            for (int i = 0; i < n; ++i) h->handoff.times.add(msgs[base + i].traj_start_time);
+        }
+        HIP_TRY(h, nmpc::launch_traj_build(store, pb, n, state_seq_res, integral_res_int, h->poly.d_knot, h->poly.d_panels,
+                                           h->poly.d_inc, h->poly.d_overflow, s, pending ? h->handoff.d_status : nullptr));
         HIP_TRY(h, hipStreamSynchronize(s)); // `pack` is reused by the next chunk
     }
+    if (pending) return ALORE_NMPC_OK; // what happened to a slot is in its status word
     int ov = 0;
     HIP_TRY(h, hipMemcpyAsync(&ov, h->poly.d_overflow, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     if (ov & 1) return fail(h, ALORE_NMPC_E_INVALID, "refs_set_polynomes: a message has more pieces than max_pieces (or none)");
     if (ov & 2) return fail(h, ALORE_NMPC_E_INVALID, "refs_set_polynomes: a trajectory needs more checkpoints than max_checkpoints");
     return ALORE_NMPC_OK;
+}
+} // namespace
+
+int alore_nmpc_refs_set_polynomes(alore_nmpc_handle h, int count, const int* robots, const alore_polynome* msgs,
+                                  double state_seq_res, int integral_res_int, void* stream)
+{
+    return set_polynomes(h, count, robots, msgs, state_seq_res, integral_res_int, stream, false);
+}
+
+int alore_nmpc_refs_set_pending_polynomes(alore_nmpc_handle h, int count, const int* robots, const alore_polynome* msgs,
+                                          double state_seq_res, int integral_res_int, void* stream)
+{
+    return set_polynomes(h, count, robots, msgs, state_seq_res, integral_res_int, stream, true);
 }
 
 int alore_nmpc_refs_set_from_backend(alore_nmpc_handle h, const void* view, int count, double traj_start_time, double xv,
@@ -210,16 +299,117 @@ int alore_nmpc_refs_set_from_backend(alore_nmpc_handle h, const void* view, int 
     return ALORE_NMPC_OK;
 }
 
+int alore_nmpc_refs_set_pending_from_backend(alore_nmpc_handle h, const void* view, int count, const int* mask, int mask_stride_bytes,
+                                             double traj_start_time, double xv, double state_seq_res, int integral_res_int, void* stream)
+{
+    const alore_backend_device_view* v = static_cast<const alore_backend_device_view*>(view);
+    if (!h || !h->refs.store.dur || !v || count < 1 || count > h->refs.B || !(state_seq_res > 0.0) || integral_res_int < 1 ||
+        (mask && (mask_stride_bytes < (int)sizeof(int) || mask_stride_bytes % (int)sizeof(int))))
+        return fail(h, ALORE_NMPC_E_INVALID, "refs_set_pending_from_backend: bad argument");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = ensure_pending(h)) return rc;
+    // the workspace for the whole store at once: no later call allocates, whatever its count
+    if ((size_t)h->refs.B > h->poly.panels_cap) {
+        if (h->poly.d_panels_be) (void)hipFree(h->poly.d_panels_be);
+        h->poly.d_panels_be = nullptr;
+        h->poly.panels_cap = 0;
+        HIP_TRY(h, hipMalloc((void**)&h->poly.d_panels_be, sizeof(int) * h->refs.B));
+        h->poly.panels_cap = h->refs.B;
+    }
+    const size_t need = (size_t)h->refs.B * h->refs.store.C * integral_res_int * 2;
+    if (need > h->poly.inc_doubles) {
+        if (h->poly.d_inc) (void)hipFree(h->poly.d_inc);
+        h->poly.d_inc = nullptr;
+        h->poly.inc_doubles = 0;
+        HIP_TRY(h, hipMalloc((void**)&h->poly.d_inc, sizeof(double) * need));
+        h->poly.inc_doubles = need;
+    }
+    const int stride = mask ? mask_stride_bytes : 0;
+    // mpc.cpp:151-156: an entry that is still pending in an addressed slot becomes active first, whatever its start time
+    nmpc::PromoteArgs pa = promote_args(h, count, 0.0, true);
+    pa.mask = mask; pa.mask_stride = stride; pa.ok = v->ok;
+    HIP_TRY(h, nmpc::launch_traj_promote(pa, s));
+    const nmpc::BackendView bv{v->max_pieces, v->n_pieces, v->T, v->coef, v->start_xytheta, v->ok};
+    HIP_TRY(h, nmpc::launch_traj_from_backend(h->handoff.pending, bv, count, traj_start_time, state_seq_res, integral_res_int, xv,
+                                              h->poly.d_panels_be, h->poly.d_inc, nullptr, s, mask, stride, h->handoff.d_status));
+    h->handoff.times.add(traj_start_time);
+    return ALORE_NMPC_OK;
+}
+
+int alore_nmpc_refs_promote(alore_nmpc_handle h, int B, double now, void* stream)
+{
+    if (!h || !h->refs.store.dur || B <= 0 || B > h->refs.B || now != now) return fail(h, ALORE_NMPC_E_INVALID, "refs_promote: bad argument");
+    if (!h->handoff.pending.dur) return ALORE_NMPC_OK; // no pending entry was ever written
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, nmpc::launch_traj_promote(promote_args(h, B, now, false), (hipStream_t)stream));
+    if (B == h->refs.B) h->handoff.times.promoted(now);
+    return ALORE_NMPC_OK;
+}
+
+int alore_nmpc_refs_pending_status(alore_nmpc_handle h, int B, int* status, double* start_time, int* valid, int* promotions, void* stream)
+{
+    if (!h || !h->refs.store.dur || B <= 0 || B > h->refs.B) return fail(h, ALORE_NMPC_E_INVALID, "refs_pending_status: bad argument");
+    if (!h->handoff.pending.dur) { // nothing pending, nothing promoted, no slot addressed
+        for (int b = 0; b < B; ++b) {
+            if (status) status[b] = traj_handoff::kNotAddressed;
+            if (start_time) start_time[b] = 0.0;
+            if (valid) valid[b] = 0;
+            if (promotions) promotions[b] = 0;
+        }
+        return ALORE_NMPC_OK;
+    }
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<double> meta((size_t)B * 8);
+    HIP_TRY(h, hipMemcpyAsync(meta.data(), h->handoff.pending.meta, sizeof(double) * B * 8, hipMemcpyDeviceToHost, s));
+    if (status) HIP_TRY(h, hipMemcpyAsync(status, h->handoff.d_status, sizeof(int) * B, hipMemcpyDeviceToHost, s));
+    if (promotions) HIP_TRY(h, hipMemcpyAsync(promotions, h->handoff.d_promotions, sizeof(int) * B, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    for (int b = 0; b < B; ++b) {
+        if (start_time) start_time[b] = meta[(size_t)b * 8];
+        if (valid) valid[b] = meta[(size_t)b * 8 + 6] != 0.0 ? 1 : 0;
+    }
+    return ALORE_NMPC_OK;
+}
+
+int alore_nmpc_refs_pending_device(alore_nmpc_handle h, alore_refs_pending_view* out)
+{
+    if (!h || !h->refs.store.dur || !out) return fail(h, ALORE_NMPC_E_INVALID, "refs_pending_device: bad argument");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (int rc = ensure_pending(h)) return rc;
+    out->status = h->handoff.d_status;
+    out->promotions = h->handoff.d_promotions;
+    out->pending_meta = h->handoff.pending.meta;
+    out->active_meta = h->refs.store.meta;
+    return ALORE_NMPC_OK;
+}
+
+namespace {
+int download_slot(alore_nmpc_handle h, const nmpc::RefStore& st, int robot, double* meta8, double* durations, double* coeffs, double* ckpt_xy)
+{
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipDeviceSynchronize());
+    if (meta8) HIP_TRY(h, hipMemcpy(meta8, st.meta + (size_t)robot * 8, sizeof(double) * 8, hipMemcpyDeviceToHost));
+    if (durations) HIP_TRY(h, hipMemcpy(durations, st.dur + (size_t)robot * st.P, sizeof(double) * st.P, hipMemcpyDeviceToHost));
+    if (coeffs) HIP_TRY(h, hipMemcpy(coeffs, st.coef + (size_t)robot * st.P * 12, sizeof(double) * st.P * 12, hipMemcpyDeviceToHost));
+    if (ckpt_xy) HIP_TRY(h, hipMemcpy(ckpt_xy, st.ckpt + (size_t)robot * st.C * 2, sizeof(double) * st.C * 2, hipMemcpyDeviceToHost));
+    return ALORE_NMPC_OK;
+}
+} // namespace
+
 int alore_nmpc_refs_download(alore_nmpc_handle h, int robot, double* meta8, double* durations, double* coeffs, double* ckpt_xy)
 {
     if (!h || !h->refs.store.dur || robot < 0 || robot >= h->refs.B) return fail(h, ALORE_NMPC_E_INVALID, "refs_download: bad argument");
+    return download_slot(h, h->refs.store, robot, meta8, durations, coeffs, ckpt_xy);
+}
+
+int alore_nmpc_refs_pending_download(alore_nmpc_handle h, int robot, double* meta8, double* durations, double* coeffs, double* ckpt_xy)
+{
+    if (!h || !h->refs.store.dur || robot < 0 || robot >= h->refs.B) return fail(h, ALORE_NMPC_E_INVALID, "refs_pending_download: bad argument");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    HIP_TRY(h, hipDeviceSynchronize());
-    if (meta8) HIP_TRY(h, hipMemcpy(meta8, h->refs.store.meta + (size_t)robot * 8, sizeof(double) * 8, hipMemcpyDeviceToHost));
-    if (durations) HIP_TRY(h, hipMemcpy(durations, h->refs.store.dur + (size_t)robot * h->refs.store.P, sizeof(double) * h->refs.store.P, hipMemcpyDeviceToHost));
-    if (coeffs) HIP_TRY(h, hipMemcpy(coeffs, h->refs.store.coef + (size_t)robot * h->refs.store.P * 12, sizeof(double) * h->refs.store.P * 12, hipMemcpyDeviceToHost));
-    if (ckpt_xy) HIP_TRY(h, hipMemcpy(ckpt_xy, h->refs.store.ckpt + (size_t)robot * h->refs.store.C * 2, sizeof(double) * h->refs.store.C * 2, hipMemcpyDeviceToHost));
-    return ALORE_NMPC_OK;
+    if (int rc = ensure_pending(h)) return rc;
+    return download_slot(h, h->handoff.pending, robot, meta8, durations, coeffs, ckpt_xy);
 }
 
 int alore_nmpc_refs_sample(alore_nmpc_handle h, const alore_nmpc_batch* dev, int B, double now, const double* est,
@@ -350,6 +540,7 @@ int alore_nmpc_closed_loop_tick(alore_nmpc_handle h, const alore_nmpc_batch* dev
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     const int N = h->cfg.N;
+    if (int rc = promote_if_due(h, now, s)) return rc; // mpc.cpp:177-182: a pending trajectory whose start time has passed is swapped in
     // CmdCallback: references from the measured pose, one real-time iteration, command = input column delay_num
     HIP_TRY(h, nmpc::launch_ref_sample(h->refs.store, *dev, B, N, (double)h->cfg.dt, now, h->refs.d_est, h->refs.d_icr, h->refs.d_goal, h->refs.d_psi, 1, s));
     const int rc = alore_nmpc_rti(h, dev, B, 1, stream);
@@ -399,16 +590,19 @@ int alore_nmpc_input_column(alore_nmpc_handle h, const alore_nmpc_batch* dev, in
     return ALORE_NMPC_OK;
 }
 
-int alore_nmpc_closed_loop_run(alore_nmpc_handle h, const alore_nmpc_batch* dev, int B, double t0, double dt_tick, int n_ticks,
-                               int delay_num, void* stream)
+namespace {
+// ticks [first, first + n_ticks) of a run that started at t0, as a complete run: tick t of them has the time of tick first + t of the
+// whole run (traj_handoff::tick_time), never a time summed up from a shifted t0
+int run_segment(alore_nmpc_handle h, const alore_nmpc_batch* dev, int B, double t0, double dt_tick, int first, int n_ticks, int delay_num,
+                void* stream)
 {
-    if (n_ticks < 0 || !(dt_tick > 0.0)) return fail(h, ALORE_NMPC_E_INVALID, "closed_loop_run: bad argument");
+    auto time_of = [&](int t) { return traj_handoff::tick_time(t0, dt_tick, (long)first + t); };
     static const bool serial = [] { const char* e = getenv("ALORE_NMPC_CLOSED_LOOP_SERIAL"); return e && atoi(e) != 0; }();
     const bool ahead = !serial && n_ticks >= 3 && h && h->refs.has_plant && dev && dev->y && dev->yN && dev->x0 && B > 0 && B <= h->refs.B &&
                        delay_num >= 0 && nmpc::ref_sample_ahead_supported(h->cfg.N);
     if (!ahead) {
         for (int t = 0; t < n_ticks; ++t) {
-            const int rc = alore_nmpc_closed_loop_tick(h, dev, B, t0 + dt_tick * t, delay_num, stream);
+            const int rc = alore_nmpc_closed_loop_tick(h, dev, B, time_of(t), delay_num, stream);
             if (rc != ALORE_NMPC_OK) return rc;
         }
         return ALORE_NMPC_OK;
@@ -429,7 +623,7 @@ int alore_nmpc_closed_loop_run(alore_nmpc_handle h, const alore_nmpc_batch* dev,
     HIP_TRY(h, hipMemcpyAsync(h->refs.cl_y, dev->y, sizeof(float) * (size_t)B * N * 5, hipMemcpyDeviceToDevice, s));
     HIP_TRY(h, hipMemcpyAsync(h->refs.cl_yN, dev->yN, sizeof(float) * (size_t)B * 3, hipMemcpyDeviceToDevice, s));
     // tick 0 is sampled whole (od, x0 from the current pose)
-    HIP_TRY(h, nmpc::launch_ref_sample(h->refs.store, *dev, B, N, (double)h->cfg.dt, t0, h->refs.d_est, h->refs.d_icr, h->refs.d_goal, h->refs.d_psi, 1, s));
+    HIP_TRY(h, nmpc::launch_ref_sample(h->refs.store, *dev, B, N, (double)h->cfg.dt, time_of(0), h->refs.d_est, h->refs.d_icr, h->refs.d_goal, h->refs.d_psi, 1, s));
     // per tick ONE launch: [plant step of tick t - 1 -> solve of tick t] beside [sampler of tick t + 1]
     auto plant_of = [&](int t, bool more) {
         const int cur = t & 1, nxt = cur ^ 1;
@@ -445,7 +639,7 @@ int alore_nmpc_closed_loop_run(alore_nmpc_handle h, const alore_nmpc_batch* dev,
         a.vw = h->refs.d_vw;
         a.psi_rel = more ? h->refs.cl_psi[nxt] : nullptr;
         a.p = h->refs.plant;
-        a.now = t0 + dt_tick * t;
+        a.now = time_of(t);
         a.B = B; a.N = N; a.node = node;
         return a;
     };
@@ -459,7 +653,7 @@ int alore_nmpc_closed_loop_run(alore_nmpc_handle h, const alore_nmpc_batch* dev,
         sa.icr = h->refs.d_icr;
         sa.psi_rel = h->refs.cl_psi[nxt];
         sa.dt = (double)h->cfg.dt;
-        sa.now = t0 + dt_tick * (t + 1);
+        sa.now = time_of(t + 1);
         sa.B = more ? B : 0; // the last tick has nothing to sample for
         sa.N = N;
         bool sampled = false;
@@ -476,6 +670,43 @@ int alore_nmpc_closed_loop_run(alore_nmpc_handle h, const alore_nmpc_batch* dev,
         HIP_TRY(h, hipMemcpyAsync(const_cast<float*>(dev->yN), h->refs.cl_yN, sizeof(float) * (size_t)B * 3, hipMemcpyDeviceToDevice, s));
     }
     return ALORE_NMPC_OK;
+}
+} // namespace
+
+int alore_nmpc_closed_loop_run(alore_nmpc_handle h, const alore_nmpc_batch* dev, int B, double t0, double dt_tick, int n_ticks,
+                               int delay_num, void* stream)
+{
+    if (n_ticks < 0 || !(dt_tick > 0.0)) return fail(h, ALORE_NMPC_E_INVALID, "closed_loop_run: bad argument");
+    if (!h || !h->handoff.times.any()) return run_segment(h, dev, B, t0, dt_tick, 0, n_ticks, delay_num, stream);
+    // The fused run reads the store for two ticks at once (the ahead sampler of tick t + 1 beside the plant step of tick t - 1), so
+    // a promotion cannot go between two of its launches: the run is cut where one is due, every part runs as a complete run (with its
+    // trailing plant step and the copy back of y / yN), and the promotion goes between the parts (traj_handoff.h: split_run)
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const std::vector<double> starts = h->handoff.times.t;
+    for (const traj_handoff::Segment& g : traj_handoff::split_run(t0, dt_tick, n_ticks, starts.data(), starts.size())) {
+        if (g.promote)
+            if (int rc = promote_if_due(h, traj_handoff::tick_time(t0, dt_tick, g.first), (hipStream_t)stream)) return rc;
+        if (int rc = run_segment(h, dev, B, t0, dt_tick, g.first, g.count, delay_num, stream)) return rc;
+    }
+    return ALORE_NMPC_OK;
+}
+
+// internal (not in the public header), for the LTV-MPC loops on this handle's store (ltv_mpc_capi.hip): the promotion that goes in
+// front of a sampler at `now` (enqueued only while a pending start time is outstanding; nonzero: a HIP error), and the outstanding
+// start times, for the run splitter
+int alore_nmpc_internal_promote_if_due(void* nmpc_handle, double now, void* stream)
+{
+    alore_nmpc_handle h = static_cast<alore_nmpc_handle>(nmpc_handle);
+    if (!h || !h->handoff.times.any()) return 0;
+    return promote_if_due(h, now, (hipStream_t)stream);
+}
+int alore_nmpc_internal_pending_times(void* nmpc_handle, const double** starts, size_t* n)
+{
+    alore_nmpc_handle h = static_cast<alore_nmpc_handle>(nmpc_handle);
+    if (!h || !starts || !n) return -1;
+    *starts = h->handoff.times.t.data();
+    *n = h->handoff.times.t.size();
+    return 0;
 }
 
 // internal (not in the public header): the trajectory store of a handle, for the LTV-MPC reference sampler (ltv_mpc.hip)

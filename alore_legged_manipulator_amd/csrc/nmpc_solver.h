@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "nmpc_kernels.h"
+#include "traj_handoff.h"
 
 // The handle: the configuration and the per-call settings, then one member per subsystem that owns device or host resources, each
 // with the function that gives them back (alore_nmpc_destroy calls them).
@@ -93,6 +94,24 @@ struct alore_nmpc_solver {
             if (d_mask) (void)hipFree(d_mask);
         }
     } refs;
+
+    // hand-over to a replanned trajectory (alore_nmpc_refs_set_pending_*, alore_nmpc_refs_promote; traj_handoff.h): a second store
+    // with the P and C of refs.store, allocated by the first call that needs it
+    struct Handoff {
+        nmpc::RefStore pending{};
+        int* d_status = nullptr;      // [B] traj_handoff::kWritten ... of the last set_pending call that addressed the slot
+        int* d_promotions = nullptr;  // [B]
+        traj_handoff::PendingTimes times; // start times handed in and not yet passed by a promotion over every robot
+        void release()
+        {
+            if (pending.dur) (void)hipFree(pending.dur);
+            if (pending.coef) (void)hipFree(pending.coef);
+            if (pending.ckpt) (void)hipFree(pending.ckpt);
+            if (pending.meta) (void)hipFree(pending.meta);
+            if (d_status) (void)hipFree(d_status);
+            if (d_promotions) (void)hipFree(d_promotions);
+        }
+    } handoff;
 
     // Polynome -> store on the device: staging + workspace for chunks of kChunk messages
     struct PolyStaging {
@@ -353,6 +372,10 @@ inline int grow_stage(alore_nmpc_handle h, char*& buf, size_t& cap, size_t need)
 // *co_done says whether it did
 int rti_one(alore_nmpc_handle h, const alore_nmpc_batch* dev, int B, int n_sqp, void* stream, int B_in_flight, const nmpc::AheadSampler* co = nullptr,
             bool* co_done = nullptr, const nmpc::PlantAhead* plant = nullptr);
+
+// What every sampler of the closed loops has in front of it (nmpc_refs_capi.hip): while the handle has an outstanding pending start
+// time below `now`, the promotion for `now` over all robots of the store; otherwise nothing is enqueued
+int promote_if_due(alore_nmpc_handle h, double now, hipStream_t s);
 
 } // namespace nmpc_capi
 #endif

@@ -16,6 +16,7 @@
 
 #include "minco_spline.h"
 #include "ref_sampler_device.h"
+#include "traj_handoff.h"
 
 namespace nmpc {
 
@@ -92,7 +93,7 @@ hipError_t launch_ref_eval(const RefStore& s, int B, double now, double* out, hi
 //      2 x 2 blocks, instead of the reference's 6M x 6M band LU), Simpson panels (one thread per (message,
 //      panel): independent), checkpoints (one thread per message: the running sum in the reference's order).
 __global__ void traj_spline_kernel(RefStore s, PolyBatch m, int count, double res, int res_int, double* knot_ws,
-                                   int* n_panels, int* overflow)
+                                   int* n_panels, int* overflow, int* status)
 {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= 2 * count) return;
@@ -101,7 +102,7 @@ __global__ void traj_spline_kernel(RefStore s, PolyBatch m, int count, double re
     double* meta = s.meta + (size_t)r * 8;
     if (d == 0) n_panels[t] = 0;
     if (M < 1 || M > s.P) {
-        if (d == 0) { meta[6] = 0.0; atomicOr(overflow, 1); }
+        if (d == 0) { meta[6] = 0.0; atomicOr(overflow, 1); if (status) status[r] = traj_handoff::kTooManyPieces; }
         return;
     }
     const double* T = m.t_pts + (size_t)t * m.P;
@@ -130,7 +131,8 @@ __global__ void traj_spline_kernel(RefStore s, PolyBatch m, int count, double re
     const double fine = res / res_int;
     const int seq = (int)floor(total / fine);
     const int nck = 1 + seq / res_int;
-    if (nck > s.C) { meta[6] = 0.0; atomicOr(overflow, 2); return; }
+    if (nck > s.C) { meta[6] = 0.0; atomicOr(overflow, 2); if (status) status[r] = traj_handoff::kTooManyCheckpoints; return; }
+    if (status) status[r] = traj_handoff::kWritten;
     n_panels[t] = seq;
     meta[0] = m.t0[t]; meta[1] = total; meta[2] = m.icr[(size_t)t * 3 + 2]; meta[3] = res;
     meta[4] = (double)M; meta[5] = (double)nck; meta[6] = 1.0; meta[7] = 0.0;
@@ -178,11 +180,11 @@ __global__ void traj_checkpoint_kernel(RefStore s, PolyBatch m, int count, int r
 }
 
 hipError_t launch_traj_build(const RefStore& s, const PolyBatch& m, int count, double res, int res_int, double* knot_ws,
-                             int* n_panels, double* inc, int* overflow, hipStream_t st)
+                             int* n_panels, double* inc, int* overflow, hipStream_t st, int* status)
 {
     const int max_panels = s.C * res_int;
     hipLaunchKernelGGL(traj_spline_kernel, dim3((2 * count + 63) / 64), dim3(64), 0, st, s, m, count, res, res_int, knot_ws,
-                       n_panels, overflow);
+                       n_panels, overflow, status);
     const long total = (long)count * max_panels;
     hipLaunchKernelGGL(traj_panel_kernel, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, st, s, m, count, res, res_int,
                        n_panels, max_panels, inc);
@@ -196,8 +198,10 @@ hipError_t launch_traj_build(const RefStore& s, const PolyBatch& m, int count, d
 //      Polynome -> MpcController::TrajCallback -> TrajAnal::setTraj re-solves the spline): the coefficients the
 //      optimiser ended with ARE that spline (same knot system, tests/test_backend_gpu.py), so they are copied, and
 //      only the Simpson checkpoints are built.  One thread per (problem, piece) for the copy.
+//      mask / status (alore_nmpc_refs_set_pending_from_backend): a slot whose mask word is 0 is left alone, and what happened to a
+//      slot that the mask addresses is written to its status word instead of the one overflow flag; both null: the kernel of alore_nmpc_refs_set_from_backend.
 __global__ void traj_from_backend_kernel(RefStore s, BackendView v, int count, double t0, double res, int res_int, double xv,
-                                         int* n_panels, int* overflow)
+                                         int* n_panels, int* overflow, const int* mask, int mask_stride, int* status)
 {
     const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= (long)count * v.P) return;
@@ -205,12 +209,17 @@ __global__ void traj_from_backend_kernel(RefStore s, BackendView v, int count, d
     const int M = v.n_pieces[t];
     double* meta = s.meta + (size_t)t * 8;
     const bool ok = v.ok[t] != 0 && M >= 1 && M <= s.P;
+    if (mask && *(const int*)((const char*)mask + (size_t)t * mask_stride) == 0) {
+        if (i == 0) n_panels[t] = 0; // not addressed: its pending entry, its active entry and its status word stay
+        return;
+    }
     if (i == 0) {
         n_panels[t] = 0;
+        if (status) status[t] = ok ? traj_handoff::kWritten : (v.ok[t] != 0 ? traj_handoff::kTooManyPieces : traj_handoff::kNotAddressed);
         // a failed replan leaves the robot on the trajectory it is tracking: MSPlanner::minco_plan returns false before
         // final_traj_ is replaced (optimizer.cpp:204-209), nothing is published and the controller carries on.  Only
         // a plan that succeeded but does not fit the store invalidates the slot (and is reported).
-        if (!ok && v.ok[t] != 0) { meta[6] = 0.0; atomicOr(overflow, 1); }
+        if (!ok && v.ok[t] != 0) { meta[6] = 0.0; if (overflow) atomicOr(overflow, 1); }
     }
     if (!ok || i >= M) return;
     s.dur[(size_t)t * s.P + i] = v.T[(size_t)t * v.P + i];
@@ -223,7 +232,7 @@ __global__ void traj_from_backend_kernel(RefStore s, BackendView v, int count, d
     const double fine = res / res_int;
     const int seq = (int)floor(total / fine);
     const int nck = 1 + seq / res_int;
-    if (nck > s.C) { meta[6] = 0.0; atomicOr(overflow, 2); return; }
+    if (nck > s.C) { meta[6] = 0.0; if (overflow) atomicOr(overflow, 2); if (status) status[t] = traj_handoff::kTooManyCheckpoints; return; }
     n_panels[t] = seq;
     meta[0] = t0; meta[1] = total; meta[2] = xv; meta[3] = res;
     meta[4] = (double)M; meta[5] = (double)nck; meta[6] = 1.0; meta[7] = 0.0;
@@ -232,12 +241,12 @@ __global__ void traj_from_backend_kernel(RefStore s, BackendView v, int count, d
 }
 
 hipError_t launch_traj_from_backend(const RefStore& s, const BackendView& v, int count, double t0, double res, int res_int, double xv,
-                                    int* n_panels, double* inc, int* overflow, hipStream_t st)
+                                    int* n_panels, double* inc, int* overflow, hipStream_t st, const int* mask, int mask_stride, int* status)
 {
     const int max_panels = s.C * res_int;
     const long threads = (long)count * v.P;
     hipLaunchKernelGGL(traj_from_backend_kernel, dim3((unsigned)((threads + 127) / 128)), dim3(128), 0, st, s, v, count, t0, res, res_int,
-                       xv, n_panels, overflow);
+                       xv, n_panels, overflow, mask, mask_stride, status);
     PolyBatch m{};
     m.robot = nullptr; // identity: problem t -> store slot t
     const long total = (long)count * max_panels;

@@ -290,6 +290,9 @@ class BatchedNmpc:
 
     def refs_set_polynomes(self, robots, msgs, state_seq_res: float = 0.1, integral_res_int: int = 4) -> None:
         """msgs: objects with the fields of Polynome.msg (alore_legged_manipulator_amd.host.Polynome)."""
+        self._set_polynomes(self.lib.alore_nmpc_refs_set_polynomes, robots, msgs, state_seq_res, integral_res_int)
+
+    def _set_polynomes(self, call, robots, msgs, state_seq_res, integral_res_int) -> None:
         n = len(msgs)
         arr = (_lib.PolynomeMsg * n)()
         keep = []
@@ -308,14 +311,47 @@ class BatchedNmpc:
                 q.start_position[k] = float(m.start_position[k]); q.ICR[k] = float(m.ICR[k])
             q.traj_start_time = float(m.traj_start_time)
         rb = np.ascontiguousarray(robots, np.int32)
-        self._check(self.lib.alore_nmpc_refs_set_polynomes(self.h, n, rb.ctypes.data, C.addressof(arr) if n else None,
-                                                           float(state_seq_res), int(integral_res_int), self._stream()))
+        self._check(call(self.h, n, rb.ctypes.data, C.addressof(arr) if n else None, float(state_seq_res), int(integral_res_int),
+                         self._stream()))
 
-    def refs_download(self, robot: int) -> dict:
+    # -- hand-over to a replanned trajectory at its start time (include/alore_nmpc.h: alore_nmpc_refs_set_pending_*, _promote)
+    def refs_set_pending_polynomes(self, robots, msgs, state_seq_res: float = 0.1, integral_res_int: int = 4) -> None:
+        """refs_set_polynomes into the PENDING slots: tracked from msg.traj_start_time on; overflows go to refs_pending_status."""
+        self._set_polynomes(self.lib.alore_nmpc_refs_set_pending_polynomes, robots, msgs, state_seq_res, integral_res_int)
+
+    def refs_set_pending_from_backend(self, planner, count: int | None = None, mask=None, traj_start_time: float = 0.0, xv: float = 0.0,
+                                      state_seq_res: float = 0.1, integral_res_int: int = 4) -> None:
+        """Pending slots <- the plans of a BatchedMSPlanner, device to device, nothing waits.  mask: int32 DEVICE tensor (count,) or
+        None = every slot; a slot is written when its mask word is not 0 and its plan has ok != 0."""
+        view = planner.device_view()
+        n = int(count or planner.count)
+        if mask is not None and not (mask.is_cuda and mask.dtype == self.torch.int32 and mask.dim() == 1 and mask.numel() >= n):
+            raise ValueError("mask: an int32 device tensor with a word per slot")
+        self._check(self.lib.alore_nmpc_refs_set_pending_from_backend(
+            self.h, C.addressof(view), n, None if mask is None else mask.data_ptr(), 0 if mask is None else mask.stride(0) * 4,
+            float(traj_start_time), float(xv), float(state_seq_res), int(integral_res_int), self._stream()))
+
+    def refs_promote(self, now: float) -> None:
+        """active <- pending for every robot whose pending entry is valid and now > its start time (strict).  Asynchronous."""
+        self._check(self.lib.alore_nmpc_refs_promote(self.h, self.B, float(now), self._stream()))
+
+    def refs_pending_status(self) -> dict:
+        """status (0 written, 1 not addressed, -1 / -2 too many pieces / checkpoints), start_time, valid, promotions.  Synchronises."""
+        st = np.zeros(self.B, np.int32); t0 = np.zeros(self.B); va = np.zeros(self.B, np.int32); pr = np.zeros(self.B, np.int32)
+        self._check(self.lib.alore_nmpc_refs_pending_status(self.h, self.B, st.ctypes.data, t0.ctypes.data, va.ctypes.data, pr.ctypes.data,
+                                                            self._stream()))
+        return {"status": st, "start_time": t0, "valid": va.astype(bool), "promotions": pr}
+
+    def refs_pending_view(self) -> "_lib.RefsPendingView":
+        v = _lib.RefsPendingView()
+        self._check(self.lib.alore_nmpc_refs_pending_device(self.h, C.byref(v)))
+        return v
+
+    def refs_download(self, robot: int, pending: bool = False) -> dict:
         P, Cn = self._refs_shape
         meta = np.zeros(8); dur = np.zeros(P); coef = np.zeros((P, 2, 6)); ck = np.zeros((Cn, 2))
-        self._check(self.lib.alore_nmpc_refs_download(self.h, int(robot), meta.ctypes.data, dur.ctypes.data,
-                                                      coef.ctypes.data, ck.ctypes.data))
+        call = self.lib.alore_nmpc_refs_pending_download if pending else self.lib.alore_nmpc_refs_download
+        self._check(call(self.h, int(robot), meta.ctypes.data, dur.ctypes.data, coef.ctypes.data, ck.ctypes.data))
         n, c = int(meta[4]), int(meta[5])
         return {"start_time": meta[0], "duration": meta[1], "xv": meta[2], "res": meta[3], "valid": bool(meta[6]),
                 "durations": dur[:n], "coeffs": coef[:n], "checkpoints": ck[:c]}

@@ -261,6 +261,15 @@ int alore_backend_predicted_state_device(alore_backend_handle h, int count, doub
  * have left the host). */
 int alore_backend_plan_masked(alore_backend_handle h, int count, const int *mask, int mask_stride_bytes, void *stream);
 
+/* The delivery mask of a replan cycle (check -> predict -> search -> set paths -> plan_masked), on DEVICE memory in stream order:
+ * out_mask[b] = 1 where the last alore_backend_check_plans flags a collision AND the search status of slot b is
+ * ALORE_BE_SEARCH_OK AND its build status is ALORE_BE_BUILD_OK AND its plan has ok != 0; else 0.  A flagged slot whose search or
+ * build failed is planned again by alore_backend_plan_masked from its OLD problem: without this mask that plan would be delivered
+ * to the controllers under a new start time (alore_nmpc_refs_set_pending_from_backend takes the mask as it lies).
+ * A robot whose replan failed keeps its colliding trajectory: the reference goes to EMERGENCY_STOP there
+ * (plan_manager.hpp:662-666); stopping it stays with the caller, who reads the collision words and this mask. */
+int alore_backend_replan_mask(alore_backend_handle h, int count, int *out_mask, void *stream);
+
 /* ---- the resident occupancy map: point clouds in, ESDF out, on the device ------------------------------------- */
 /* The half of plan_env::SDFmap that runs before updateESDF2d (sdf_map.cpp: updateOccupancyCallback :35-130, raycastProcess
  * :132-175, updateOccupancyMap :281-314, RemoveOutliers :316-350), then updateESDF2d itself, on a map that stays on the device:

@@ -341,6 +341,58 @@ int alore_nmpc_refs_set_polynomes(alore_nmpc_handle h, int count, const int *rob
  * MSPlanner::minco_plan fails (optimizer.cpp:204-209: nothing is published).  Synchronises the stream; errors as alore_nmpc_refs_set_polynomes. */
 int alore_nmpc_refs_set_from_backend(alore_nmpc_handle h, const void *view, int count, double traj_start_time, double xv,
                                      double state_seq_res, int integral_res_int, void *stream);
+/* ---- hand-over to a replanned trajectory at its start time ---------------------------------------------------------
+ * The reference plans from the state predicted at current + max_replan_time and stamps the message with that time
+ * (plan_manager.hpp:585-588, 686-691); the controller keeps the new trajectory in new_traj_ and goes on tracking traj_
+ * until now > new_traj_start_time_ (nmpc_controller/src/mpc.cpp:177-182).  Here every robot has a PENDING slot beside its
+ * active one (a second store of the same layout, allocated by the first call below; a handle that never uses them allocates
+ * and launches nothing).  The two set_pending calls write pending entries in stream order and leave the active entries
+ * alone; alore_nmpc_refs_promote, and every closed-loop tick by itself, makes a pending entry active once its start time
+ * has passed -- by copying it (csrc/traj_handoff.hip), so that no sampler reads through an index.
+ * A slot whose pending entry is still valid: the older entry becomes active first, whatever its start time, and then the
+ * new one is written (mpc.cpp:151-156).
+ * Ordering: stream order only.  A sampler of this store on ANOTHER stream is the caller's to order against these calls.
+ * Deviation: a robot with no active trajectory and a valid pending entry stays idle until its promotion (its slot is
+ * invalid and the samplers skip it), where the reference would sample an empty traj_.  Its cold start after the promotion
+ * is the caller's (alore_nmpc_closed_loop_reset); the promotion counters say which robots.
+ * Status word of a slot: what the last set_pending call that ADDRESSED it did -- a robot that a message call does not name and a
+ * slot whose mask word is 0 keep their word, so an overflow stays readable until the slot is addressed again.
+ * An overflow leaves the pending entry invalid and writes nothing to the active entry; an OLDER pending entry of that slot has
+ * become active all the same (the forced promotion runs in front of the build, as the reference promotes before it parses). */
+#define ALORE_NMPC_PENDING_WRITTEN 0
+#define ALORE_NMPC_PENDING_NOT_ADDRESSED 1       /* never addressed, or addressed by the mask with a plan that has ok = 0 */
+#define ALORE_NMPC_PENDING_TOO_MANY_PIECES (-1)  /* more pieces than max_pieces (or none) */
+#define ALORE_NMPC_PENDING_TOO_MANY_CHECKPOINTS (-2)
+/* TrajCallback for the message route: alore_nmpc_refs_set_polynomes (same staging, same three kernels) into the pending
+ * slots, start time = msgs[i].traj_start_time.  Overflows do not fail the call: they set the slot's status word.  Host
+ * pointers; the call synchronises the stream once per chunk of 2048 messages (its host staging is reused), which waits for
+ * whatever was enqueued on the stream before.  A robot may be named ONCE per call (two wavefronts would race on its slot, as in
+ * alore_nmpc_refs_set_polynomes): two messages in a row for one robot are two calls. */
+int alore_nmpc_refs_set_pending_polynomes(alore_nmpc_handle h, int count, const int *robots, const alore_polynome *msgs,
+                                          double state_seq_res, int integral_res_int, void *stream);
+/* The planner route, device to device and without any wait: as alore_nmpc_refs_set_from_backend, but slot t (t < count) is
+ * written only when the int at (char*)mask + t * mask_stride_bytes is not 0 (mask: DEVICE memory, read as
+ * alore_backend_set_paths reads its mask; NULL = every slot) and the plan has ok != 0.  Every other slot keeps its pending
+ * and its active entry bit for bit.  Nothing is allocated after the first call, nothing but the arguments crosses the bus. */
+int alore_nmpc_refs_set_pending_from_backend(alore_nmpc_handle h, const void *view, int count, const int *mask, int mask_stride_bytes,
+                                             double traj_start_time, double xv, double state_seq_res, int integral_res_int,
+                                             void *stream);
+/* active <- pending for every robot b < B with a valid pending entry and now > its start time (strict, as the reference);
+ * the pending entry becomes invalid and the robot's promotion counter goes up by one.  Asynchronous. */
+int alore_nmpc_refs_promote(alore_nmpc_handle h, int B, double now, void *stream);
+/* status [B], pending start times [B], validity flags [B], promotion counters [B] to the host (any may be NULL).  Synchronises. */
+int alore_nmpc_refs_pending_status(alore_nmpc_handle h, int B, int *status, double *start_time, int *valid, int *promotions,
+                                   void *stream);
+typedef struct alore_refs_pending_view { /* device pointers, valid until alore_nmpc_destroy */
+    const int *status;           /* [B] */
+    const int *promotions;       /* [B] */
+    const double *pending_meta;  /* [B][8]: start_time, duration, xv, state_seq_res, n_pieces, n_ckpt, valid, 0 */
+    const double *active_meta;   /* [B][8] */
+} alore_refs_pending_view;
+int alore_nmpc_refs_pending_device(alore_nmpc_handle h, alore_refs_pending_view *out);
+/* alore_nmpc_refs_download of the pending slot */
+int alore_nmpc_refs_pending_download(alore_nmpc_handle h, int robot, double *meta8, double *durations, double *coeffs,
+                                     double *ckpt_xy);
 /* read one slot back (tests, logging): meta8 = start_time, duration, xv, state_seq_res, n_pieces, n_ckpt,
  * valid, 0; durations [max_pieces]; coeffs [max_pieces][2][6]; ckpt_xy [max_checkpoints][2]; any may be NULL */
 int alore_nmpc_refs_download(alore_nmpc_handle h, int robot, double *meta8, double *durations, double *coeffs,
@@ -392,6 +444,12 @@ int alore_nmpc_closed_loop_tick(alore_nmpc_handle h, const alore_nmpc_batch *dev
  * 19 us per tick against 29.5 for the three kernels in a row.  ALORE_NMPC_CLOSED_LOOP_SERIAL=1 (diagnostic): the ticks one by one. */
 int alore_nmpc_closed_loop_run(alore_nmpc_handle h, const alore_nmpc_batch *dev, int B, double t0, double dt_tick,
                                int n_ticks, int delay_num, void *stream);
+/* Pending trajectories (alore_nmpc_refs_set_pending_*): alore_nmpc_closed_loop_tick and alore_nmpc_ekf_closed_loop_tick enqueue
+ * the promotion for their `now` in front of their sampler while the handle has a pending start time outstanding, and so do
+ * the alore_ltv_refs_from_store* calls on this handle.  The four *_run functions give, bit for bit, n_ticks such ticks: a fused
+ * run is cut at every tick whose time is the first to exceed an outstanding start time, the part in front runs as a complete
+ * run (trailing plant step, copy back of y / yN), the promotion follows, and the rest is a new run; every tick's time is
+ * t0 + dt_tick * t with the tick's index in the whole run.  Without a pending entry a run enqueues what it always did. */
 
 /* ---- the ICR EKF on the device, and the closed loop on its estimate ------------------------------------------------
  * The reference's controllers do not read the true pose: ~odom is /ICREKF/EKF_XYTheta and the od of every stage is
