@@ -131,6 +131,30 @@ class TaskViewC(C.Structure):
                 ("fields", C.c_void_p), ("sweeps", C.c_void_p)]
 
 
+class MapEditC(C.Structure):
+    """alore_backend_map_edit: a rectangle of the reference's paint* loops and the state it writes"""
+    _fields_ = [("cx", C.c_double), ("cy", C.c_double), ("hx", C.c_double), ("hy", C.c_double), ("make_obs", C.c_int), ("reserved", C.c_int)]
+
+
+class MissionParamsC(C.Structure):
+    """alore_backend_mission_params (include/alore_backend.h)"""
+    _fields_ = [("item_half", C.c_double), ("free_half", C.c_double), ("item_free_dist", C.c_double), ("target_lock_half", C.c_double),
+                ("target_lock_dist", C.c_double), ("left_target_half", C.c_double), ("left_target_dist", C.c_double)]
+
+
+class MissionViewC(C.Structure):
+    """alore_backend_mission_view: device addresses of the slab of missions, their edit list and the paint counters"""
+    _fields_ = [("max_tasks", C.c_int), ("edit_capacity", C.c_int), ("status", C.c_void_p), ("phase", C.c_void_p), ("goal_item", C.c_void_p),
+                ("goal_target", C.c_void_p), ("goal_status", C.c_void_p), ("n_tasks", C.c_void_p), ("kinds", C.c_void_p), ("items", C.c_void_p),
+                ("targets", C.c_void_p), ("edits", C.c_void_p), ("n_edits", C.c_void_p), ("counters", C.c_void_p)]
+
+
+# alore_backend_map_edit as a numpy dtype (what map_paint takes and mission_state returns)
+EDIT_DTYPE = np.dtype([("cx", np.float64), ("cy", np.float64), ("hx", np.float64), ("hy", np.float64), ("make_obs", np.int32),
+                       ("reserved", np.int32)])
+MISSION_OK, MISSION_MASKED, MISSION_E_POINT, MISSION_E_TASKS = 0, 1, -1, -6
+PHASE_NONE, PHASE_ITEM, PHASE_TARGET = 0, 1, 2
+ITEM_SQUARE, ITEM_BOX, ITEM_TABLE, ITEM_CHAIR = 0, 1, 2, 3
 MAX_PATH_POINTS = 31
 TASK_MAX_TASKS, TASK_MAX_POINTS, TASK_MAX_LEGS = 10, 21, 20
 TASK_GREEDY, TASK_OPTIMAL = 0, 1
@@ -213,6 +237,18 @@ def _bind(L):
                                           C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     L.alore_backend_device_task.argtypes = [C.c_void_p, C.POINTER(TaskViewC)]
     L.alore_backend_get_task.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_int)] * 5 + [DP, DP] + [C.POINTER(C.c_int)] * 2
+    L.alore_backend_map_paint.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.alore_backend_device_paint_counters.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.alore_backend_map_paint_counters.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    L.alore_backend_mission_default_params.argtypes = [C.POINTER(MissionParamsC)]
+    L.alore_backend_mission_default_params.restype = None
+    L.alore_backend_mission_create.argtypes = [C.c_void_p, C.POINTER(MissionParamsC)]
+    L.alore_backend_mission_set.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                            C.c_int, C.c_void_p]
+    L.alore_backend_mission_set_goals.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.alore_backend_mission_step.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.alore_backend_device_mission.argtypes = [C.c_void_p, C.POINTER(MissionViewC)]
+    L.alore_backend_get_mission.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_int)] * 5 + [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L._backend_bound = True
 
 
@@ -234,6 +270,16 @@ def default_map_params() -> MapParamsC:
     _bind(L)
     p = MapParamsC()
     L.alore_backend_map_default_params(C.byref(p))
+    return p
+
+
+def default_mission_params() -> MissionParamsC:
+    """plan_manager.hpp: item squares of half 0.5, freed with half 0.5 within 2.0 m, targets locked with half 0.3 within 0.5 m, a
+    target just left locked with half 0.2 within 0.3 m"""
+    L = _lib.load()
+    _bind(L)
+    p = MissionParamsC()
+    L.alore_backend_mission_default_params(C.byref(p))
     return p
 
 
@@ -460,6 +506,107 @@ class BatchedMSPlanner:
         v = MapViewC()
         self._check(self.L.alore_backend_map_device(self.h, C.byref(v)))
         return v
+
+    # ---- the edits of missions in the resident map: item and target footprints
+    def map_paint(self, edits, stream=None) -> dict:
+        """paintSquare / paintBox / ... for a host list, as if one edit after the other.  edits: an EDIT_DTYPE array, or rows
+        (cx, cy, hx, hy, make_obs).  The list is uploaded and the call waits; returns the counters (paint_counters)."""
+        if isinstance(edits, np.ndarray) and edits.dtype == EDIT_DTYPE:
+            e = np.ascontiguousarray(edits)
+        else:
+            rows = np.asarray(edits, np.float64).reshape(-1, 5)
+            e = np.zeros(len(rows), EDIT_DTYPE)
+            for k, name in enumerate(("cx", "cy", "hx", "hy")):
+                e[name] = rows[:, k]
+            e["make_obs"] = rows[:, 4] != 0
+        self._check(self.L.alore_backend_map_paint(self.h, e.ctypes.data if len(e) else None, len(e), None, 0, _stream(stream)))
+        return self.paint_counters()
+
+    def map_paint_device(self, edits, d_count, capacity: int | None = None, stream=None):
+        """the same for a list in DEVICE memory (a torch tensor or an address) of `capacity` entries of 40 bytes whose length is the
+        device int at d_count; nothing waits, the counters stay on the device (paint_counters fetches them)"""
+        if capacity is None:
+            capacity = int(edits.numel() * edits.element_size() // C.sizeof(MapEditC))
+        self._check(self.L.alore_backend_map_paint(self.h, _dev(edits), int(capacity), _dev(d_count), 1, _stream(stream)))
+
+    def paint_counters(self) -> dict:
+        """n_changed, box (min_x, min_y, max_x, max_y) and n_skipped of the last paint; waits"""
+        out = (C.c_int * 6)()
+        self._check(self.L.alore_backend_map_paint_counters(self.h, out))
+        return {"n_changed": out[0], "box": (out[1], out[2], out[3], out[4]), "n_skipped": out[5]}
+
+    def mission_create(self, params: MissionParamsC | None = None, **fields):
+        """the slab of max_problems missions on the resident map; fields: single parameters to change (item_half=0.3, ...)"""
+        p = default_mission_params()
+        if params is not None:
+            C.memmove(C.byref(p), C.byref(params), C.sizeof(p))
+        for k, v in fields.items():
+            if k not in dict(MissionParamsC._fields_):
+                raise TypeError(f"alore_backend_mission_params has no field {k}")
+            setattr(p, k, v)
+        self._check(self.L.alore_backend_mission_create(self.h, C.byref(p)))
+        self.mission_params = p
+
+    def mission_set(self, n_tasks, points, kinds=None, mask=None, stream=None):
+        """items and targets of missions 0..count-1 from host rows [count][1 + 2 T][2] (the layout of task_plan; point 0 is
+        ignored), then "items -> OBS" in the map.  kinds: [count][T] of ITEM_*; mask: [count] ints.  Waits."""
+        n = np.ascontiguousarray(n_tasks, np.int32)
+        p = np.ascontiguousarray(points, np.float64)
+        count, T = len(n), (p.shape[1] - 1) // 2
+        k = None if kinds is None else np.ascontiguousarray(kinds, np.int32).reshape(count, T)
+        m = None if mask is None else np.ascontiguousarray(mask, np.int32)
+        self._check(self.L.alore_backend_mission_set(self.h, count, T, n.ctypes.data, p.ctypes.data, p.shape[1] * 16, None if k is None else k.ctypes.data,
+                                                     0, None if m is None else m.ctypes.data, 4, _stream(stream)))
+
+    def mission_set_device(self, count, max_tasks, n_tasks, points, point_row_stride=None, kinds=None, mask=None, mask_stride: int = 4, stream=None):
+        """mission_set on DEVICE memory (torch tensors or addresses) in stream order; nothing waits"""
+        ma, ms = _mask(mask, mask_stride)
+        self._check(self.L.alore_backend_mission_set(self.h, int(count), int(max_tasks), _dev(n_tasks), _dev(points),
+                                                     int(point_row_stride or 16 * (1 + 2 * max_tasks)), _dev(kinds), 1, ma, ms, _stream(stream)))
+
+    def mission_set_goals(self, goal_xy, mask=None, stride=None, mask_stride: int = 4, stream=None, count=None):
+        """the goal classification at a plan start.  goal_xy: a host array [count][>= 2] (waits) or, with count, a device tensor or
+        address read with `stride` bytes between goals in stream order"""
+        if count is None:
+            g = np.ascontiguousarray(goal_xy, np.float64)
+            m = None if mask is None else np.ascontiguousarray(mask, np.int32)
+            self._check(self.L.alore_backend_mission_set_goals(self.h, len(g), g.ctypes.data, g.shape[1] * 8, 0, None if m is None else m.ctypes.data, 4,
+                                                               _stream(stream)))
+        else:
+            ma, ms = _mask(mask, mask_stride)
+            self._check(self.L.alore_backend_mission_set_goals(self.h, int(count), _dev(goal_xy), int(stride or 16), 1, ma, ms, _stream(stream)))
+
+    def mission_step(self, poses, after_plan_mask=None, stride=None, mask_stride: int = 4, stream=None, count=None, esdf_odom=None,
+                     esdf_range: float | None = None):
+        """one tick of MapUpdateThread plus the post-plan rule, painted in the same call.  poses: a host array [count][>= 2] (waits)
+        or, with count, a device tensor or address with `stride` bytes between poses (nothing waits).  esdf_odom: enqueue
+        map_update_esdf behind it on the same stream, in the window esdf_odom +- esdf_range (None: the map's own)."""
+        if count is None:
+            p = np.ascontiguousarray(poses, np.float64)
+            m = None if after_plan_mask is None else np.ascontiguousarray(after_plan_mask, np.int32)
+            self._check(self.L.alore_backend_mission_step(self.h, len(p), p.ctypes.data, p.shape[1] * 8, 0, None if m is None else m.ctypes.data, 4,
+                                                          _stream(stream)))
+        else:
+            ma, ms = _mask(after_plan_mask, mask_stride)
+            self._check(self.L.alore_backend_mission_step(self.h, int(count), _dev(poses), int(stride or 16), 1, ma, ms, _stream(stream)))
+        if esdf_odom is not None:
+            self.map_update_esdf(esdf_odom, esdf_range, stream=stream)
+
+    def device_mission(self) -> MissionViewC:
+        v = MissionViewC()
+        self._check(self.L.alore_backend_device_mission(self.h, C.byref(v)))
+        return v
+
+    def mission_state(self, count: int | None = None) -> dict:
+        """status, phase, goal_item, goal_target, goal_status [count], the edit list of the last mission_set / mission_step (an
+        EDIT_DTYPE array) and the counters of the last paint; waits"""
+        n = self.B if count is None else int(count)
+        ints = {k: np.zeros(n, np.int32) for k in ("status", "phase", "goal_item", "goal_target", "goal_status")}
+        edits, ne, cnt = np.zeros(self.B * TASK_MAX_TASKS, EDIT_DTYPE), C.c_int(0), (C.c_int * 6)()
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        self._check(self.L.alore_backend_get_mission(self.h, n, ip(ints["status"]), ip(ints["phase"]), ip(ints["goal_item"]), ip(ints["goal_target"]),
+                                                     ip(ints["goal_status"]), edits.ctypes.data, C.byref(ne), cnt))
+        return dict(ints, edits=edits[:ne.value].copy(), n_changed=cnt[0], box=(cnt[1], cnt[2], cnt[3], cnt[4]), n_skipped=cnt[5])
 
     def predicted_state(self, times, resolution: float = 0.01, start_times=None, start_xytheta=None):
         """MSPlanner::get_the_predicted_state[_and_path] for the plans of the last launch"""

@@ -10,6 +10,7 @@
 #include "backend_kernels.h"
 #include "flat_traj_build.h"
 #include "laser_scan_launch.h"
+#include "mission_map.h"
 #include "path_search.h"
 #include "task_plan.h"
 
@@ -93,6 +94,21 @@ struct alore_backend_planner {
     char *h_laser = nullptr, *d_laser_in = nullptr;
     hipEvent_t ev_laser = nullptr; // the upload of the previous call has left h_laser
     bool laser_pending = false;
+    // alore_backend_map_paint: the descriptors of one launch, the counters, the staging of a host list (grows); allocated by the
+    // first paint call or by alore_backend_mission_create, whichever comes first
+    mission::Desc* p_desc = nullptr;
+    int p_desc_cap = 0; // descriptors: at least mission::PAINT_CHUNK, the longest host list, the missions' edit list
+    int* p_counters = nullptr;
+    mission::Edit* p_host_edits = nullptr;
+    size_t p_host_cap = 0; // edits
+    // alore_backend_mission_*: the slab of the missions (one allocation, m_slab_mem), their edit list with its length on the
+    // device, and the staging of the host routes
+    bool has_mission = false;
+    mission::Params m_params{};
+    mission::Slab m_slab{};
+    char *m_slab_mem = nullptr, *m_stage = nullptr;
+    int *m_was_set = nullptr, *m_n_edits = nullptr;
+    mission::Edit* m_edits = nullptr;
 };
 
 namespace {
@@ -179,7 +195,7 @@ void free_all(alore_backend_handle h)
                     h->d_cost, h->d_err, h->d_ret, h->d_params, h->d_order, h->d_check_in, h->d_check, h->d_build_in, h->d_build_status,
                     h->d_search_in, h->d_path_n, h->d_path_cost, h->d_search_status, h->d_search_sweeps, h->d_path_xy,
                     h->d_task_in, h->t_status, h->t_matrix, h->t_order, h->t_n_order, h->t_total, h->t_fields, h->t_sweeps, h->t_src_fields,
-                    h->t_src_sweeps, h->t_leg_start, h->t_leg_goal};
+                    h->t_src_sweeps, h->t_leg_start, h->t_leg_goal, h->p_desc, h->p_counters, h->p_host_edits, h->m_slab_mem, h->m_stage, h->m_edits};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_task) (void)hipHostFree(h->h_task);
@@ -1432,6 +1448,276 @@ int alore_backend_get_task(alore_backend_handle h, int count, int* status, int* 
     if (leg_goal_xy) BE_TRY(h, hipMemcpy(leg_goal_xy, h->t_leg_goal, sizeof(double) * n * L * 2, hipMemcpyDeviceToHost));
     if (fields) BE_TRY(h, hipMemcpy(fields, h->t_fields, sizeof(int) * n, hipMemcpyDeviceToHost));
     if (sweeps) BE_TRY(h, hipMemcpy(sweeps, h->t_sweeps, sizeof(int) * n, hipMemcpyDeviceToHost));
+    return ALORE_BE_OK;
+}
+
+// ---- the edits of missions in the resident map ---------------------------------------------------------------------------------
+static_assert(sizeof(alore_backend_map_edit) == sizeof(mission::Edit) && sizeof(alore_backend_map_edit) == 40, "alore_backend_map_edit");
+static_assert(sizeof(alore_backend_mission_params) == sizeof(mission::Params), "alore_backend_mission_params");
+
+// the descriptors and counters of the paint kernels; `need`: a list that must fit into one launch (a host list, the missions' list)
+static int paint_buffers(alore_backend_handle h, int need)
+{
+    const int want = std::max(need, (int)mission::PAINT_CHUNK);
+    if (want > h->p_desc_cap) {
+        if (h->p_desc) {
+            BE_TRY(h, hipDeviceSynchronize()); // an earlier call on another stream may still read the old descriptors
+            (void)hipFree(h->p_desc);
+            h->p_desc = nullptr;
+            h->p_desc_cap = 0;
+        }
+        BE_TRY(h, hipMalloc((void**)&h->p_desc, sizeof(mission::Desc) * (size_t)want));
+        h->p_desc_cap = want;
+    }
+    if (!h->p_counters) {
+        BE_TRY(h, dalloc(&h->p_counters, 8));
+        const mission::Counters c = mission::no_change(h->omap.nx, h->omap.ny);
+        BE_TRY(h, hipMemcpy(h->p_counters, &c, sizeof(c), hipMemcpyHostToDevice));
+    }
+    return ALORE_BE_OK;
+}
+static occ::Geom paint_geom(alore_backend_handle h) { return occ::make_geom(h->omap.nx, h->omap.ny, h->omap.x_lo, h->omap.y_lo, h->omap.res); }
+
+int alore_backend_map_paint(alore_backend_handle h, const alore_backend_map_edit* edits, int n_or_capacity, const int* d_count, int device_edits,
+                            void* stream)
+{
+    BE_MAP(h, "map_paint");
+    if (n_or_capacity < 0 || (n_or_capacity > 0 && !edits) || (device_edits && !d_count))
+        return fail(h, ALORE_BE_E_INVALID, "map_paint: a list needs edits and a length that is not negative, a device list its device count");
+    const mission::Edit* list = (const mission::Edit*)edits;
+    if (!device_edits) {
+        const long bad = mission::first_invalid(list, n_or_capacity, h->omap.res);
+        if (bad >= 0)
+            return fail(h, ALORE_BE_E_INVALID, "map_paint: an edit has a field that is not finite, a negative half size or more than 64 lattice points on an axis");
+    }
+    BE_TRY(h, hipSetDevice(h->device));
+    if (const int rc = paint_buffers(h, device_edits ? 0 : n_or_capacity)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (!device_edits) {
+        if ((size_t)n_or_capacity > h->p_host_cap) {
+            BE_TRY(h, hipDeviceSynchronize()); // an earlier call on another stream may still read the old buffer
+            if (h->p_host_edits) { (void)hipFree(h->p_host_edits); h->p_host_edits = nullptr; h->p_host_cap = 0; }
+            BE_TRY(h, hipMalloc((void**)&h->p_host_edits, sizeof(mission::Edit) * (size_t)n_or_capacity));
+            h->p_host_cap = (size_t)n_or_capacity;
+        }
+        if (n_or_capacity > 0)
+            BE_TRY(h, hipMemcpyAsync(h->p_host_edits, edits, sizeof(mission::Edit) * (size_t)n_or_capacity, hipMemcpyHostToDevice, s));
+        list = h->p_host_edits;
+        d_count = nullptr;
+    }
+    BE_TRY(h, mission::paint_enqueue(paint_geom(h), h->omap.grid, list, d_count, n_or_capacity, h->p_desc, h->p_desc_cap, h->p_counters, s));
+    if (!device_edits) BE_TRY(h, hipStreamSynchronize(s));
+    return ALORE_BE_OK;
+}
+
+int alore_backend_device_paint_counters(alore_backend_handle h, const int** out)
+{
+    if (!h || !out) return fail(h, ALORE_BE_E_INVALID, "device_paint_counters: bad argument");
+    if (!h->p_counters) return fail(h, ALORE_BE_E_INVALID, "device_paint_counters: nothing was painted yet (alore_backend_map_paint / alore_backend_mission_create)");
+    *out = h->p_counters;
+    return ALORE_BE_OK;
+}
+
+int alore_backend_map_paint_counters(alore_backend_handle h, int out[6])
+{
+    if (!h || !out) return fail(h, ALORE_BE_E_INVALID, "map_paint_counters: bad argument");
+    if (!h->p_counters) return fail(h, ALORE_BE_E_INVALID, "map_paint_counters: nothing was painted yet (alore_backend_map_paint / alore_backend_mission_create)");
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, hipDeviceSynchronize());
+    BE_TRY(h, hipMemcpy(out, h->p_counters, sizeof(int) * 6, hipMemcpyDeviceToHost));
+    return ALORE_BE_OK;
+}
+
+void alore_backend_mission_default_params(alore_backend_mission_params* p)
+{
+    mission::Params d;
+    mission::default_params(&d);
+    std::memcpy(p, &d, sizeof(d));
+}
+
+namespace {
+// the staging of the host routes of alore_backend_mission_*: rows of points, then n_tasks, kinds and a mask
+size_t mission_stage_bytes(size_t B) { return B * (sizeof(double) * 2 * ALORE_BE_TASK_MAX_POINTS + sizeof(int) * (ALORE_BE_TASK_MAX_TASKS + 2)); }
+bool stride_ok(int stride, int least, int unit) { return stride >= least && stride % unit == 0; }
+} // namespace
+
+int alore_backend_mission_create(alore_backend_handle h, const alore_backend_mission_params* params)
+{
+    BE_MAP(h, "mission_create");
+    mission::Params prm;
+    if (params) std::memcpy(&prm, params, sizeof(prm)); else mission::default_params(&prm);
+    const double v[7] = {prm.item_half, prm.free_half, prm.item_free_dist, prm.target_lock_half, prm.target_lock_dist, prm.left_target_half, prm.left_target_dist};
+    for (double x : v)
+        if (!std::isfinite(x) || x < 0.0) return fail(h, ALORE_BE_E_INVALID, "mission_create: half sizes and distances must be finite and not negative");
+    BE_TRY(h, hipSetDevice(h->device));
+    if (const int rc = paint_buffers(h, h->B * mission::MAX_TASKS)) return rc;
+    h->m_params = prm;
+    if (h->has_mission) return ALORE_BE_OK; // the slab is sized by the handle, not by the parameters
+    const size_t B = h->B, T = mission::MAX_TASKS;
+    const size_t doubles = B * T * 4, ints = B * 7 + 2 + B * T;
+    std::vector<char> init(sizeof(double) * doubles + sizeof(int) * ints, 0);
+    int* hi = (int*)(init.data() + sizeof(double) * doubles);
+    for (size_t b = 0; b < B; ++b) {
+        hi[b] = mission::MASKED; // never set
+        hi[2 * B + b] = hi[3 * B + b] = -1;
+    }
+    hipError_t e = hipMalloc((void**)&h->m_slab_mem, init.size());
+    if (e == hipSuccess) e = hipMemcpy(h->m_slab_mem, init.data(), init.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->m_edits, sizeof(mission::Edit) * B * T);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->m_stage, mission_stage_bytes(B));
+    if (e != hipSuccess) {
+        void* ptrs[] = {h->m_slab_mem, h->m_edits, h->m_stage};
+        for (void* p : ptrs)
+            if (p) (void)hipFree(p);
+        h->m_slab_mem = h->m_stage = nullptr;
+        h->m_edits = nullptr;
+        return fail(h, e == hipErrorOutOfMemory ? ALORE_BE_E_NOMEM : ALORE_BE_E_HIP, "mission_create", e);
+    }
+    double* dd = (double*)h->m_slab_mem;
+    int* di = (int*)(dd + doubles);
+    h->m_slab = mission::Slab{di, di + B, di + 2 * B, di + 3 * B, di + 4 * B, di + 5 * B, di + 7 * B + 2, dd, dd + B * T * 2};
+    h->m_was_set = di + 6 * B;
+    h->m_n_edits = di + 7 * B;
+    h->has_mission = true;
+    return ALORE_BE_OK;
+}
+
+#define BE_MISSION(h, what)                                                                                       \
+    do {                                                                                                          \
+        BE_MAP(h, what);                                                                                          \
+        if (!h->has_mission) return fail(h, ALORE_BE_E_INVALID, what ": no missions (alore_backend_mission_create)"); \
+    } while (0)
+
+int alore_backend_mission_set(alore_backend_handle h, int count, int max_tasks, const int* n_tasks, const double* points,
+                              int point_row_stride_bytes, const int* kinds_or_null, int device_pointers, const int* mask,
+                              int mask_stride_bytes, void* stream)
+{
+    BE_MISSION(h, "mission_set");
+    if (count < 1 || count > h->B || !n_tasks || !points) return fail(h, ALORE_BE_E_INVALID, "mission_set: bad argument");
+    if (max_tasks < 1 || max_tasks > mission::MAX_TASKS) return fail(h, ALORE_BE_E_INVALID, "mission_set: max_tasks must be 1 .. 10");
+    const int row = 2 * (int)sizeof(double) * (1 + 2 * max_tasks);
+    if (!stride_ok(point_row_stride_bytes, row, 8))
+        return fail(h, ALORE_BE_E_INVALID, "mission_set: the row stride of the points must be a multiple of 8, at least 16 (1 + 2 max_tasks)");
+    if (mask && !stride_ok(mask_stride_bytes, 4, 4)) return fail(h, ALORE_BE_E_INVALID, "mission_set: the mask stride must be a positive multiple of sizeof(int)");
+    BE_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = count, T = max_tasks;
+    std::vector<char> pack;
+    if (!device_pointers) {
+        pack.resize((size_t)row * n + sizeof(int) * (n + n * T + n));
+        int *hn = (int*)(pack.data() + (size_t)row * n), *hk = hn + n, *hm = hk + n * T;
+        for (size_t b = 0; b < n; ++b) {
+            std::memcpy(pack.data() + (size_t)row * b, (const char*)points + b * (size_t)point_row_stride_bytes, (size_t)row);
+            hn[b] = n_tasks[b];
+            for (size_t i = 0; i < T; ++i) hk[b * T + i] = kinds_or_null ? kinds_or_null[b * T + i] : mission::KIND_SQUARE;
+            hm[b] = mask ? *(const int*)((const char*)mask + b * (size_t)mask_stride_bytes) : 1;
+        }
+        BE_TRY(h, hipMemcpyAsync(h->m_stage, pack.data(), pack.size(), hipMemcpyHostToDevice, s));
+        points = (const double*)h->m_stage;
+        point_row_stride_bytes = row;
+        n_tasks = (const int*)(h->m_stage + (size_t)row * n);
+        kinds_or_null = n_tasks + n;
+        mask = kinds_or_null + n * T;
+        mask_stride_bytes = (int)sizeof(int);
+    }
+    BE_TRY(h, mission::set_enqueue(h->m_slab, count, max_tasks, n_tasks, points, point_row_stride_bytes, kinds_or_null, mask, mask ? mask_stride_bytes : 0,
+                                   h->m_was_set, s));
+    BE_TRY(h, mission::edits_enqueue(h->m_slab, h->m_params, count, h->m_was_set, nullptr, 0, nullptr, 0, h->m_edits, h->m_n_edits, s));
+    BE_TRY(h, mission::paint_enqueue(paint_geom(h), h->omap.grid, h->m_edits, h->m_n_edits, count * mission::MAX_TASKS, h->p_desc, h->p_desc_cap, h->p_counters, s));
+    if (!device_pointers) BE_TRY(h, hipStreamSynchronize(s));
+    return ALORE_BE_OK;
+}
+
+int alore_backend_mission_set_goals(alore_backend_handle h, int count, const double* goal_xy, int goal_stride_bytes, int device_pointers,
+                                    const int* mask, int mask_stride_bytes, void* stream)
+{
+    BE_MISSION(h, "mission_set_goals");
+    if (count < 1 || count > h->B || !goal_xy || !stride_ok(goal_stride_bytes, 16, 8))
+        return fail(h, ALORE_BE_E_INVALID, "mission_set_goals: needs 1 .. max_problems goals with a stride that is a multiple of 8, at least 16");
+    if (mask && !stride_ok(mask_stride_bytes, 4, 4)) return fail(h, ALORE_BE_E_INVALID, "mission_set_goals: the mask stride must be a positive multiple of sizeof(int)");
+    BE_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = count;
+    std::vector<char> pack;
+    if (!device_pointers) {
+        pack.resize(16 * n + sizeof(int) * n);
+        int* hm = (int*)(pack.data() + 16 * n);
+        for (size_t b = 0; b < n; ++b) {
+            std::memcpy(pack.data() + 16 * b, (const char*)goal_xy + b * (size_t)goal_stride_bytes, 16);
+            hm[b] = mask ? *(const int*)((const char*)mask + b * (size_t)mask_stride_bytes) : 1;
+        }
+        BE_TRY(h, hipMemcpyAsync(h->m_stage, pack.data(), pack.size(), hipMemcpyHostToDevice, s));
+        goal_xy = (const double*)h->m_stage;
+        goal_stride_bytes = 16;
+        mask = (const int*)(h->m_stage + 16 * n);
+        mask_stride_bytes = (int)sizeof(int);
+    }
+    BE_TRY(h, mission::goals_enqueue(h->m_slab, count, goal_xy, goal_stride_bytes, mask, mask ? mask_stride_bytes : 0, s));
+    if (!device_pointers) BE_TRY(h, hipStreamSynchronize(s));
+    return ALORE_BE_OK;
+}
+
+int alore_backend_mission_step(alore_backend_handle h, int count, const double* poses, int pose_stride_bytes, int device_pointers,
+                               const int* after_plan_mask, int mask_stride_bytes, void* stream)
+{
+    BE_MISSION(h, "mission_step");
+    if (count < 1 || count > h->B || !poses || !stride_ok(pose_stride_bytes, 16, 8))
+        return fail(h, ALORE_BE_E_INVALID, "mission_step: needs 1 .. max_problems poses with a stride that is a multiple of 8, at least 16");
+    if (after_plan_mask && !stride_ok(mask_stride_bytes, 4, 4))
+        return fail(h, ALORE_BE_E_INVALID, "mission_step: the mask stride must be a positive multiple of sizeof(int)");
+    BE_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = count;
+    std::vector<char> pack;
+    if (!device_pointers) {
+        pack.resize(16 * n + sizeof(int) * n);
+        int* hm = (int*)(pack.data() + 16 * n);
+        for (size_t b = 0; b < n; ++b) {
+            std::memcpy(pack.data() + 16 * b, (const char*)poses + b * (size_t)pose_stride_bytes, 16);
+            hm[b] = after_plan_mask ? *(const int*)((const char*)after_plan_mask + b * (size_t)mask_stride_bytes) : 0;
+        }
+        BE_TRY(h, hipMemcpyAsync(h->m_stage, pack.data(), pack.size(), hipMemcpyHostToDevice, s));
+        poses = (const double*)h->m_stage;
+        pose_stride_bytes = 16;
+        after_plan_mask = (const int*)(h->m_stage + 16 * n);
+        mask_stride_bytes = (int)sizeof(int);
+    }
+    BE_TRY(h, mission::edits_enqueue(h->m_slab, h->m_params, count, h->m_was_set, poses, pose_stride_bytes, after_plan_mask,
+                                     after_plan_mask ? mask_stride_bytes : 0, h->m_edits, h->m_n_edits, s));
+    BE_TRY(h, mission::paint_enqueue(paint_geom(h), h->omap.grid, h->m_edits, h->m_n_edits, 2 * count, h->p_desc, h->p_desc_cap, h->p_counters, s));
+    if (!device_pointers) BE_TRY(h, hipStreamSynchronize(s));
+    return ALORE_BE_OK;
+}
+
+int alore_backend_device_mission(alore_backend_handle h, alore_backend_mission_view* out)
+{
+    if (!h || !out) return fail(h, ALORE_BE_E_INVALID, "device_mission: bad argument");
+    if (!h->has_mission) return fail(h, ALORE_BE_E_INVALID, "device_mission: no missions (alore_backend_mission_create)");
+    const mission::Slab& s = h->m_slab;
+    *out = alore_backend_mission_view{mission::MAX_TASKS, h->B * mission::MAX_TASKS, s.status, s.phase, s.goal_item, s.goal_target, s.goal_status,
+                                      s.n, s.kinds, s.items, s.targets, (const alore_backend_map_edit*)h->m_edits, h->m_n_edits, h->p_counters};
+    return ALORE_BE_OK;
+}
+
+int alore_backend_get_mission(alore_backend_handle h, int count, int* status, int* phase, int* goal_item, int* goal_target, int* goal_status,
+                              alore_backend_map_edit* edits, int* n_edits, int counters[6])
+{
+    if (!h || count < 1 || count > h->B) return fail(h, ALORE_BE_E_INVALID, "get_mission: bad argument");
+    if (!h->has_mission) return fail(h, ALORE_BE_E_INVALID, "get_mission: no missions (alore_backend_mission_create)");
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, hipDeviceSynchronize());
+    const size_t n = count;
+    const mission::Slab& s = h->m_slab;
+    if (status) BE_TRY(h, hipMemcpy(status, s.status, sizeof(int) * n, hipMemcpyDeviceToHost));
+    if (phase) BE_TRY(h, hipMemcpy(phase, s.phase, sizeof(int) * n, hipMemcpyDeviceToHost));
+    if (goal_item) BE_TRY(h, hipMemcpy(goal_item, s.goal_item, sizeof(int) * n, hipMemcpyDeviceToHost));
+    if (goal_target) BE_TRY(h, hipMemcpy(goal_target, s.goal_target, sizeof(int) * n, hipMemcpyDeviceToHost));
+    if (goal_status) BE_TRY(h, hipMemcpy(goal_status, s.goal_status, sizeof(int) * n, hipMemcpyDeviceToHost));
+    int ne = 0;
+    BE_TRY(h, hipMemcpy(&ne, h->m_n_edits, sizeof(int), hipMemcpyDeviceToHost));
+    if (n_edits) *n_edits = ne;
+    if (edits && ne > 0) BE_TRY(h, hipMemcpy(edits, h->m_edits, sizeof(mission::Edit) * (size_t)ne, hipMemcpyDeviceToHost));
+    if (counters) BE_TRY(h, hipMemcpy(counters, h->p_counters, sizeof(int) * 6, hipMemcpyDeviceToHost));
     return ALORE_BE_OK;
 }
 

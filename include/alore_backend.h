@@ -542,6 +542,127 @@ int alore_backend_device_task(alore_backend_handle h, alore_backend_task_view *o
 int alore_backend_get_task(alore_backend_handle h, int count, int *status, int *matrix, int *order, int *n_order, int *total,
                            double *leg_start_xy, double *leg_goal_xy, int *fields, int *sweeps);
 
+/* ---- the edits a mission makes to the resident map: item and target footprints, on the device -------------------------- */
+/* What plan_manager does to its map while a mission runs (plan_manager.hpp: paintSquare / paintBox / paintTable / paintChair
+ * :470-496, MapUpdateThread :498-554, MainThread :618-658 and :695-704; sdf_map.cpp setObs / setFree :485-509): the items are
+ * painted into the occupancy grid as obstacles, an item's square is freed when the robot comes near, a target's square is locked
+ * when the robot delivers there, a target just left is locked after the next plan.  csrc/mission_map.h holds the arithmetic,
+ * csrc/mission_map.hip the kernels.  An edit is the reference's double loop
+ *     for (x = cx - hx; x <= cx + hx; x += res) for (y = cy - hy; y <= cy + hy; y += res) setObs / setFree (x, y)
+ * and three details of it decide cells: the lattice is ACCUMULATED in double (x += res, not cx - hx + i * res); setObs / setFree
+ * NARROW the coordinate to float, compare the float with the double bounds (< lo or >= hi: the point is skipped) and index with
+ * (int)((coord - lo) * inv), so the cells of an edit are neither a contiguous range nor one per lattice point; ONLY THE STATE GRID
+ * is written (2 occupied for make_obs != 0, else 1 unoccupied), log-odds and counts stay.  Deviations: an index that rounding
+ * takes to n is clamped to n - 1 (the reference writes out of bounds), and the validity rule below. */
+typedef struct alore_backend_map_edit {
+    double cx, cy, hx, hy;
+    int make_obs;
+    int reserved; /* 0 */
+} alore_backend_map_edit; /* 40 bytes */
+/* Applies the edits to the state grid of the resident map AS IF ONE AFTER THE OTHER IN LIST ORDER: where a free and a lock overlap
+ * the later one wins.  The call also leaves, in six device ints of the handle (alore_backend_device_paint_counters): n_changed, the
+ * number of cells whose state after the call differs from before it; min_x, min_y, max_x, max_y, the box of those cells (nx, ny,
+ * -1, -1 without one); n_skipped.  A DEVICE edit is skipped and counted when a field is not finite, a half size is negative, or it
+ * has more than 64 lattice points on an axis ((int)(2 h / res) + 2 > 64).
+ * device_edits == 0: `edits` is HOST memory of n_or_capacity edits and d_count is ignored; a list with an edit that would be
+ * skipped is refused with ALORE_BE_E_INVALID before anything is enqueued; the list is uploaded (the staging buffer grows when
+ * needed) and the stream is synchronised.
+ * device_edits != 0: `edits` is DEVICE memory of n_or_capacity entries and so is the length, *d_count: entries at and beyond
+ * min(*d_count, n_or_capacity) are never read into the map.  Nothing waits and nothing but the arguments crosses the bus; nothing
+ * is allocated after the handle's first paint call or alore_backend_mission_create (8192 descriptors and the counters).
+ * A list of more than 8192 edits is cut into launches in list order; later-wins holds across them, the counters then add up per
+ * launch (a cell one launch changes and a later one changes back counts twice, and is in the box).
+ * The ESDF is NOT part of the call: enqueue alore_backend_map_update_esdf behind it on the same stream in the window you want (the
+ * reference calls updateESDF2d after each group of edits).  Calls on one handle must be ordered on the device, as for
+ * alore_backend_search_paths; so must a map_integrate or map_update_esdf on another stream.  Without a resident map:
+ * ALORE_BE_E_INVALID. */
+int alore_backend_map_paint(alore_backend_handle h, const alore_backend_map_edit *edits, int n_or_capacity, const int *d_count,
+                            int device_edits, void *stream);
+/* the six device ints above; valid until the handle is destroyed.  ALORE_BE_E_INVALID before the first paint call */
+int alore_backend_device_paint_counters(alore_backend_handle h, const int **out);
+/* the same copied to HOST memory; waits for the device */
+int alore_backend_map_paint_counters(alore_backend_handle h, int out[6]);
+
+/* Mission state: one mission slot per problem slot of the handle (max_problems), up to ALORE_BE_TASK_MAX_TASKS tasks each.  ALL
+ * missions edit the handle's ONE map: the fleet form of the reference's one robot with its own map -- a robot sees the items of
+ * every other robot as obstacles, and the edits of a call are applied in slot order. */
+typedef struct alore_backend_mission_params {
+    double item_half;        /* 0.5  items -> OBS, plan_manager.hpp:518 */
+    double free_half;        /* 0.5  :533 */
+    double item_free_dist;   /* 2.0  :531 */
+    double target_lock_half; /* 0.3  :547 */
+    double target_lock_dist; /* 0.5  :545 */
+    double left_target_half; /* 0.2  :700 */
+    double left_target_dist; /* 0.3  :699 */
+} alore_backend_mission_params;
+void alore_backend_mission_default_params(alore_backend_mission_params *p);
+/* status of a mission */
+#define ALORE_BE_MISSION_OK 0
+#define ALORE_BE_MISSION_MASKED 1      /* the slot was never set: a mask that leaves a slot out leaves ALL of it, this word included */
+#define ALORE_BE_MISSION_E_POINT (-1)  /* a coordinate of an item or target is not finite */
+#define ALORE_BE_MISSION_E_TASKS (-6)  /* n outside 1..max_tasks, or a kind outside 0..3 */
+/* phase of a mission, and the status of its last goal */
+#define ALORE_BE_MISSION_PHASE_NONE 0
+#define ALORE_BE_MISSION_PHASE_ITEM 1
+#define ALORE_BE_MISSION_PHASE_TARGET 2
+#define ALORE_BE_MISSION_GOAL_OK 0
+#define ALORE_BE_MISSION_GOAL_E_POINT (-1) /* the goal is not finite: the phase is NONE */
+/* footprints of an item (the reference's if_mix_task shapes) */
+#define ALORE_BE_ITEM_SQUARE 0 /* item_half x item_half */
+#define ALORE_BE_ITEM_BOX 1    /* 0.25 x 0.15 */
+#define ALORE_BE_ITEM_TABLE 2  /* 0.5 x 0.25 */
+#define ALORE_BE_ITEM_CHAIR 3  /* 0.2 x 0.2 */
+/* Allocates, once: the slab of max_problems missions, an edit list of ALORE_BE_TASK_MAX_TASKS * max_problems entries (mission_set
+ * appends one edit per item, mission_step at most two per mission) with its length, and the staging of the host routes.  params
+ * NULL: the defaults; a second call only replaces the parameters.  Needs the resident map. */
+int alore_backend_mission_create(alore_backend_handle h, const alore_backend_mission_params *params);
+/* Stores items and targets of missions 0..count-1 from rows of the layout alore_backend_task_plan reads (point 0, the robot, is
+ * ignored; the same buffer serves both calls), then paints "items -> OBS" (:507-522): for missions in slot order and items in index
+ * order one edit per item, through the kernels of alore_backend_map_paint on the same stream.  kinds: [count][max_tasks] ints, one
+ * ALORE_BE_ITEM_* per item, NULL: all squares.  A mission that is set starts with phase NONE.  A mission with a negative status
+ * paints nothing and takes no part in later calls.  The mask is read as alore_backend_search_paths reads its mask.
+ * device_pointers as for alore_backend_task_plan: != 0, everything is DEVICE memory read in stream order and nothing waits; == 0,
+ * HOST memory, uploaded, and the stream is synchronised (the return value speaks of the call: read the status words). */
+int alore_backend_mission_set(alore_backend_handle h, int count, int max_tasks, const int *n_tasks, const double *points,
+                              int point_row_stride_bytes, const int *kinds_or_null, int device_pointers, const int *mask,
+                              int mask_stride_bytes, void *stream);
+/* The classification MainThread makes at every plan start (:618-658) for the goal of mission m, the two doubles at (char *)goal_xy
+ * + m * goal_stride_bytes (a multiple of 8, at least 16): goal_item is the FIRST item at the least distance from the goal
+ * (nearest_point starts from DBL_MAX and compares with <), goal_target likewise, the phase ITEM if dist_item < dist_target, else
+ * TARGET.  A goal that is not finite leaves the phase NONE and the goal status ALORE_BE_MISSION_GOAL_E_POINT.  leg_goal_xy + 2 l
+ * of alore_backend_device_task with stride ALORE_BE_TASK_MAX_LEGS * 16 serves as the goals as it lies. */
+int alore_backend_mission_set_goals(alore_backend_handle h, int count, const double *goal_xy, int goal_stride_bytes, int device_pointers,
+                                    const int *mask, int mask_stride_bytes, void *stream);
+/* One tick of MapUpdateThread plus the post-plan rule, for missions 0..count-1 in slot order, each with status OK and a phase; x, y
+ * of robot m are the two doubles at (char *)poses + m * pose_stride_bytes (a multiple of 8, at least 16: d_xytheta of
+ * alore_backend_predicted_state_device and the closed loops' pose slabs serve as they lie).  Each rule that fires appends one edit:
+ *   1. phase ITEM and |pose - goal_item| < item_free_dist: free goal_item with free_half (:526-537);
+ *   2. phase TARGET and |pose - goal_target| < target_lock_dist: lock goal_target with target_lock_half (:539-552);
+ *   3. after_plan_mask selects the mission (NULL: none; the word alore_backend_replan_mask writes serves as it lies) and the phase
+ *      is ITEM: the nearest target to the POSE, if closer than left_target_dist, is locked with left_target_half (:695-704).
+ * Distances are sqrt(dx * dx + dy * dy) in double without contraction, comparisons are strict (a pose exactly 2.0 away frees
+ * nothing), a pose that is not finite fails every comparison.  As in the reference an edit repeats on every tick while its
+ * condition holds: n_changed says whether anything moved.  The list is compacted in slot order with its length on the device and
+ * painted by the kernels of alore_backend_map_paint in the same call on the same stream; with device_pointers != 0 nothing waits
+ * and nothing is copied to the host. */
+int alore_backend_mission_step(alore_backend_handle h, int count, const double *poses, int pose_stride_bytes, int device_pointers,
+                               const int *after_plan_mask, int mask_stride_bytes, void *stream);
+/* the device slab of the missions [max_problems]; valid until the handle is destroyed */
+typedef struct alore_backend_mission_view {
+    int max_tasks, edit_capacity; /* 10, 10 * max_problems */
+    const int *status, *phase, *goal_item, *goal_target, *goal_status, *n_tasks; /* [.]; goal_item / goal_target: indices, -1 before a goal */
+    const int *kinds;                                                            /* [.][10] */
+    const double *items, *targets;                                               /* [.][10][2] */
+    const alore_backend_map_edit *edits; /* the list of the last mission_set or mission_step */
+    const int *n_edits;                  /* its length */
+    const int *counters;                 /* n_changed, min_x, min_y, max_x, max_y, n_skipped of the last paint */
+} alore_backend_mission_view;
+int alore_backend_device_mission(alore_backend_handle h, alore_backend_mission_view *out);
+/* The same copied to HOST arrays [count] (any pointer may be NULL); edits needs room for edit_capacity entries and receives
+ * *n_edits.  Waits for the device. */
+int alore_backend_get_mission(alore_backend_handle h, int count, int *status, int *phase, int *goal_item, int *goal_target,
+                              int *goal_status, alore_backend_map_edit *edits, int *n_edits, int counters[6]);
+
 #ifdef __cplusplus
 }
 #endif
