@@ -130,6 +130,8 @@ SYMBOLS = (
     ("alore_nmpc_refs_set_pending_from_backend", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double,
                                                            C.c_double, C.c_int, C.c_void_p]),
     ("alore_nmpc_refs_promote", C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_void_p]),
+    ("alore_nmpc_refs_stop", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    ("alore_nmpc_plant_stop", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     ("alore_nmpc_refs_pending_status", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("alore_nmpc_refs_pending_device", C.c_int, [C.c_void_p, C.POINTER(RefsPendingView)]),
     ("alore_nmpc_refs_pending_download", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -149,6 +149,26 @@ class MissionViewC(C.Structure):
                 ("targets", C.c_void_p), ("edits", C.c_void_p), ("n_edits", C.c_void_p), ("counters", C.c_void_p)]
 
 
+class ManagerParamsC(C.Structure):
+    """alore_backend_manager_params (include/alore_backend.h)"""
+    _fields_ = [("replan_time", C.c_double), ("max_replan_time", C.c_double), ("replan_on_collision_only", C.c_int),
+                ("stop_inside_obstacle", C.c_int), ("stop_on_no_path", C.c_int), ("reserved", C.c_int)]
+
+
+MANAGER_INT_ROWS = ("state", "have_goal", "have_start", "leg", "action", "returned", "plan_mask", "fresh_mask", "replan_mask", "stop_mask",
+                    "after_plan_mask")
+MANAGER_DOUBLE_ROWS = ("goal", "start", "plan_start_xytheta", "loop_start_time", "plan_start_time", "traj_start_time", "traj_total_time", "time")
+MANAGER_COUNTERS = ("fresh", "replan", "going_to_goal", "stopped", "delivered", "arrived", "refused")
+STATE_INIT, STATE_IDLE, STATE_PLANNING, STATE_REPLAN, STATE_GOINGTOGOAL, STATE_EMERGENCY_STOP = range(6)
+ACTION_NONE, ACTION_FRESH, ACTION_REPLAN = 0, 1, 2
+
+
+class ManagerViewC(C.Structure):
+    """alore_backend_manager_view: device addresses of the slab of the robots' state machines"""
+    _fields_ = [("max_problems", C.c_int), ("n_counters", C.c_int)] + [(k, C.c_void_p) for k in MANAGER_INT_ROWS + MANAGER_DOUBLE_ROWS] + \
+        [("counters", C.c_void_p)]
+
+
 # alore_backend_map_edit as a numpy dtype (what map_paint takes and mission_state returns)
 EDIT_DTYPE = np.dtype([("cx", np.float64), ("cy", np.float64), ("hx", np.float64), ("hy", np.float64), ("make_obs", np.int32),
                        ("reserved", np.int32)])
@@ -249,6 +269,16 @@ def _bind(L):
     L.alore_backend_mission_step.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     L.alore_backend_device_mission.argtypes = [C.c_void_p, C.POINTER(MissionViewC)]
     L.alore_backend_get_mission.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_int)] * 5 + [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.alore_backend_manager_default_params.argtypes = [C.POINTER(ManagerParamsC)]
+    L.alore_backend_manager_default_params.restype = None
+    L.alore_backend_manager_create.argtypes = [C.c_void_p, C.POINTER(ManagerParamsC)]
+    L.alore_backend_manager_request.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.alore_backend_manager_begin.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.alore_backend_manager_starts.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
+    L.alore_backend_manager_end.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
+    L.alore_backend_manager_next_legs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.alore_backend_device_manager.argtypes = [C.c_void_p, C.POINTER(ManagerViewC)]
+    L.alore_backend_get_manager.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), DP, C.POINTER(C.c_int)]
     L._backend_bound = True
 
 
@@ -280,6 +310,15 @@ def default_mission_params() -> MissionParamsC:
     _bind(L)
     p = MissionParamsC()
     L.alore_backend_mission_default_params(C.byref(p))
+    return p
+
+
+def default_manager_params() -> ManagerParamsC:
+    """planner_sim.launch: replan_time 5000, max_replan_time 0.05; periodic replans, no collision stop, no stop flag without a path"""
+    L = _lib.load()
+    _bind(L)
+    p = ManagerParamsC()
+    L.alore_backend_manager_default_params(C.byref(p))
     return p
 
 
@@ -607,6 +646,86 @@ class BatchedMSPlanner:
         self._check(self.L.alore_backend_get_mission(self.h, n, ip(ints["status"]), ip(ints["phase"]), ip(ints["goal_item"]), ip(ints["goal_target"]),
                                                      ip(ints["goal_status"]), edits.ctypes.data, C.byref(ne), cnt))
         return dict(ints, edits=edits[:ne.value].copy(), n_changed=cnt[0], box=(cnt[1], cnt[2], cnt[3], cnt[4]), n_skipped=cnt[5])
+
+    # ---- plan_manager's state machine for the fleet (csrc/fleet_manager.h)
+    def manager_create(self, params: ManagerParamsC | None = None, **fields):
+        """the slab of max_problems robots, all IDLE; fields: single parameters to change (replan_time=1.0, ...).  A second call only
+        replaces the parameters."""
+        p = default_manager_params()
+        if params is not None:
+            C.memmove(C.byref(p), C.byref(params), C.sizeof(p))
+        for k, v in fields.items():
+            if k not in dict(ManagerParamsC._fields_):
+                raise TypeError(f"alore_backend_manager_params has no field {k}")
+            setattr(p, k, v)
+        self._check(self.L.alore_backend_manager_create(self.h, C.byref(p)))
+        self.manager_params = p
+
+    def manager_request(self, start_xytheta=None, goal_xytheta=None, mask=None, stride=None, mask_stride: int = 4, stream=None, count=None):
+        """start_callback / goal_callback.  Host arrays [count][3] (waits) or, with count, device tensors or addresses read with
+        `stride` bytes between robots in stream order.  Either may be None."""
+        if count is None:
+            s = None if start_xytheta is None else np.ascontiguousarray(start_xytheta, np.float64).reshape(-1, 3)
+            g = None if goal_xytheta is None else np.ascontiguousarray(goal_xytheta, np.float64).reshape(-1, 3)
+            m = None if mask is None else np.ascontiguousarray(mask, np.int32)
+            n = len(s if s is not None else g) if (s is not None or g is not None) else 0
+            self._check(self.L.alore_backend_manager_request(self.h, n, None if s is None else s.ctypes.data, None if g is None else g.ctypes.data, 24, 0,
+                                                             None if m is None else m.ctypes.data, 4, _stream(stream)))
+        else:
+            ma, ms = _mask(mask, mask_stride)
+            self._check(self.L.alore_backend_manager_request(self.h, int(count), _dev(start_xytheta), _dev(goal_xytheta), int(stride or 24), 1, ma, ms,
+                                                             _stream(stream)))
+
+    def manager_begin(self, now: float, poses, collision_mask=None, stride=None, mask_stride: int = 4, stream=None, count=None):
+        """the head of MainThread at `now`.  poses: a host array [count][>= 2] (waits) or, with count, a device tensor or address with
+        `stride` bytes between poses (nothing waits); collision_mask: who may replan under replan_on_collision_only"""
+        if count is None:
+            p = np.ascontiguousarray(poses, np.float64)
+            m = None if collision_mask is None else np.ascontiguousarray(collision_mask, np.int32)
+            self._check(self.L.alore_backend_manager_begin(self.h, len(p), float(now), p.ctypes.data, p.shape[1] * 8, None if m is None else m.ctypes.data, 4,
+                                                           0, _stream(stream)))
+        else:
+            ma, ms = _mask(collision_mask, mask_stride)
+            self._check(self.L.alore_backend_manager_begin(self.h, int(count), float(now), _dev(poses), int(stride or 16), ma, ms, 1, _stream(stream)))
+
+    def manager_starts(self, count, xytheta, vaj, oaj, start_yaw=None, end_yaw=None, stream=None):
+        """behind predicted_state_device, on its DEVICE outputs: start states of FRESH robots in, predicted poses of REPLAN robots
+        out, start_yaw / end_yaw for set_paths_device"""
+        self._check(self.L.alore_backend_manager_starts(self.h, int(count), _dev(xytheta), _dev(vaj), _dev(oaj), _dev(start_yaw), _dev(end_yaw),
+                                                        _stream(stream)))
+
+    def manager_end(self, count=None, search_status=None, build_status=None, plan_ok=None, T=None, n_pieces=None, stream=None):
+        """the rest of MainThread with the `now` of the matching manager_begin; each array: None (the handle's own slab) or DEVICE
+        memory of the same layout (T: [count][self.P])"""
+        self._check(self.L.alore_backend_manager_end(self.h, int(count or self.B), _dev(search_status), _dev(build_status), _dev(plan_ok), _dev(T),
+                                                     _dev(n_pieces), _stream(stream)))
+
+    def manager_next_legs(self, count, poses, leg_yaw, stride=None, reset_legs: bool = False, stream=None):
+        """the next leg of its mission (the slab of task_plan) for every robot that is IDLE without a goal; DEVICE memory: poses
+        (x, y, yaw, `stride` bytes apart) and leg_yaw [count][TASK_MAX_LEGS]"""
+        self._check(self.L.alore_backend_manager_next_legs(self.h, int(count), _dev(poses), int(stride or 24), _dev(leg_yaw), int(bool(reset_legs)),
+                                                           _stream(stream)))
+
+    def manager_view(self) -> ManagerViewC:
+        v = ManagerViewC()
+        self._check(self.L.alore_backend_device_manager(self.h, C.byref(v)))
+        return v
+
+    def manager_mask(self, name: str):
+        """(address, stride) of plan_mask, fresh_mask, replan_mask, stop_mask or after_plan_mask, for the mask arguments"""
+        return int(getattr(self.manager_view(), name)), 4
+
+    def get_manager(self, count: int | None = None) -> dict:
+        """the slab copied to the host (waits): the int rows [count], goal / start / plan_start_xytheta [count][3], the times
+        [count], `counters` (a dict), and the raw blocks `ints` [11][count] and `doubles` [14][count]"""
+        n = self.B if count is None else int(count)
+        ints, dbl, cnt = np.zeros((len(MANAGER_INT_ROWS), n), np.int32), np.zeros((14, n)), np.zeros(8, np.int32)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        self._check(self.L.alore_backend_get_manager(self.h, n, ip(ints), _dp(dbl), ip(cnt)))
+        out = dict(zip(MANAGER_INT_ROWS, ints), ints=ints, doubles=dbl, counters=dict(zip(MANAGER_COUNTERS, cnt.tolist())))
+        out.update(goal=dbl[0:3].T.copy(), start=dbl[3:6].T.copy(), plan_start_xytheta=dbl[6:9].T.copy())
+        out.update(zip(MANAGER_DOUBLE_ROWS[3:], dbl[9:]))
+        return out
 
     def predicted_state(self, times, resolution: float = 0.01, start_times=None, start_xytheta=None):
         """MSPlanner::get_the_predicted_state[_and_path] for the plans of the last launch"""

@@ -9,6 +9,7 @@
 
 #include "backend_kernels.h"
 #include "flat_traj_build.h"
+#include "fleet_manager.h"
 #include "laser_scan_launch.h"
 #include "mission_map.h"
 #include "path_search.h"
@@ -109,6 +110,13 @@ struct alore_backend_planner {
     char *m_slab_mem = nullptr, *m_stage = nullptr;
     int *m_was_set = nullptr, *m_n_edits = nullptr;
     mission::Edit* m_edits = nullptr;
+    // alore_backend_manager_*: the slab of the robots' state machines (one allocation, g_mem), the staging of the host routes and
+    // the `now` of the last begin
+    bool has_manager = false, g_begun = false;
+    fleet::Params g_params{};
+    fleet::Slab g_slab{};
+    char *g_mem = nullptr, *g_stage = nullptr;
+    double g_now = 0.0;
 };
 
 namespace {
@@ -195,7 +203,8 @@ void free_all(alore_backend_handle h)
                     h->d_cost, h->d_err, h->d_ret, h->d_params, h->d_order, h->d_check_in, h->d_check, h->d_build_in, h->d_build_status,
                     h->d_search_in, h->d_path_n, h->d_path_cost, h->d_search_status, h->d_search_sweeps, h->d_path_xy,
                     h->d_task_in, h->t_status, h->t_matrix, h->t_order, h->t_n_order, h->t_total, h->t_fields, h->t_sweeps, h->t_src_fields,
-                    h->t_src_sweeps, h->t_leg_start, h->t_leg_goal, h->p_desc, h->p_counters, h->p_host_edits, h->m_slab_mem, h->m_stage, h->m_edits};
+                    h->t_src_sweeps, h->t_leg_start, h->t_leg_goal, h->p_desc, h->p_counters, h->p_host_edits, h->m_slab_mem, h->m_stage, h->m_edits,
+                    h->g_mem, h->g_stage};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_task) (void)hipHostFree(h->h_task);
@@ -1718,6 +1727,202 @@ int alore_backend_get_mission(alore_backend_handle h, int count, int* status, in
     if (n_edits) *n_edits = ne;
     if (edits && ne > 0) BE_TRY(h, hipMemcpy(edits, h->m_edits, sizeof(mission::Edit) * (size_t)ne, hipMemcpyDeviceToHost));
     if (counters) BE_TRY(h, hipMemcpy(counters, h->p_counters, sizeof(int) * 6, hipMemcpyDeviceToHost));
+    return ALORE_BE_OK;
+}
+
+// ---- plan_manager's state machine for the fleet -----------------------------------------------------------------------------------
+static_assert(sizeof(alore_backend_manager_params) == sizeof(fleet::Params) && sizeof(alore_backend_manager_params) == 32, "alore_backend_manager_params");
+static_assert(ALORE_BE_TASK_MAX_LEGS == fleet::MAX_LEGS && ALORE_BE_SEARCH_OK == fleet::SEARCH_OK && ALORE_BE_BUILD_OK == fleet::BUILD_OK, "fleet_manager.h");
+
+void alore_backend_manager_default_params(alore_backend_manager_params* p)
+{
+    fleet::Params d;
+    fleet::default_params(&d);
+    std::memcpy(p, &d, sizeof(d));
+}
+
+namespace {
+// the staging of the host routes of alore_backend_manager_*: starts and goals [n][3] and a mask, or poses [n][2] and a mask
+size_t manager_stage_bytes(size_t B) { return B * (sizeof(double) * 6 + sizeof(int)); }
+} // namespace
+
+int alore_backend_manager_create(alore_backend_handle h, const alore_backend_manager_params* params)
+{
+    if (!h) return ALORE_BE_E_INVALID;
+    fleet::Params prm;
+    if (params) std::memcpy(&prm, params, sizeof(prm)); else fleet::default_params(&prm);
+    if (!std::isfinite(prm.replan_time) || !std::isfinite(prm.max_replan_time) || prm.max_replan_time < 0.0)
+        return fail(h, ALORE_BE_E_INVALID, "manager_create: the times must be finite and max_replan_time not negative");
+    BE_TRY(h, hipSetDevice(h->device));
+    if (h->has_manager) { // the slab is sized by the handle, not by the parameters
+        h->g_params = prm;
+        return ALORE_BE_OK;
+    }
+    const size_t B = h->B, doubles = B * fleet::SLAB_DOUBLE_ROWS, ints = B * fleet::SLAB_INT_ROWS + fleet::N_COUNTERS;
+    std::vector<char> init(sizeof(double) * doubles + sizeof(int) * ints, 0);
+    double* hd = (double*)init.data();
+    int* hi = (int*)(init.data() + sizeof(double) * doubles);
+    const fleet::Robot r0 = fleet::initial();
+    for (size_t b = 0; b < B; ++b) {
+        hi[b] = r0.state;
+        hi[5 * B + b] = r0.returned;
+        hd[10 * B + b] = r0.plan_start_time;
+        hd[13 * B + b] = r0.time;
+    }
+    hipError_t e = hipMalloc((void**)&h->g_mem, init.size());
+    if (e == hipSuccess) e = hipMemcpy(h->g_mem, init.data(), init.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->g_stage, manager_stage_bytes(B));
+    if (e != hipSuccess) {
+        if (h->g_mem) (void)hipFree(h->g_mem);
+        if (h->g_stage) (void)hipFree(h->g_stage);
+        h->g_mem = h->g_stage = nullptr;
+        return fail(h, e == hipErrorOutOfMemory ? ALORE_BE_E_NOMEM : ALORE_BE_E_HIP, "manager_create", e);
+    }
+    double* dd = (double*)h->g_mem;
+    int* di = (int*)(dd + doubles);
+    fleet::Slab& s = h->g_slab;
+    s.B = h->B;
+    s.state = di; s.have_goal = di + B; s.have_start = di + 2 * B; s.leg = di + 3 * B; s.action = di + 4 * B; s.returned = di + 5 * B;
+    s.plan_mask = di + 6 * B; s.fresh_mask = di + 7 * B; s.replan_mask = di + 8 * B; s.stop_mask = di + 9 * B; s.after_plan_mask = di + 10 * B;
+    s.counters = di + 11 * B;
+    s.goal = dd; s.start = dd + 3 * B; s.plan_start_xytheta = dd + 6 * B;
+    s.loop_start_time = dd + 9 * B; s.plan_start_time = dd + 10 * B; s.traj_start_time = dd + 11 * B; s.traj_total_time = dd + 12 * B;
+    s.time = dd + 13 * B;
+    h->g_params = prm;
+    h->g_begun = false;
+    h->has_manager = true;
+    return ALORE_BE_OK;
+}
+
+#define BE_MANAGER(h, what)                                                                                        \
+    do {                                                                                                           \
+        if (!h) return ALORE_BE_E_INVALID;                                                                         \
+        if (!h->has_manager) return fail(h, ALORE_BE_E_INVALID, what ": no manager (alore_backend_manager_create)"); \
+    } while (0)
+
+int alore_backend_manager_request(alore_backend_handle h, int count, const double* start_xytheta, const double* goal_xytheta, int stride_bytes,
+                                  int device_pointers, const int* mask, int mask_stride_bytes, void* stream)
+{
+    BE_MANAGER(h, "manager_request");
+    if (count < 1 || count > h->B || (!start_xytheta && !goal_xytheta) || !stride_ok(stride_bytes, 24, 8))
+        return fail(h, ALORE_BE_E_INVALID, "manager_request: needs 1 .. max_problems robots, a start or a goal, and a stride that is a multiple of 8, at least 24");
+    if (mask && !stride_ok(mask_stride_bytes, 4, 4)) return fail(h, ALORE_BE_E_INVALID, "manager_request: the mask stride must be a positive multiple of sizeof(int)");
+    BE_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = count;
+    std::vector<char> pack;
+    if (!device_pointers) {
+        pack.resize(48 * n + sizeof(int) * n, 0);
+        int* hm = (int*)(pack.data() + 48 * n);
+        for (size_t b = 0; b < n; ++b) {
+            if (start_xytheta) std::memcpy(pack.data() + 24 * b, (const char*)start_xytheta + b * (size_t)stride_bytes, 24);
+            if (goal_xytheta) std::memcpy(pack.data() + 24 * (n + b), (const char*)goal_xytheta + b * (size_t)stride_bytes, 24);
+            hm[b] = mask ? *(const int*)((const char*)mask + b * (size_t)mask_stride_bytes) : 1;
+        }
+        BE_TRY(h, hipMemcpyAsync(h->g_stage, pack.data(), pack.size(), hipMemcpyHostToDevice, s));
+        if (start_xytheta) start_xytheta = (const double*)h->g_stage;
+        if (goal_xytheta) goal_xytheta = (const double*)(h->g_stage + 24 * n);
+        stride_bytes = 24;
+        mask = (const int*)(h->g_stage + 48 * n);
+        mask_stride_bytes = (int)sizeof(int);
+    }
+    BE_TRY(h, fleet::request_enqueue(h->g_slab, count, start_xytheta, goal_xytheta, stride_bytes, mask, mask ? mask_stride_bytes : 0, s));
+    if (!device_pointers) BE_TRY(h, hipStreamSynchronize(s));
+    return ALORE_BE_OK;
+}
+
+int alore_backend_manager_begin(alore_backend_handle h, int count, double now, const double* poses, int pose_stride_bytes,
+                                const int* collision_mask_or_null, int mask_stride_bytes, int device_pointers, void* stream)
+{
+    BE_MANAGER(h, "manager_begin");
+    if (count < 1 || count > h->B || !poses || !stride_ok(pose_stride_bytes, 16, 8) || !std::isfinite(now))
+        return fail(h, ALORE_BE_E_INVALID, "manager_begin: needs 1 .. max_problems poses with a stride that is a multiple of 8, at least 16, and a finite time");
+    if (collision_mask_or_null && !stride_ok(mask_stride_bytes, 4, 4))
+        return fail(h, ALORE_BE_E_INVALID, "manager_begin: the mask stride must be a positive multiple of sizeof(int)");
+    BE_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = count;
+    std::vector<char> pack;
+    if (!device_pointers) {
+        pack.resize(16 * n + sizeof(int) * n);
+        int* hm = (int*)(pack.data() + 16 * n);
+        for (size_t b = 0; b < n; ++b) {
+            std::memcpy(pack.data() + 16 * b, (const char*)poses + b * (size_t)pose_stride_bytes, 16);
+            hm[b] = collision_mask_or_null ? *(const int*)((const char*)collision_mask_or_null + b * (size_t)mask_stride_bytes) : 0;
+        }
+        BE_TRY(h, hipMemcpyAsync(h->g_stage, pack.data(), pack.size(), hipMemcpyHostToDevice, s));
+        poses = (const double*)h->g_stage;
+        pose_stride_bytes = 16;
+        collision_mask_or_null = (const int*)(h->g_stage + 16 * n);
+        mask_stride_bytes = (int)sizeof(int);
+    }
+    const fleet::Map m{h->d_map ? h->map.dist : nullptr, h->map.nx, h->map.ny, h->map.x_lo, h->map.y_lo, h->map.x_hi, h->map.y_hi, h->map.res};
+    BE_TRY(h, fleet::begin_enqueue(h->g_slab, h->g_params, m, count, now, poses, pose_stride_bytes, collision_mask_or_null,
+                                   collision_mask_or_null ? mask_stride_bytes : 0, s));
+    h->g_now = now;
+    h->g_begun = true;
+    if (!device_pointers) BE_TRY(h, hipStreamSynchronize(s));
+    return ALORE_BE_OK;
+}
+
+int alore_backend_manager_starts(alore_backend_handle h, int count, double* d_xytheta, double* d_vaj, double* d_oaj, double* d_start_yaw,
+                                 double* d_end_yaw, void* stream)
+{
+    BE_MANAGER(h, "manager_starts");
+    if (count < 1 || count > h->B || !d_xytheta || !d_vaj || !d_oaj) return fail(h, ALORE_BE_E_INVALID, "manager_starts: bad argument");
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, fleet::starts_enqueue(h->g_slab, count, d_xytheta, d_vaj, d_oaj, d_start_yaw, d_end_yaw, (hipStream_t)stream));
+    return ALORE_BE_OK;
+}
+
+int alore_backend_manager_end(alore_backend_handle h, int count, const int* search_status, const int* build_status, const int* plan_ok,
+                              const double* T, const int* n_pieces, void* stream)
+{
+    BE_MANAGER(h, "manager_end");
+    if (count < 1 || count > h->B) return fail(h, ALORE_BE_E_INVALID, "manager_end: needs 1 .. max_problems robots");
+    if (!h->g_begun) return fail(h, ALORE_BE_E_INVALID, "manager_end: no alore_backend_manager_begin before it");
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, fleet::end_enqueue(h->g_slab, h->g_params, count, h->g_now, search_status ? search_status : h->d_search_status,
+                                 build_status ? build_status : h->d_build_status, plan_ok ? plan_ok : h->r_ok, T ? T : h->r_T, h->P,
+                                 n_pieces ? n_pieces : h->d_M, (hipStream_t)stream));
+    h->g_begun = false;
+    return ALORE_BE_OK;
+}
+
+int alore_backend_manager_next_legs(alore_backend_handle h, int count, const double* poses, int pose_stride_bytes, const double* leg_yaw, int reset_legs,
+                                    void* stream)
+{
+    BE_MANAGER(h, "manager_next_legs");
+    if (count < 1 || count > h->B || !poses || !leg_yaw || !stride_ok(pose_stride_bytes, 24, 8))
+        return fail(h, ALORE_BE_E_INVALID, "manager_next_legs: needs 1 .. max_problems poses with a stride that is a multiple of 8, at least 24, and the legs' yaws");
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, fleet::next_legs_enqueue(h->g_slab, count, poses, pose_stride_bytes, h->t_status, h->t_n_order, h->t_leg_goal, leg_yaw, reset_legs,
+                                       (hipStream_t)stream));
+    return ALORE_BE_OK;
+}
+
+int alore_backend_device_manager(alore_backend_handle h, alore_backend_manager_view* out)
+{
+    BE_MANAGER(h, "device_manager");
+    if (!out) return fail(h, ALORE_BE_E_INVALID, "device_manager: bad argument");
+    const fleet::Slab& s = h->g_slab;
+    *out = alore_backend_manager_view{h->B, fleet::N_COUNTERS, s.state, s.have_goal, s.have_start, s.leg, s.action, s.returned, s.plan_mask, s.fresh_mask,
+                                      s.replan_mask, s.stop_mask, s.after_plan_mask, s.goal, s.start, s.plan_start_xytheta, s.loop_start_time,
+                                      s.plan_start_time, s.traj_start_time, s.traj_total_time, s.time, s.counters};
+    return ALORE_BE_OK;
+}
+
+int alore_backend_get_manager(alore_backend_handle h, int count, int* ints, double* doubles, int* counters)
+{
+    BE_MANAGER(h, "get_manager");
+    if (count < 1 || count > h->B) return fail(h, ALORE_BE_E_INVALID, "get_manager: bad argument");
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, hipDeviceSynchronize());
+    const size_t n = count, B = h->B;
+    const fleet::Slab& s = h->g_slab;
+    if (ints) BE_TRY(h, hipMemcpy2D(ints, sizeof(int) * n, s.state, sizeof(int) * B, sizeof(int) * n, fleet::SLAB_INT_ROWS, hipMemcpyDeviceToHost));
+    if (doubles) BE_TRY(h, hipMemcpy2D(doubles, sizeof(double) * n, s.goal, sizeof(double) * B, sizeof(double) * n, fleet::SLAB_DOUBLE_ROWS, hipMemcpyDeviceToHost));
+    if (counters) BE_TRY(h, hipMemcpy(counters, s.counters, sizeof(int) * fleet::N_COUNTERS, hipMemcpyDeviceToHost));
     return ALORE_BE_OK;
 }
 

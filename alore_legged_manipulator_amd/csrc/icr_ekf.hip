@@ -112,6 +112,8 @@ int ekf_tick(alore_nmpc_handle h, const alore_nmpc_batch* dev, int B, double now
     HIP_TRY(h, nmpc::launch_ref_sample(h->refs.store, *dev, B, N, (double)h->cfg.dt, now, L.d.est_pose, L.d.est_icr, h->refs.d_goal, h->refs.d_psi, 1, s));
     const int rc = alore_nmpc_rti(h, dev, B, 1, stream);
     if (rc != ALORE_NMPC_OK) return rc;
+    if (h->handoff.d_stopped) // alore_nmpc_refs_stop: the zero command holds while the robot has no trajectory
+        HIP_TRY(h, nmpc::launch_stop_hold(dev->u, h->refs.store.meta, h->handoff.d_stopped, B, N, delay_num < N ? delay_num : N - 1, s));
     h->ekf.ticks += 1;
     const int do_update = ltv_plan::is_update_tick(h->ekf.ticks, h->ekf.params.odom_every) ? 1 : 0;
     hipLaunchKernelGGL(icrekf::plant_ekf_kernel, dim3((B + 63) / 64), dim3(64), 0, s, *dev, B, N, delay_num < N ? delay_num : N - 1,

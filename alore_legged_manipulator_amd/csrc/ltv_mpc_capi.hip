@@ -669,6 +669,17 @@ int alore_ltv_plant_set_state(alore_ltv_handle h, int B, const double* pose, con
     return ALORE_LTV_OK;
 }
 
+int alore_ltv_plant_stop(alore_ltv_handle h, int B, const int* d_mask, int mask_stride_bytes, void* stream)
+{
+    if (!h) return ALORE_LTV_E_INVALID;
+    LTV_ARGS(h, "plant_stop", plant_args_bad(h, B));
+    if (d_mask && (mask_stride_bytes < (int)sizeof(int) || mask_stride_bytes % (int)sizeof(int)))
+        return lfail(h, ALORE_LTV_E_INVALID, "plant_stop: the mask stride must be a positive multiple of sizeof(int)");
+    LTV_TRY(h, hipSetDevice(h->device));
+    LTV_TRY(h, nmpc::launch_plant_stop(h->d_vw, h->d_des, 2, d_mask, d_mask ? mask_stride_bytes : 0, B, (hipStream_t)stream));
+    return ALORE_LTV_OK;
+}
+
 int alore_ltv_plant_get_state(alore_ltv_handle h, int B, double* pose, double* vw, int* at_goal, void* stream)
 {
     if (!h) return ALORE_LTV_E_INVALID;

@@ -161,6 +161,14 @@ struct PromoteArgs {
     double now;
 };
 hipError_t launch_traj_promote(const PromoteArgs& a, hipStream_t st);
+// emergencyStop for the robots a DEVICE mask names (traj_handoff.hip; the mask is read as PromoteArgs::mask, null: every robot):
+// launch_traj_stop clears the valid word of the active and (pen_meta not null) pending meta rows and sets stopped[t];
+// launch_plant_stop zeroes rows of `width` doubles at `state` (v, omega of a plant) and, where given, at `desired`;
+// launch_stop_hold, between a solve and the plant step of the NMPC closed loop, zeroes input column `node` of a robot that is
+// stopped and still has no active trajectory, and clears the flag of a robot that has one again
+hipError_t launch_traj_stop(double* act_meta, double* pen_meta, int* stopped, const int* mask, int mask_stride, int count, hipStream_t st);
+hipError_t launch_plant_stop(double* state, double* desired, int width, const int* mask, int mask_stride, int count, hipStream_t st);
+hipError_t launch_stop_hold(float* u, const double* act_meta, int* stopped, int B, int N, int node, hipStream_t st);
 // the plant step of tick t with the completion of tick t + 1's references (ref_sampler_device.h: plant_ahead_one)
 struct PlantAhead {
     const float* u;        // [B][N][2] inputs the solve of tick t left

@@ -347,6 +347,29 @@ int alore_nmpc_refs_promote(alore_nmpc_handle h, int B, double now, void* stream
     return ALORE_NMPC_OK;
 }
 
+int alore_nmpc_refs_stop(alore_nmpc_handle h, int B, const int* d_mask, int mask_stride_bytes, void* stream)
+{
+    if (!h || !h->refs.store.dur || B <= 0 || B > h->refs.B || (d_mask && (mask_stride_bytes < (int)sizeof(int) || mask_stride_bytes % (int)sizeof(int))))
+        return fail(h, ALORE_NMPC_E_INVALID, "refs_stop: bad argument");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (!h->handoff.d_stopped) { // the first stop of the handle allocates the flags
+        HIP_TRY(h, hipMalloc((void**)&h->handoff.d_stopped, sizeof(int) * h->refs.B));
+        HIP_TRY(h, hipMemset(h->handoff.d_stopped, 0, sizeof(int) * h->refs.B));
+    }
+    HIP_TRY(h, nmpc::launch_traj_stop(h->refs.store.meta, h->handoff.pending.meta, h->handoff.d_stopped, d_mask, d_mask ? mask_stride_bytes : 0, B,
+                                      (hipStream_t)stream));
+    return ALORE_NMPC_OK;
+}
+
+int alore_nmpc_plant_stop(alore_nmpc_handle h, int B, const int* d_mask, int mask_stride_bytes, void* stream)
+{
+    if (!h || !h->refs.has_plant || B <= 0 || B > h->refs.B || (d_mask && (mask_stride_bytes < (int)sizeof(int) || mask_stride_bytes % (int)sizeof(int))))
+        return fail(h, ALORE_NMPC_E_INVALID, "plant_stop: bad argument");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, nmpc::launch_plant_stop(h->refs.d_vw, nullptr, 2, d_mask, d_mask ? mask_stride_bytes : 0, B, (hipStream_t)stream));
+    return ALORE_NMPC_OK;
+}
+
 int alore_nmpc_refs_pending_status(alore_nmpc_handle h, int B, int* status, double* start_time, int* valid, int* promotions, void* stream)
 {
     if (!h || !h->refs.store.dur || B <= 0 || B > h->refs.B) return fail(h, ALORE_NMPC_E_INVALID, "refs_pending_status: bad argument");
@@ -545,6 +568,10 @@ int alore_nmpc_closed_loop_tick(alore_nmpc_handle h, const alore_nmpc_batch* dev
     HIP_TRY(h, nmpc::launch_ref_sample(h->refs.store, *dev, B, N, (double)h->cfg.dt, now, h->refs.d_est, h->refs.d_icr, h->refs.d_goal, h->refs.d_psi, 1, s));
     const int rc = alore_nmpc_rti(h, dev, B, 1, stream);
     if (rc != ALORE_NMPC_OK) return rc;
+    // alore_nmpc_refs_stop: the zero command of emergencyStop holds while the robot has no trajectory (a handle that never stopped
+    // a robot enqueues what it always did)
+    if (h->handoff.d_stopped)
+        HIP_TRY(h, nmpc::launch_stop_hold(dev->u, h->refs.store.meta, h->handoff.d_stopped, B, N, delay_num < N ? delay_num : N - 1, s));
     HIP_TRY(h, nmpc::launch_plant(*dev, B, N, delay_num < N ? delay_num : N - 1, h->refs.d_icr, h->refs.d_goal, h->refs.d_est, h->refs.d_vw, h->refs.plant, s));
     return ALORE_NMPC_OK;
 }
@@ -598,8 +625,9 @@ int run_segment(alore_nmpc_handle h, const alore_nmpc_batch* dev, int B, double 
 {
     auto time_of = [&](int t) { return traj_handoff::tick_time(t0, dt_tick, (long)first + t); };
     static const bool serial = [] { const char* e = getenv("ALORE_NMPC_CLOSED_LOOP_SERIAL"); return e && atoi(e) != 0; }();
+    // a handle that has stopped a robot (alore_nmpc_refs_stop) runs tick by tick: the hold of the zero command sits between solve and plant
     const bool ahead = !serial && n_ticks >= 3 && h && h->refs.has_plant && dev && dev->y && dev->yN && dev->x0 && B > 0 && B <= h->refs.B &&
-                       delay_num >= 0 && nmpc::ref_sample_ahead_supported(h->cfg.N);
+                       delay_num >= 0 && nmpc::ref_sample_ahead_supported(h->cfg.N) && !h->handoff.d_stopped;
     if (!ahead) {
         for (int t = 0; t < n_ticks; ++t) {
             const int rc = alore_nmpc_closed_loop_tick(h, dev, B, time_of(t), delay_num, stream);

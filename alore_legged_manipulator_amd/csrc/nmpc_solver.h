@@ -101,9 +101,11 @@ struct alore_nmpc_solver {
         nmpc::RefStore pending{};
         int* d_status = nullptr;      // [B] traj_handoff::kWritten ... of the last set_pending call that addressed the slot
         int* d_promotions = nullptr;  // [B]
+        int* d_stopped = nullptr;     // [B] alore_nmpc_refs_stop: robots whose command is held at zero until they have a trajectory again
         traj_handoff::PendingTimes times; // start times handed in and not yet passed by a promotion over every robot
         void release()
         {
+            if (d_stopped) (void)hipFree(d_stopped);
             if (pending.dur) (void)hipFree(pending.dur);
             if (pending.coef) (void)hipFree(pending.coef);
             if (pending.ckpt) (void)hipFree(pending.ckpt);

@@ -57,6 +57,61 @@ __global__ __launch_bounds__(256) void traj_promote_kernel(PromoteArgs a)
     if (lane == 0) a.promotions[r] += 1;
 }
 
+// ---- the controllers' side of an emergency stop (nmpc_controller/src/mpc.cpp:279-294, mpc_controller/src/mpc.cpp:616-632):
+//      receive_traj_ = false and a zero command.  One lane per robot, ordinary stores, no LDS.
+namespace {
+__device__ inline bool stop_selected(const int* mask, int stride, int t) { return !mask || *(const int*)((const char*)mask + (size_t)t * stride) != 0; }
+} // namespace
+
+__global__ __launch_bounds__(256) void traj_stop_kernel(double* act_meta, double* pen_meta, int* stopped, const int* mask, int mask_stride, int count)
+{
+    const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (t >= count || !stop_selected(mask, mask_stride, t)) return;
+    act_meta[(size_t)t * 8 + 6] = 0.0;
+    if (pen_meta) pen_meta[(size_t)t * 8 + 6] = 0.0;
+    stopped[t] = 1;
+}
+
+__global__ __launch_bounds__(256) void plant_stop_kernel(double* state, double* desired, int width, const int* mask, int mask_stride, int count)
+{
+    const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (t >= count || !stop_selected(mask, mask_stride, t)) return;
+    for (int k = 0; k < width; ++k) {
+        state[(size_t)t * width + k] = 0.0;
+        if (desired) desired[(size_t)t * width + k] = 0.0;
+    }
+}
+
+__global__ __launch_bounds__(256) void stop_hold_kernel(float* u, const double* act_meta, int* stopped, int B, int N, int node)
+{
+    const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (r >= B || !stopped[r]) return;
+    if (act_meta[(size_t)r * 8 + 6] != 0.0) { stopped[r] = 0; return; } // a promotion since: the robot tracks again
+    u[((size_t)r * N + node) * 2] = 0.f;
+    u[((size_t)r * N + node) * 2 + 1] = 0.f;
+}
+
+hipError_t launch_traj_stop(double* act_meta, double* pen_meta, int* stopped, const int* mask, int mask_stride, int count, hipStream_t st)
+{
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(traj_stop_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, act_meta, pen_meta, stopped, mask, mask_stride, count);
+    return hipGetLastError();
+}
+
+hipError_t launch_plant_stop(double* state, double* desired, int width, const int* mask, int mask_stride, int count, hipStream_t st)
+{
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(plant_stop_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, state, desired, width, mask, mask_stride, count);
+    return hipGetLastError();
+}
+
+hipError_t launch_stop_hold(float* u, const double* act_meta, int* stopped, int B, int N, int node, hipStream_t st)
+{
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(stop_hold_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, u, act_meta, stopped, B, N, node);
+    return hipGetLastError();
+}
+
 hipError_t launch_traj_promote(const PromoteArgs& a, hipStream_t st)
 {
     if (a.count <= 0) return hipSuccess;

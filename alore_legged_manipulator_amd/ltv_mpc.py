@@ -50,6 +50,7 @@ def _bind(L):
     L.alore_ltv_plant_init.argtypes = [C.c_void_p, C.POINTER(LtvPlantParams), C.c_int]
     L.alore_ltv_plant_set_state.argtypes = [C.c_void_p, C.c_int, DP, DP, DP, C.c_void_p]
     L.alore_ltv_plant_get_state.argtypes = [C.c_void_p, C.c_int, DP, DP, IP, C.c_void_p]
+    L.alore_ltv_plant_stop.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     L.alore_ltv_plant_device.argtypes = [C.c_void_p, C.POINTER(LtvPlantView)]
     L.alore_ltv_refs_from_store_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]
     L.alore_ltv_get_cmd_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p]
@@ -196,6 +197,22 @@ class BatchedLtvMpc:
         pose = np.zeros((n, 3)); vw = np.zeros((n, 2)); goal = np.zeros(n, np.int32)
         self._check(self.L.alore_ltv_plant_get_state(self.h, n, _dp(pose), _dp(vw), goal.ctypes.data_as(IP), None))
         return pose, vw, goal.astype(bool)
+
+    def plant_stop(self, mask=None, n=None):
+        """the zero command of emergencyStop for the robots of a DEVICE mask (an int32 tensor or an (address, stride) pair; None:
+        all): v = omega = 0 and desired = 0.  Asynchronous."""
+        n = self._n if n is None else n
+        if mask is None:
+            a, st = None, 0
+        elif isinstance(mask, tuple):
+            a, st = int(mask[0]), int(mask[1])
+        else:
+            a, st = int(mask.data_ptr()), int(mask.stride(0) * 4)
+        self._check(self.L.alore_ltv_plant_stop(self.h, n, a, st, None))
+
+    def refs_stop(self, nmpc_engine, mask=None):
+        """the trajectories of the masked robots become invalid in the store this controller samples (BatchedNmpc.refs_stop)"""
+        nmpc_engine.refs_stop(mask)
 
     def plant_view(self) -> LtvPlantView:
         v = LtvPlantView()

@@ -335,6 +335,27 @@ class BatchedNmpc:
         """active <- pending for every robot whose pending entry is valid and now > its start time (strict).  Asynchronous."""
         self._check(self.lib.alore_nmpc_refs_promote(self.h, self.B, float(now), self._stream()))
 
+    @staticmethod
+    def _device_mask(mask):
+        """(address, stride in bytes) of a device mask: None, an int32 device tensor, or an (address, stride) pair such as
+        BatchedMSPlanner.manager_mask("stop_mask")"""
+        if mask is None:
+            return None, 0
+        if isinstance(mask, tuple):
+            return int(mask[0]), int(mask[1])
+        return int(mask.data_ptr()), int(mask.stride(0) * 4)
+
+    def refs_stop(self, mask=None) -> None:
+        """emergencyStop for the robots of a DEVICE mask (None: all): their active and pending entries become invalid, and the ticks
+        hold their command at zero until a later pending entry is promoted.  Asynchronous."""
+        a, st = self._device_mask(mask)
+        self._check(self.lib.alore_nmpc_refs_stop(self.h, self.B, a, st, self._stream()))
+
+    def plant_stop(self, mask=None) -> None:
+        """the zero command in the plant: v = omega = 0 for the robots of a DEVICE mask (None: all).  Asynchronous."""
+        a, st = self._device_mask(mask)
+        self._check(self.lib.alore_nmpc_plant_stop(self.h, self.B, a, st, self._stream()))
+
     def refs_pending_status(self) -> dict:
         """status (0 written, 1 not addressed, -1 / -2 too many pieces / checkpoints), start_time, valid, promotions.  Synchronises."""
         st = np.zeros(self.B, np.int32); t0 = np.zeros(self.B); va = np.zeros(self.B, np.int32); pr = np.zeros(self.B, np.int32)

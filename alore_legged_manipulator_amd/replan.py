@@ -76,3 +76,100 @@ def replan_cycle(planner, nmpc, now: float, max_replan_time: float, goals_xy, en
                                        state_seq_res=state_seq_res, integral_res_int=integral_res_int)
     mark("set_pending")
     return w
+
+
+class ManagerWork:
+    """the device tensors a manager period works on, allocated once, and torch views of the manager's slab (planner.manager_create
+    first): nothing is allocated in a period that is given one"""
+
+    def __init__(self, planner, count: int | None = None, device="cuda"):
+        import torch
+        from .backend import _DeviceArray
+        n = self.count = int(count or planner.B)
+        f64 = dict(dtype=torch.float64, device=device)
+        self.xytheta = torch.zeros(n, 3, **f64)         # predicted state, then the start of every plan of the period
+        self.vaj = torch.zeros(n, 3, **f64)
+        self.oaj = torch.zeros(n, 3, **f64)
+        self.start_yaw = torch.zeros(n, **f64)
+        self.end_yaw = torch.zeros(n, **f64)
+        self.goal_xy = torch.zeros(n, 2, **f64)         # the goals as the search reads them
+        self.forward = torch.zeros(n, dtype=torch.int32, device=device)
+        self.run_mask = torch.zeros(n, dtype=torch.int32, device=device)    # plan_mask AND searched AND built: the slots the optimiser runs
+        v, B = planner.manager_view(), planner.B
+        ints = lambda a: torch.as_tensor(_DeviceArray(a, (B,), "<i4"), device=device)
+        self.goal = torch.as_tensor(_DeviceArray(v.goal, (3, B), "<f8"), device=device)
+        self.time = v.time                               # address: the d_time of predicted_state_device
+        self.plan_mask, self.fresh_mask, self.replan_mask, self.stop_mask, self.after_plan_mask = (
+            ints(a) for a in (v.plan_mask, v.fresh_mask, v.replan_mask, v.stop_mask, v.after_plan_mask))
+        self.search_status = ints(planner.device_search_status())
+        self.build_status = ints(planner.device_build_status())
+        self.planned = False                             # a plan has been launched on the handle: the predicted state exists
+
+
+def manager_cycle(planner, nmpc, now: float, poses, work: ManagerWork | None = None, count: int | None = None, collision_mask=None,
+                  pose_stride: int = 24, nmpc_plant: bool = True, ltv=None, xv: float = 0.0, state_seq_res: float = 0.1, integral_res_int: int = 4,
+                  resolution: float = 0.01, safe_dis=None, window_margin=None, params=None, mark=None) -> ManagerWork:
+    """One period of plan_manager's MainThread for every robot of a BatchedMSPlanner (manager_create first) / BatchedNmpc pair,
+    enqueued on the stream of `nmpc` (torch's current stream); returns at once.  Who plans, from where, what is delivered under which
+    start time and who is stopped is decided on the device (csrc/fleet_manager.h); there is no per-robot state on the host.
+
+      1. manager_begin            FRESH, REPLAN or nothing for every robot, and the time of the predicted state
+      2. predicted_state_device   (from the handle's first plan on) the state to replan from
+      3. manager_starts           FRESH robots start from their requested start; start_yaw / end_yaw; then the goals for the search
+      4. mission_set_goals        (a handle with missions) under plan_mask
+      5. search_paths_device      under plan_mask
+      6. set_paths_device         under plan_mask
+      7. plan (masked)            the slots of plan_mask that were searched and built: a slot whose search failed is not planned again
+      8. manager_end              the delivery masks, the stop flags, the finish rule
+      9. refs_set_pending_from_backend   twice: fresh_mask with start time now, replan_mask with now + max_replan_time
+     10. refs_stop, plant_stop    under stop_mask (nmpc_plant False: the NMPC handle has no plant; ltv: a BatchedLtvMpc whose plant
+                                  is stopped as well)
+     11. mission_step             (a handle with missions) with after_plan_mask
+
+    poses: float64 device tensor [count][>= 2] or an address with pose_stride bytes between robots (x, y first).  collision_mask: who
+    may replan under replan_on_collision_only (planner.check_mask() after a check_plans of the caller's).  The cold start of a robot
+    that had no trajectory stays with the caller (alore_nmpc.h)."""
+    mark = mark or (lambda name: None)
+    n = int(count or planner.B)
+    w = work or ManagerWork(planner, n)
+    s = nmpc._stream().value
+    if not isinstance(poses, int):
+        pose_stride = int(poses.stride(0) * poses.element_size())
+    planner.manager_begin(now, poses, collision_mask, stride=pose_stride, count=n, stream=s)
+    mark("manager_begin")
+    if w.planned and planner.count >= n:
+        planner.predicted_state_device(n, w.time, w.xytheta, w.vaj, w.oaj, w.forward, resolution, stream=s)
+        mark("predicted_state")
+    planner.manager_starts(n, w.xytheta, w.vaj, w.oaj, w.start_yaw, w.end_yaw, stream=s)
+    w.goal_xy[:n].copy_(w.goal[:2, :n].T)
+    mark("manager_starts")
+    missions = hasattr(planner, "mission_params")
+    if missions:
+        planner.mission_set_goals(w.goal_xy, mask=w.plan_mask, stride=16, count=n, stream=s)
+        mark("mission_set_goals")
+    planner.search_paths_device(n, w.xytheta, w.goal_xy, safe_dis=safe_dis, window_margin=window_margin, mask=w.plan_mask, stream=s)
+    mark("search_paths")
+    v = planner.device_paths()
+    planner.set_paths_device(n, v.max_points, v.n_points, v.xy, w.start_yaw, w.end_yaw, w.vaj, w.oaj, params=params, mask=w.plan_mask,
+                             stream=s)
+    mark("set_paths")
+    w.run_mask[:n].copy_((w.plan_mask[:n] != 0) & (w.search_status[:n] == 0) & (w.build_status[:n] == 0))
+    planner.plan(count=n, mask=w.run_mask, stream=s)
+    w.planned = True
+    mark("plan_masked")
+    planner.manager_end(n, stream=s)
+    mark("manager_end")
+    kw = dict(count=n, xv=xv, state_seq_res=state_seq_res, integral_res_int=integral_res_int)
+    nmpc.refs_set_pending_from_backend(planner, mask=w.fresh_mask, traj_start_time=now, **kw)
+    nmpc.refs_set_pending_from_backend(planner, mask=w.replan_mask, traj_start_time=now + planner.manager_params.max_replan_time, **kw)
+    mark("set_pending")
+    nmpc.refs_stop(w.stop_mask)
+    if nmpc_plant:
+        nmpc.plant_stop(w.stop_mask)
+    if ltv is not None:
+        ltv.plant_stop(w.stop_mask, n)
+    mark("stop")
+    if missions:
+        planner.mission_step(poses, after_plan_mask=w.after_plan_mask, stride=pose_stride, count=n, stream=s)
+        mark("mission_step")
+    return w

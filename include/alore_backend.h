@@ -663,6 +663,95 @@ int alore_backend_device_mission(alore_backend_handle h, alore_backend_mission_v
 int alore_backend_get_mission(alore_backend_handle h, int count, int *status, int *phase, int *goal_item, int *goal_target,
                               int *goal_status, alore_backend_map_edit *edits, int *n_edits, int counters[6]);
 
+/* ---- plan_manager's state machine for the fleet, on the device -------------------------------------------------------- */
+/* What decides in plan_manager: start_callback / goal_callback (plan_manager.hpp:434-468) and PlanManager::MainThread (:556-712),
+ * with the collision stop of PlanTester::MainThread (plan_tester.hpp:529-541), as per-robot device state, one robot per problem slot
+ * of the handle.  csrc/fleet_manager.h holds the rules, states their order of operations and lists the deviations from the
+ * reference; csrc/fleet_manager.hip holds the kernels (one lane per robot).  A manager period is
+ *     manager_begin -> predicted_state_device -> manager_starts -> search_paths / set_paths / plan_masked under plan_mask ->
+ *     manager_end -> refs_set_pending_from_backend under fresh_mask (start time now) and replan_mask (now + max_replan_time) ->
+ *     alore_nmpc_refs_stop / alore_*_plant_stop under stop_mask -> mission_step with after_plan_mask,
+ * all device memory in stream order: nothing waits, and there is no per-robot state on the host.  Calls on one handle must be
+ * ordered on one stream, as for alore_backend_search_paths.
+ * A robot in GOINGTOGOAL or EMERGENCY_STOP leaves that state only through the finish rule (now - traj_start_time >=
+ * traj_total_time), as in the reference. */
+#define ALORE_BE_STATE_INIT 0
+#define ALORE_BE_STATE_IDLE 1
+#define ALORE_BE_STATE_PLANNING 2
+#define ALORE_BE_STATE_REPLAN 3
+#define ALORE_BE_STATE_GOINGTOGOAL 4
+#define ALORE_BE_STATE_EMERGENCY_STOP 5
+#define ALORE_BE_ACTION_NONE 0
+#define ALORE_BE_ACTION_FRESH 1  /* a first plan from the requested start, with zero derivatives */
+#define ALORE_BE_ACTION_REPLAN 2 /* a plan from the state predicted at `time` along the stored plan */
+typedef struct alore_backend_manager_params {
+    double replan_time;           /* 5000 (planner_sim.launch:63) */
+    double max_replan_time;       /* 0.05 (planner_sim.launch:65) */
+    int replan_on_collision_only; /* 0: the reference replans periodically */
+    int stop_inside_obstacle;     /* 0; not 0: the collision stop of plan_tester.hpp:529-541 in front of every begin */
+    int stop_on_no_path;          /* 0: a robot without a path goes to EMERGENCY_STOP and no stop flag is raised (the reference
+                                     publishes nothing there); not 0: the flag is raised */
+    int reserved;                 /* 0 */
+} alore_backend_manager_params;
+void alore_backend_manager_default_params(alore_backend_manager_params *p);
+/* Allocates, once: the slab of max_problems robots (every robot IDLE without goal and start, `returned` 1, all times 0 but plan_start_time
+ * and time, which are -1), the masks and the counters (0).  params NULL: the defaults.  A second call only replaces the parameters.
+ * ALORE_BE_E_INVALID for times that are not finite or a max_replan_time that is negative. */
+int alore_backend_manager_create(alore_backend_handle h, const alore_backend_manager_params *params);
+/* start_callback and goal_callback for robots 0..count-1: x, y, yaw of robot b are the three doubles at (char *)start_xytheta + b *
+ * stride_bytes (a multiple of 8, at least 24), likewise the goal.  Either array may be NULL (not both).  A robot that is not IDLE
+ * refuses both, a value that is not finite is refused; the `refused` counter holds the refusals of THIS call (a start and a goal
+ * count one each).  mask (NULL: every robot) is read as alore_backend_search_paths reads its mask; it is DEVICE memory when
+ * device_pointers != 0.  device_pointers == 0: the arrays are HOST memory, uploaded, and the stream is synchronised. */
+int alore_backend_manager_request(alore_backend_handle h, int count, const double *start_xytheta, const double *goal_xytheta, int stride_bytes,
+                                  int device_pointers, const int *mask, int mask_stride_bytes, void *stream);
+/* The head of MainThread for robots 0..count-1 at time `now`: x, y of robot b are the two doubles at (char *)poses + b *
+ * pose_stride_bytes (a multiple of 8, at least 16).  Writes the action (ALORE_BE_ACTION_*), the predicted time and the five masks
+ * (plan_mask = the action is not NONE; the others 0 but stop_mask of a robot the collision stop fires for).
+ * collision_mask_or_null: the robots that may replan under replan_on_collision_only, read with mask_stride_bytes; the
+ * `collision` words of alore_backend_device_check serve as they lie.  The collision stop reads the handle's map of now.
+ * device_pointers as for alore_backend_manager_request. */
+int alore_backend_manager_begin(alore_backend_handle h, int count, double now, const double *poses, int pose_stride_bytes,
+                                const int *collision_mask_or_null, int mask_stride_bytes, int device_pointers, void *stream);
+/* Behind alore_backend_predicted_state_device, on its outputs (DEVICE, [count][3]): the rows of FRESH robots become the requested
+ * start with zero d_vaj and d_oaj, the predicted pose of REPLAN robots becomes their plan_start_xytheta (:588), rows of other robots
+ * stay bit for bit.  d_start_yaw and d_end_yaw (DEVICE, [count], may be NULL) receive plan_start_xytheta[2] and goal[2] of every
+ * robot: the arrays alore_backend_set_paths reads. */
+int alore_backend_manager_starts(alore_backend_handle h, int count, double *d_xytheta, double *d_vaj, double *d_oaj, double *d_start_yaw,
+                                 double *d_end_yaw, void *stream);
+/* The rest of MainThread with the `now` of the matching begin (without one: ALORE_BE_E_INVALID): the outcome of the robots that
+ * planned, the delivery masks (fresh_mask: deliver with start time now; replan_mask: with now + max_replan_time), after_plan_mask,
+ * stop_mask, then the finish rule.  Each pointer may be NULL, which means the handle's own slab (search status, build status, the
+ * plans' ok words, their durations T [.][max_pieces as rounded by the handle] and piece counts); a pointer that is not NULL is
+ * DEVICE memory of the same layout.  The duration of a plan is the sum of T[0 .. n_pieces - 1] in piece order. */
+int alore_backend_manager_end(alore_backend_handle h, int count, const int *search_status, const int *build_status, const int *plan_ok,
+                              const double *T, const int *n_pieces, void *stream);
+/* Sequencing of a mission's legs (the ALORE FSM sends /planner_start_pose and /planner_goal_pose once per entry of
+ * /task_plan/results): a robot that is IDLE without a goal, whose mission in the slab of alore_backend_task_plan has status >= 0 and
+ * whose `leg` is below n_order takes goal = (leg_goal_xy[leg], leg_yaw[leg]), start = its pose (x, y, yaw at (char *)poses + b *
+ * pose_stride_bytes, a multiple of 8, at least 24), both flags, leg += 1.  Every other robot is untouched.  reset_legs != 0: such a
+ * robot starts again at leg 0 (alore_backend_manager_request never changes `leg`).  All pointers are DEVICE memory; leg_yaw is
+ * [count][ALORE_BE_TASK_MAX_LEGS]. */
+int alore_backend_manager_next_legs(alore_backend_handle h, int count, const double *poses, int pose_stride_bytes, const double *leg_yaw,
+                                    int reset_legs, void *stream);
+/* the device slab [max_problems]; vectors are [3][max_problems] (component-major); valid until the handle is destroyed */
+typedef struct alore_backend_manager_view {
+    int max_problems, n_counters; /* n_counters = 8 */
+    const int *state, *have_goal, *have_start, *leg;
+    const int *action;   /* of the last begin */
+    const int *returned; /* the last begin left MainThread early for this robot: its end does nothing */
+    const int *plan_mask, *fresh_mask, *replan_mask, *stop_mask, *after_plan_mask; /* stride sizeof(int) */
+    const double *goal, *start, *plan_start_xytheta;                               /* [3][max_problems] */
+    const double *loop_start_time, *plan_start_time, *traj_start_time, *traj_total_time;
+    const double *time;  /* the predicted time of the last begin: the d_time of alore_backend_predicted_state_device; -1 for FRESH */
+    const int *counters; /* fresh, replan, going_to_goal, stopped, delivered, arrived (since manager_create), refused (last request), 0 */
+} alore_backend_manager_view;
+int alore_backend_device_manager(alore_backend_handle h, alore_backend_manager_view *out);
+/* The slab of robots 0..count-1 copied to HOST memory: ints [11][count] in the order of the view (state .. after_plan_mask), doubles
+ * [14][count] (goal x, y, yaw, start x, y, yaw, plan_start x, y, yaw, loop_start_time, plan_start_time, traj_start_time,
+ * traj_total_time, time), counters [8].  Any pointer may be NULL.  Waits for the device. */
+int alore_backend_get_manager(alore_backend_handle h, int count, int *ints, double *doubles, int *counters);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,10 @@ void alore_ltv_plant_default_params(alore_ltv_plant_params *p);
 int alore_ltv_plant_init(alore_ltv_handle h, const alore_ltv_plant_params *p, int max_trace_ticks);
 /* pose [B][3], vw [B][2] (NULL: at rest), desired [B][2] (NULL: zeros): host pointers.  Empties the trace.  Synchronises. */
 int alore_ltv_plant_set_state(alore_ltv_handle h, int B, const double *pose, const double *vw, const double *desired, void *stream);
+/* The zero command of emergencyStop (mpc_controller/src/mpc.cpp:616-632) for every robot t < B whose int at (char*)d_mask + t *
+ * mask_stride_bytes is not 0 (DEVICE memory; NULL: every robot): v = omega = 0 and desired = 0.  With alore_nmpc_refs_stop on the
+ * store the robot has no trajectory, gets no command any more and stands (see the table above).  Asynchronous. */
+int alore_ltv_plant_stop(alore_ltv_handle h, int B, const int *d_mask, int mask_stride_bytes, void *stream);
 /* any of pose, vw, at_goal may be NULL.  Synchronises. */
 int alore_ltv_plant_get_state(alore_ltv_handle h, int B, double *pose, double *vw, int *at_goal, void *stream);
 /* device views, valid until alore_ltv_plant_init is called again or the handle is destroyed: pose [B][3] (stride 24 bytes, as the

@@ -380,6 +380,19 @@ int alore_nmpc_refs_set_pending_from_backend(alore_nmpc_handle h, const void *vi
 /* active <- pending for every robot b < B with a valid pending entry and now > its start time (strict, as the reference);
  * the pending entry becomes invalid and the robot's promotion counter goes up by one.  Asynchronous. */
 int alore_nmpc_refs_promote(alore_nmpc_handle h, int B, double now, void *stream);
+/* The controller's side of an emergency stop (emergencyStop, nmpc_controller/src/mpc.cpp:279-294: receive_traj_ = false and a zero
+ * command) for every robot t < B whose int at (char*)d_mask + t * mask_stride_bytes is not 0 (DEVICE memory, read as the mask of
+ * alore_nmpc_refs_set_pending_from_backend; NULL: every robot; the stop_mask of alore_backend_device_manager serves as it lies):
+ * the active AND the pending entry of such a robot become invalid by the `valid` word of their meta rows; every other word of both
+ * stores stays bit for bit.  A start time the handle still remembers for such a pending entry then promotes nothing, which is
+ * harmless.  From the handle's first stop on (it allocates one int per robot), alore_nmpc_closed_loop_tick and
+ * alore_nmpc_ekf_closed_loop_tick hold the command of a stopped robot at zero between their solve and their plant step while it
+ * has no active trajectory (one more small launch per tick), and the *_run functions enqueue their ticks one by one; a promotion
+ * of a later pending entry makes the robot track again (its cold start is the caller's, as after any stand-still).
+ * Asynchronous, nothing crosses the bus. */
+int alore_nmpc_refs_stop(alore_nmpc_handle h, int B, const int *d_mask, int mask_stride_bytes, void *stream);
+/* the zero command in the plant: v = omega = 0 for the robots of the mask (needs alore_nmpc_plant_init).  Asynchronous. */
+int alore_nmpc_plant_stop(alore_nmpc_handle h, int B, const int *d_mask, int mask_stride_bytes, void *stream);
 /* status [B], pending start times [B], validity flags [B], promotion counters [B] to the host (any may be NULL).  Synchronises. */
 int alore_nmpc_refs_pending_status(alore_nmpc_handle h, int B, int *status, double *start_time, int *valid, int *promotions,
                                    void *stream);
