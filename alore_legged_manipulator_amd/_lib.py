@@ -125,10 +125,13 @@ SYMBOLS = (
                                                  C.c_double, C.c_double, C.c_double, C.c_void_p]),
     ("alore_nmpc_refs_set_polynomes", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p]),
     ("alore_nmpc_refs_set_from_backend", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p]),
+    ("alore_nmpc_refs_set_from_backend_xv", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_double, C.c_int, C.c_void_p]),
     ("alore_nmpc_refs_download", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("alore_nmpc_refs_set_pending_polynomes", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p]),
     ("alore_nmpc_refs_set_pending_from_backend", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double,
                                                            C.c_double, C.c_int, C.c_void_p]),
+    ("alore_nmpc_refs_set_pending_from_backend_xv", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
+                                                              C.c_double, C.c_int, C.c_void_p]),
     ("alore_nmpc_refs_promote", C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_void_p]),
     ("alore_nmpc_refs_stop", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     ("alore_nmpc_plant_stop", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),

@@ -71,6 +71,19 @@ class CheckC(C.Structure):
                 ("first_time", C.c_double), ("first_xy", C.c_double * 2), ("min_dist", C.c_double)]
 
 
+class ClassStatC(C.Structure):
+    """alore_backend_class_stat (include/alore_backend.h): the outcome of a plan launch per object class"""
+    _fields_ = [("n", C.c_int), ("n_ok", C.c_int), ("n_collision", C.c_int), ("sum_attempts", C.c_int), ("sum_evals", C.c_longlong),
+                ("max_evals", C.c_int), ("pad", C.c_int), ("min_dist", C.c_double), ("max_duration", C.c_double)]
+
+
+class ClassViewC(C.Structure):
+    """alore_backend_class_view: device addresses of the class table, the class and the effective xv per slot, the counter of
+    clamped indices and the records of the last class_stats"""
+    _fields_ = [("n_classes", C.c_int), ("pad", C.c_int), ("class_of", C.c_void_p), ("xv", C.c_void_p), ("clamped", C.c_void_p),
+                ("classes", C.c_void_p), ("stats", C.c_void_p)]
+
+
 class FrontEndParamsC(C.Structure):
     """alore_front_end_params (include/alore_backend.h); the fields of flat_traj.FrontEndParams"""
     _fields_ = [("distance_weight", C.c_double), ("yaw_weight", C.c_double), ("traj_cut_length", C.c_double),
@@ -191,9 +204,20 @@ CHECK_DTYPE = np.dtype([("collision", np.int32), ("first_panel", np.int32), ("n_
                         ("first_time", np.float64), ("first_xy", np.float64, 2), ("min_dist", np.float64)])
 
 
+# alore_backend_class_stat as a numpy dtype (what class_stats returns)
+CLASS_STAT_DTYPE = np.dtype([("n", np.int32), ("n_ok", np.int32), ("n_collision", np.int32), ("sum_attempts", np.int32),
+                             ("sum_evals", np.int64), ("max_evals", np.int32), ("pad", np.int32), ("min_dist", np.float64),
+                             ("max_duration", np.float64)])
+MAX_CLASSES = 256
+
+
 def _bind(L):
     if getattr(L, "_backend_bound", False):
         return
+    L.alore_backend_set_classes.argtypes = [C.c_void_p, C.c_int, C.POINTER(BackendConfig), C.POINTER(FrontEndParamsC)]
+    L.alore_backend_set_problem_classes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.alore_backend_device_classes.argtypes = [C.c_void_p, C.POINTER(ClassViewC)]
+    L.alore_backend_class_stats.argtypes = [C.c_void_p, C.c_int, C.POINTER(ClassStatC), C.c_void_p]
     L.alore_backend_default_config.argtypes = [C.POINTER(BackendConfig)]
     L.alore_backend_default_config.restype = None
     L.alore_backend_create.argtypes = [C.POINTER(BackendConfig), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -434,6 +458,81 @@ class BatchedMSPlanner:
         self.B = max_problems
         self.count = 0
         self._keep = None
+        self.n_classes = 0
+        self._class_fe = False
+
+    # ---- object classes: one robot model per problem slot (alore_backend_set_classes)
+    def set_classes(self, configs, front_end=None):
+        """The class table: a list of BackendConfig (whole configs), and optionally the front-end parameters per class
+        (flat_traj.FrontEndParams or FrontEndParamsC) that set_paths(params=None) then builds every slot with.  An empty list
+        removes the table.  Waits for the device."""
+        configs = list(configs)
+        n = len(configs)
+        arr = (BackendConfig * max(n, 1))()
+        for k, c in enumerate(configs):
+            C.memmove(C.byref(arr[k]), C.byref(c), C.sizeof(BackendConfig))
+        fe = None
+        if front_end is not None and n:
+            if len(front_end) != n:
+                raise BackendError("set_classes: front_end needs an entry per class")
+            fe = (FrontEndParamsC * n)()
+            for k, p in enumerate(front_end):
+                q = _front_end_params(p)
+                C.memmove(C.byref(fe[k]), C.byref(q), C.sizeof(FrontEndParamsC))
+        self._check(self.L.alore_backend_set_classes(self.h, n, arr if n else None, fe))
+        self.n_classes = n
+        self._class_fe = fe is not None
+
+    def set_problem_classes(self, class_of, count: int | None = None, stream=None):
+        """The class of slots 0..count-1: a NumPy array / list (checked on the host: an index outside the table raises and
+        changes nothing; waits for the stream) or an int32 device tensor (read in stream order, clamped into the table by the
+        kernel, nothing waits: class_view().clamped counts what it clamped)."""
+        if hasattr(class_of, "data_ptr"):
+            if not (class_of.is_cuda and str(class_of.dtype) == "torch.int32" and class_of.dim() == 1 and class_of.is_contiguous()):
+                raise BackendError("set_problem_classes: a contiguous int32 device tensor with a word per slot")
+            n = int(count or class_of.numel())
+            self._check(self.L.alore_backend_set_problem_classes(self.h, n, int(class_of.data_ptr()), 1, _stream(stream)))
+            return
+        k = np.ascontiguousarray(class_of, np.int32).reshape(-1)
+        self._check(self.L.alore_backend_set_problem_classes(self.h, int(count or k.size), k.ctypes.data, 0, _stream(stream)))
+
+    def class_view(self) -> ClassViewC:
+        v = ClassViewC()
+        self._check(self.L.alore_backend_device_classes(self.h, C.byref(v)))
+        return v
+
+    def class_xv(self):
+        """float64 device tensor [max_problems] over the view's xv: the effective ICR offset of every slot, what
+        BatchedNmpc.refs_set_from_backend takes for `xv`"""
+        import torch
+        return torch.as_tensor(_DeviceArray(self.class_view().xv, (self.B,), "<f8"), device="cuda")
+
+    def class_state(self, count: int | None = None) -> dict:
+        """class_of, xv [count] and the clamped counter copied to the host (waits)"""
+        import torch
+        n, v = int(count or self.count or self.B), self.class_view()
+        torch.cuda.synchronize()
+        return {"n_classes": v.n_classes,
+                "class_of": torch.as_tensor(_DeviceArray(v.class_of, (n,), "<i4"), device="cuda").cpu().numpy(),
+                "xv": torch.as_tensor(_DeviceArray(v.xv, (n,), "<f8"), device="cuda").cpu().numpy(),
+                "clamped": int(torch.as_tensor(_DeviceArray(v.clamped, (1,), "<i4"), device="cuda").cpu()[0])}
+
+    def class_stats(self, fetch: bool = True, count: int | None = None, stream=None):
+        """Per class, the outcome of slots 0..count-1 of the last plan launch, reduced on the device: a CLASS_STAT_DTYPE array
+        [max(n_classes, 1)].  fetch=False: the records stay in the slab of class_view().stats and nothing waits."""
+        n = int(count or self.count)
+        if not fetch:
+            self._check(self.L.alore_backend_class_stats(self.h, n, None, _stream(stream)))
+            return None
+        rec = np.zeros(max(self.n_classes, 1), CLASS_STAT_DTYPE)
+        self._check(self.L.alore_backend_class_stats(self.h, n, rec.ctypes.data_as(C.POINTER(ClassStatC)), _stream(stream)))
+        return rec
+
+    def _fe_arg(self, params):
+        """the fe argument of alore_backend_set_paths: NULL when the class table carries front-end parameters and none are given"""
+        if params is None and self._class_fe:
+            return None
+        return C.byref(_front_end_params(params))
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:
@@ -796,9 +895,8 @@ class BatchedMSPlanner:
         mk = None if mask is None else np.ascontiguousarray(np.asarray(mask).astype(bool), np.int32)
         pc = PathsC(xy.shape[1], npts.ctypes.data, xy.ctypes.data, sy.ctypes.data, ey.ctypes.data,
                     None if vaj is None else vaj.ctypes.data, None if oaj is None else oaj.ctypes.data)
-        fe = _front_end_params(params)
         self.count = n  # the handle's count changes whether or not every path builds
-        self._check(self.L.alore_backend_set_paths(self.h, n, C.byref(pc), C.byref(fe), 0, None if mk is None else mk.ctypes.data, 4, None))
+        self._check(self.L.alore_backend_set_paths(self.h, n, C.byref(pc), self._fe_arg(params), 0, None if mk is None else mk.ctypes.data, 4, None))
 
     def set_paths_device(self, count, max_points, n_points, xy, start_yaw, end_yaw, start_vaj=None, start_oaj=None, params=None, mask=None,
                          mask_stride=4, stream=None):
@@ -806,9 +904,8 @@ class BatchedMSPlanner:
         end_yaw [count], start_vaj / start_oaj [count][3]) or raw device addresses; mask as for plan().  Nothing is copied but the
         argument block and nothing waits; build_status() has the outcome per slot."""
         pc = PathsC(int(max_points), _dev(n_points), _dev(xy), _dev(start_yaw), _dev(end_yaw), _dev(start_vaj), _dev(start_oaj))
-        fe = _front_end_params(params)
         mp, ms = _mask(mask, mask_stride)
-        self._check(self.L.alore_backend_set_paths(self.h, int(count), C.byref(pc), C.byref(fe), 1, mp, ms, _stream(stream)))
+        self._check(self.L.alore_backend_set_paths(self.h, int(count), C.byref(pc), self._fe_arg(params), 1, mp, ms, _stream(stream)))
         self.count = int(count)
 
     def build_status(self, count: int | None = None) -> np.ndarray:
@@ -1144,6 +1241,13 @@ class BatchedMSPlanner:
             out[b, :len(x)] = x
         return out
 
+    def _configured(self, value, of_cfg):
+        """safe_dis / time_weight of eval and lbfgs: a given value holds for every slot; None is the configured one -- the
+        handle's config's, or with a class table NaN, which the library resolves to the slot's class's"""
+        if value is not None:
+            return float(value)
+        return float("nan") if self.n_classes else of_cfg
+
     def eval(self, stage: int, xs, lam=None, rho=None, safe_dis=None, time_weight=None):
         n = len(xs)
         X = self.pack_x(xs)
@@ -1151,8 +1255,8 @@ class BatchedMSPlanner:
         lam = None if lam is None else np.ascontiguousarray(np.broadcast_to(lam, (n, 2)), dtype=np.float64)
         rho = None if rho is None else np.ascontiguousarray(np.broadcast_to(rho, (n, 2)), dtype=np.float64)
         self._check(self.L.alore_backend_eval(self.h, n, stage, _dp(X), _dp(lam), _dp(rho),
-                                              self.cfg.safe_dis if safe_dis is None else safe_dis,
-                                              self.cfg.w_time if time_weight is None else time_weight, _dp(cost), _dp(grad),
+                                              self._configured(safe_dis, self.cfg.safe_dis),
+                                              self._configured(time_weight, self.cfg.w_time), _dp(cost), _dp(grad),
                                               _dp(err), None))
         return {"cost": cost, "grad": [grad[b, :len(xs[b])] for b in range(n)], "xy_err": err}
 
@@ -1164,8 +1268,8 @@ class BatchedMSPlanner:
         lam = None if lam is None else np.ascontiguousarray(np.broadcast_to(lam, (n, 2)), dtype=np.float64)
         rho = None if rho is None else np.ascontiguousarray(np.broadcast_to(rho, (n, 2)), dtype=np.float64)
         self._check(self.L.alore_backend_lbfgs(self.h, n, stage, _dp(X), _dp(lam), _dp(rho),
-                                               self.cfg.safe_dis if safe_dis is None else safe_dis,
-                                               self.cfg.w_time if time_weight is None else time_weight, max_iter, _dp(cost),
+                                               self._configured(safe_dis, self.cfg.safe_dis),
+                                               self._configured(time_weight, self.cfg.w_time), max_iter, _dp(cost),
                                                ret, it, ev, _dp(err), None))
         return {"x": [X[b, :len(xs[b])] for b in range(n)], "cost": cost, "ret": np.array(ret[:]), "iters": np.array(it[:]),
                 "evals": np.array(ev[:]), "xy_err": err}

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "backend_classes.h"
 #include "backend_kernels.h"
 #include "flat_traj_build.h"
 #include "fleet_manager.h"
@@ -117,6 +118,17 @@ struct alore_backend_planner {
     fleet::Slab g_slab{};
     char *g_mem = nullptr, *g_stage = nullptr;
     double g_now = 0.0;
+    // alore_backend_set_classes / _set_problem_classes: the table of configs (and front-end parameters) for bclass::MAX_CLASSES
+    // classes, the class and the effective xv of every slot, the counter of clamped indices, the staging of host indices and the
+    // records of alore_backend_class_stats; allocated by the first call of that section
+    int n_classes = 0; // 0: no table, every slot is planned with cfg
+    bool class_fe = false;
+    alore_backend_config* k_table = nullptr;
+    alore_front_end_params* k_fe = nullptr;
+    int *k_class_of = nullptr, *k_clamped = nullptr, *k_stage = nullptr;
+    double* k_xv = nullptr;
+    alore_backend_class_stat* k_stats = nullptr;
+    backend::Params* k_params = nullptr; // the parameter block per class that a launch with classes reads (backend::launch)
 };
 
 namespace {
@@ -204,7 +216,7 @@ void free_all(alore_backend_handle h)
                     h->d_search_in, h->d_path_n, h->d_path_cost, h->d_search_status, h->d_search_sweeps, h->d_path_xy,
                     h->d_task_in, h->t_status, h->t_matrix, h->t_order, h->t_n_order, h->t_total, h->t_fields, h->t_sweeps, h->t_src_fields,
                     h->t_src_sweeps, h->t_leg_start, h->t_leg_goal, h->p_desc, h->p_counters, h->p_host_edits, h->m_slab_mem, h->m_stage, h->m_edits,
-                    h->g_mem, h->g_stage};
+                    h->g_mem, h->g_stage, h->k_table, h->k_fe, h->k_class_of, h->k_clamped, h->k_stage, h->k_xv, h->k_stats, h->k_params};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_task) (void)hipHostFree(h->h_task);
@@ -241,6 +253,7 @@ backend::Params base_params(alore_backend_handle h, int count, int mode)
     p.err_out = h->d_err;
     p.ret_out = h->d_ret;
     p.stamps = h->d_stamps;
+    if (h->n_classes) { p.classes = h->k_table; p.class_of = h->k_class_of; p.class_params = h->k_params; p.n_classes = h->n_classes; }
     return p;
 }
 
@@ -317,10 +330,8 @@ int alore_backend_create(const alore_backend_config* cfg, int device, int max_pi
 {
     if (!cfg || !out || max_pieces < 1 || max_problems < 1) return ALORE_BE_E_INVALID;
     *out = nullptr;
-    if (cfg->sparse_res != 8 || cfg->n_check < 0 || cfg->n_check > 8 || cfg->lbfgs.mem_size < 1 || cfg->lbfgs.mem_size > backend::MEM_MAX ||
-        cfg->path_lbfgs.mem_size < 1 || cfg->path_lbfgs.mem_size > backend::MEM_MAX || cfg->lbfgs.past > 16 || cfg->path_lbfgs.past > 16 ||
-        cfg->shot_path_past > 16 || cfg->final_check_num < 1 || cfg->final_check_num > 64)
-        return ALORE_BE_E_UNSUPPORTED;
+    static_assert(bclass::MEM_MAX == backend::MEM_MAX, "backend_classes.h checks mem_size against the history the kernel has");
+    if (bclass::invalid_field(*cfg)) return ALORE_BE_E_UNSUPPORTED;
     if (max_pieces > 32) return ALORE_BE_E_UNSUPPORTED;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ALORE_BE_E_NO_DEVICE;
@@ -452,6 +463,7 @@ int alore_backend_predicted_state(alore_backend_handle h, int count, double reso
         backend::PredictArgs g{count, h->P, h->d_M, h->r_T, h->r_coef, h->d_sxyt, start_time ? d_in + n : nullptr, d_in,
                                start_xytheta ? d_in + 2 * n : nullptr, resolution, h->cfg.icr_xv, h->cfg.standard_diff != 0,
                                d_out, d_out + 3 * n, d_out + 6 * n, d_fwd};
+        if (h->n_classes) { g.classes = h->k_table; g.class_of = h->k_class_of; }
         e = backend::predicted_state(g, nullptr);
     }
     if (e == hipSuccess && xytheta) e = hipMemcpy(xytheta, d_out, sizeof(double) * n * 3, hipMemcpyDeviceToHost);
@@ -474,6 +486,7 @@ int alore_backend_predicted_state_device(alore_backend_handle h, int count, doub
     BE_TRY(h, hipSetDevice(h->device));
     backend::PredictArgs g{count, h->P, h->d_M, h->r_T, h->r_coef, h->d_sxyt, d_start_time, d_time, d_start_xytheta, resolution,
                            h->cfg.icr_xv, h->cfg.standard_diff != 0, d_xytheta, d_vaj, d_oaj, d_forward};
+    if (h->n_classes) { g.classes = h->k_table; g.class_of = h->k_class_of; }
     BE_TRY(h, backend::predicted_state(g, (hipStream_t)stream));
     return ALORE_BE_OK;
 }
@@ -495,6 +508,7 @@ int alore_backend_path_points(alore_backend_handle h, int count, int panels_per_
     if (e == hipSuccess) {
         backend::PathArgs g{count, h->P, panels_per_piece, h->d_M, h->r_ok, h->r_T, h->r_coef, h->d_sxyt, h->cfg.icr_xv, h->cfg.standard_diff != 0,
                             d_xy, d_yaw, d_n};
+        if (h->n_classes) { g.classes = h->k_table; g.class_of = h->k_class_of; }
         e = backend::path_points(g, nullptr);
     }
     if (e == hipSuccess) e = hipMemcpy(xy, d_xy, sizeof(double) * n * per * 2, hipMemcpyDeviceToHost);
@@ -596,6 +610,7 @@ int alore_backend_set_paths(alore_backend_handle h, int count, const alore_backe
     backend::BuildArgs g{};
     g.count = count; g.P = h->P; g.K = p->max_points;
     g.fe = prm;
+    if (!fe && h->n_classes && h->class_fe) { g.fe_classes = h->k_fe; g.class_of = h->k_class_of; } // the slot's class's parameters
     size_t up = BUILD_ARGS_BYTES;
     if (device_pointers) {
         g.n_points = p->n_points; g.xy = p->xy; g.start_yaw = p->start_yaw; g.end_yaw = p->end_yaw;
@@ -735,6 +750,165 @@ int alore_backend_replan_mask(alore_backend_handle h, int count, int* out_mask, 
     return ALORE_BE_OK;
 }
 
+// ---- object classes ----------------------------------------------------------------------------------------------------------
+// Slot b takes the index in[b] (in null: keeps its own), brought into the table of n classes: an index read from `in` is clamped
+// and counted, a kept one that the table no longer holds becomes class 0.  xv[b] is the effective ICR offset of the slot's class
+// (table null: xv0, the handle's config's).
+static __global__ void class_assign_kernel(const int* in, int count, int n, const alore_backend_config* table, double xv0, int* class_of,
+                                           double* xv, int* clamped)
+{
+    const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (b >= count) return;
+    int k = in ? in[b] : class_of[b];
+    if (in) {
+        const int c = bclass::clamp_class(k, n);
+        if (c != k) atomicAdd(clamped, 1);
+        k = c;
+    } else if (k < 0 || k >= n) k = 0;
+    class_of[b] = k;
+    xv[b] = table ? bclass::effective_xv(table[k]) : xv0;
+}
+
+// One workgroup per class: every thread folds the slots of the class in its stride (bclass::stat_add), the workgroup folds its
+// threads in a tree (bclass::stat_merge).  Integer sums, minima and maxima: the result does not depend on either order.
+static __global__ __launch_bounds__(256) void class_stats_kernel(const int* class_of, const alore_backend_status* status, const double* T, int P,
+                                                                 int count, alore_backend_class_stat* out)
+{
+    __shared__ alore_backend_class_stat sh[256];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    alore_backend_class_stat s;
+    bclass::stat_init(s);
+    for (int b = tid; b < count; b += 256) {
+        if ((class_of ? class_of[b] : 0) != k) continue;
+        const alore_backend_status st = status[b];
+        bclass::stat_add(s, st, bclass::plan_duration(T + (size_t)b * P, bclass::pieces_of(st, P)));
+    }
+    sh[tid] = s;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if (tid < w) bclass::stat_merge(sh[tid], sh[tid + w]);
+        __syncthreads();
+    }
+    if (tid == 0) out[k] = sh[0];
+}
+
+// the buffers of this section, once: every slot class 0 with the xv of the handle's config
+static int ensure_classes(alore_backend_handle h)
+{
+    if (h->k_class_of) return ALORE_BE_OK;
+    BE_TRY(h, hipSetDevice(h->device));
+    const size_t B = (size_t)h->B;
+    hipError_t e = hipSuccess;
+    auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    A(dalloc(&h->k_table, (size_t)bclass::MAX_CLASSES)); A(dalloc(&h->k_fe, (size_t)bclass::MAX_CLASSES)); A(dalloc(&h->k_clamped, 1));
+    A(dalloc(&h->k_stage, B)); A(dalloc(&h->k_xv, B)); A(dalloc(&h->k_stats, (size_t)bclass::MAX_CLASSES)); A(dalloc(&h->k_class_of, B));
+    A(dalloc(&h->k_params, (size_t)bclass::MAX_CLASSES));
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(class_assign_kernel, dim3((unsigned)((h->B + 255) / 256)), dim3(256), 0, nullptr, (const int*)nullptr, h->B,
+                           bclass::MAX_CLASSES, (const alore_backend_config*)nullptr, bclass::effective_xv(h->cfg), h->k_class_of, h->k_xv, h->k_clamped);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        void* ptrs[] = {h->k_table, h->k_fe, h->k_clamped, h->k_stage, h->k_xv, h->k_stats, h->k_class_of, h->k_params};
+        for (void* p : ptrs)
+            if (p) (void)hipFree(p);
+        h->k_table = nullptr; h->k_fe = nullptr; h->k_clamped = h->k_stage = h->k_class_of = nullptr; h->k_xv = nullptr; h->k_stats = nullptr; h->k_params = nullptr;
+        return fail(h, e == hipErrorOutOfMemory ? ALORE_BE_E_NOMEM : ALORE_BE_E_HIP, "classes: allocation", e);
+    }
+    return ALORE_BE_OK;
+}
+
+int alore_backend_set_classes(alore_backend_handle h, int n_classes, const alore_backend_config* classes, const alore_front_end_params* fe)
+{
+    if (!h || n_classes < 0 || n_classes > bclass::MAX_CLASSES || (n_classes > 0 && !classes))
+        return fail(h, ALORE_BE_E_INVALID, "set_classes: n_classes must be 0 .. 256, with a table");
+    for (int k = 0; k < n_classes; ++k) {
+        if (const char* f = bclass::class_error(classes[k], h->cfg)) {
+            const bool sizing = bclass::sizing_mismatch(classes[k], h->cfg) != nullptr;
+            h->err = "set_classes: class " + std::to_string(k) + ": " + f + (sizing ? " must equal the handle's" : " is outside what this build supports");
+            return ALORE_BE_E_INVALID;
+        }
+        if (fe && (!(fe[k].sample_time > 0.0) || !(fe[k].max_vel > 0.0) || !(fe[k].max_acc > 0.0) || fe[k].min_traj_num < 1)) {
+            h->err = "set_classes: class " + std::to_string(k) + ": front-end sample_time, max_vel, max_acc and min_traj_num must be positive";
+            return ALORE_BE_E_INVALID;
+        }
+    }
+    if (int rc = ensure_classes(h)) return rc;
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, hipDeviceSynchronize()); // a launch in flight may still read the table
+    if (n_classes) BE_TRY(h, hipMemcpy(h->k_table, classes, sizeof(alore_backend_config) * (size_t)n_classes, hipMemcpyHostToDevice));
+    if (n_classes && fe) BE_TRY(h, hipMemcpy(h->k_fe, fe, sizeof(alore_front_end_params) * (size_t)n_classes, hipMemcpyHostToDevice));
+    h->n_classes = n_classes;
+    h->class_fe = n_classes > 0 && fe != nullptr;
+    // without a table the indices stay as they are (nothing reads them) and every xv is the handle's config's
+    hipLaunchKernelGGL(class_assign_kernel, dim3((unsigned)((h->B + 255) / 256)), dim3(256), 0, nullptr, (const int*)nullptr, h->B,
+                       n_classes ? n_classes : bclass::MAX_CLASSES, n_classes ? (const alore_backend_config*)h->k_table : nullptr,
+                       bclass::effective_xv(h->cfg), h->k_class_of, h->k_xv, h->k_clamped);
+    BE_TRY(h, hipGetLastError());
+    BE_TRY(h, hipDeviceSynchronize());
+    return ALORE_BE_OK;
+}
+
+int alore_backend_set_problem_classes(alore_backend_handle h, int count, const int* class_of, int device_pointer, void* stream)
+{
+    if (!h || count < 1 || count > h->B || !class_of) return fail(h, ALORE_BE_E_INVALID, "set_problem_classes: bad argument");
+    const int n = h->n_classes ? h->n_classes : 1;
+    if (!device_pointer)
+        for (int b = 0; b < count; ++b)
+            if (class_of[b] < 0 || class_of[b] >= n) {
+                h->err = "set_problem_classes: slot " + std::to_string(b) + " has class " + std::to_string(class_of[b]) + ", outside the table of " +
+                         std::to_string(n);
+                return ALORE_BE_E_INVALID;
+            }
+    if (int rc = ensure_classes(h)) return rc;
+    BE_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int* src = class_of;
+    if (!device_pointer) {
+        BE_TRY(h, hipMemcpyAsync(h->k_stage, class_of, sizeof(int) * (size_t)count, hipMemcpyHostToDevice, s));
+        src = h->k_stage;
+    }
+    hipLaunchKernelGGL(class_assign_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, src, count, n,
+                       h->n_classes ? (const alore_backend_config*)h->k_table : nullptr, bclass::effective_xv(h->cfg), h->k_class_of, h->k_xv,
+                       h->k_clamped);
+    BE_TRY(h, hipGetLastError());
+    if (!device_pointer) BE_TRY(h, hipStreamSynchronize(s));
+    return ALORE_BE_OK;
+}
+
+int alore_backend_device_classes(alore_backend_handle h, alore_backend_class_view* out)
+{
+    if (!h || !out) return fail(h, ALORE_BE_E_INVALID, "device_classes: bad argument");
+    if (int rc = ensure_classes(h)) return rc;
+    out->n_classes = h->n_classes;
+    out->pad = 0;
+    out->class_of = h->k_class_of;
+    out->xv = h->k_xv;
+    out->clamped = h->k_clamped;
+    out->classes = h->n_classes ? h->k_table : nullptr;
+    out->stats = h->k_stats;
+    return ALORE_BE_OK;
+}
+
+int alore_backend_class_stats(alore_backend_handle h, int count, alore_backend_class_stat* out, void* stream)
+{
+    if (!h || count < 1 || count > h->B) return fail(h, ALORE_BE_E_INVALID, "class_stats: bad argument");
+    if (!h->timed || count > h->count) return fail(h, ALORE_BE_E_INVALID, "class_stats: no plan has run for these slots (alore_backend_plan first)");
+    if (int rc = ensure_classes(h)) return rc;
+    BE_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int n = h->n_classes ? h->n_classes : 1;
+    hipLaunchKernelGGL(class_stats_kernel, dim3((unsigned)n), dim3(256), 0, s, h->n_classes ? (const int*)h->k_class_of : nullptr,
+                       (const alore_backend_status*)h->r_status, (const double*)h->r_T, h->P, count, h->k_stats);
+    BE_TRY(h, hipGetLastError());
+    if (out) {
+        BE_TRY(h, hipMemcpyAsync(out, h->k_stats, sizeof(alore_backend_class_stat) * (size_t)n, hipMemcpyDeviceToHost, s));
+        BE_TRY(h, hipStreamSynchronize(s));
+    }
+    return ALORE_BE_OK;
+}
+
 int alore_backend_last_plan_ms(alore_backend_handle h, float* ms)
 {
     if (!h || !ms || !h->timed) return fail(h, ALORE_BE_E_INVALID, "last_plan_ms: no plan yet");
@@ -790,7 +964,7 @@ int alore_backend_check_plans(alore_backend_handle h, int count, const double* t
     if (!h) return ALORE_BE_E_INVALID;
     if (count < 1 || count > h->B) return fail(h, ALORE_BE_E_INVALID, "check_plans: count out of range");
     if (!std::isfinite(min_safe_dis)) return fail(h, ALORE_BE_E_INVALID, "check_plans: min_safe_dis is not finite");
-    if (body && h->cfg.n_check == 0) return fail(h, ALORE_BE_E_INVALID, "check_plans: body check asked for, but the configuration has no check points");
+    if (body && !h->n_classes && h->cfg.n_check == 0) return fail(h, ALORE_BE_E_INVALID, "check_plans: body check asked for, but the configuration has no check points");
     if (!h->d_map) return fail(h, ALORE_BE_E_INVALID, "check_plans: no map (alore_backend_set_map / alore_backend_build_esdf)");
     if (!h->timed || count > h->count) return fail(h, ALORE_BE_E_INVALID, "check_plans: no finished plan for these slots (alore_backend_plan first)");
     for (int b = 0; b < count; ++b) { // the caller's arrays last: only a call that can run reads them
@@ -816,6 +990,7 @@ int alore_backend_check_plans(alore_backend_handle h, int count, const double* t
     g.xv = h->cfg.standard_diff ? 0.0 : h->cfg.icr_xv;
     std::memcpy(g.check_pts, h->cfg.check_pts, sizeof(g.check_pts));
     g.out = h->d_check;
+    if (h->n_classes) { g.classes = h->k_table; g.class_of = h->k_class_of; g.use_class_thr = min_safe_dis > 0.0 ? 0 : 1; }
     std::memcpy(h->h_check, &g, sizeof(g));
     if (t_from) std::memcpy(h_win, t_from, sizeof(double) * n);
     if (t_to) std::memcpy(h_win + n, t_to, sizeof(double) * n);
@@ -857,8 +1032,10 @@ static int run_piece(alore_backend_handle h, int count, int mode, int stage, dou
     p.max_iter = max_iter;
     p.lam_in = lam ? h->d_lam : nullptr;
     p.rho_in = rho ? h->d_rho : nullptr;
-    p.safe_dis = safe_dis;
-    p.time_weight = time_weight;
+    // NaN: the configured value.  Without a table that is the handle's config, here; with one the slot's class's, which
+    // class_params_kernel writes into the class's copy of the block (backend::launch)
+    p.safe_dis = std::isnan(safe_dis) && !h->n_classes ? h->cfg.safe_dis : safe_dis;
+    p.time_weight = std::isnan(time_weight) && !h->n_classes ? h->cfg.w_time : time_weight;
     BE_TRY(h, backend::launch(p, h->d_params, h->P, s));
     std::vector<int> r3((size_t)n * 3);
     if (cost) BE_TRY(h, hipMemcpyAsync(cost, h->d_cost, sizeof(double) * n, hipMemcpyDeviceToHost, s));

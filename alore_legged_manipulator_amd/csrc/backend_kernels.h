@@ -75,6 +75,13 @@ struct Params {
     // alore_backend_plan_masked: a workgroup whose slot b has the int at (char*)mask + b * mask_stride equal to 0 returns at entry
     const int* mask; // null: every slot is planned
     int mask_stride; // bytes
+    // object classes (alore_backend_set_classes): slot b is planned with classes[class_of[b]]; all null: with cfg.  class_params:
+    // [n_classes] copies of this block, block k with cfg = classes[k], written on the device in front of the launch (launch()); the
+    // workgroup of slot b reads its parameters from block class_of[b].  Nothing of this is written by the optimiser kernel
+    const Config* classes;
+    const int* class_of; // [B]
+    const Params* class_params;
+    int n_classes;
 };
 
 size_t lds_bytes(int P);
@@ -94,6 +101,10 @@ struct CheckArgs {
     double min_safe_dis, xv;      // xv: 0 for the standard differential model
     double check_pts[8][2];
     alore_backend_check* out;     // [count]
+    // object classes: R, n_check, xv, check_pts and (use_class_thr) the threshold of slot b from classes[class_of[b]]; null: the above
+    const Config* classes;
+    const int* class_of;          // [B]
+    int use_class_thr;            // min_safe_dis <= 0 was asked for: the class's final_min_safe_dis
 };
 // the kernel reads its arguments from d_args (device memory, filled in stream order before the launch)
 hipError_t check_plans(const CheckArgs* d_args, int count, hipStream_t s);
@@ -113,6 +124,9 @@ struct BuildArgs {
     double *inner, *init_T, *positions, *head, *tail, *start_xy, *final_xy, *sxyt;
     int* status; // [count] build status: 0 built, 1 masked out, -1 bad point count, -2 more pieces than the slot holds
     int* order;  // [count] launch order: most pieces first, stable in the slot index
+    // object classes: slot b is built with fe_classes[class_of[b]]; null: with fe
+    const alore_front_end_params* fe_classes;
+    const int* class_of; // [B]
 };
 // both kernels read their arguments from d_args (device memory, filled in stream order before the launch)
 hipError_t build_problems(const BuildArgs* d_args, int count, hipStream_t s);
@@ -179,6 +193,9 @@ struct PredictArgs {
     bool standard_diff;
     double *xyt_out, *vaj_out, *oaj_out;
     int* forward_out;
+    // object classes: xv and standard_diff of slot b from classes[class_of[b]]; null: the above
+    const Config* classes;
+    const int* class_of;
 };
 hipError_t predicted_state(const PredictArgs& g, hipStream_t s);
 // MSPlanner::mincoPointPub on the plans of the last launch (esdf_build.hip)
@@ -193,6 +210,9 @@ struct PathArgs {
     double* xy_out;                // [B][P (res + 1)][2]
     double* yaw_out;               // [B][P res] or null
     int* n_out;                    // [B] points written
+    // object classes: xv and standard_diff of slot b from classes[class_of[b]]; null: the above
+    const Config* classes;
+    const int* class_of;
 };
 hipError_t path_points(const PathArgs& g, hipStream_t s);
 

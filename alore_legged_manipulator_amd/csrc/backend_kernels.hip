@@ -1378,19 +1378,26 @@ __device__ void load_problem(const Params& prm, unsigned lbase, int b)
 // poses (dead by then), the two-loop recursion's alpha[] those of a node array (it runs between two evaluations).  What fits a CU
 // was measured (tools/micro/lds_fit.hip): 8 workgroups up to 20480 B each, 7 up to 23040, 6 up to 26880, 5 up to 31744 -- not
 // 160 KB / n: the runtime's occupancy query is one too optimistic just below those sizes.
-template <int P>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void backend_kernel(const Params* __restrict__ gp)
+// Object classes (alore_backend_set_classes): the class of a problem is bound ONCE, at entry, by moving the parameter-block pointer
+// to the class's own copy of the block (class_params_kernel below writes one per class in front of the launch: this block with cfg =
+// the class's config).  One workgroup is one problem, so the move is wave-uniform; everything after it -- eval_cost, lbfgs,
+// final_collision, the body -- reads `prm.cfg` through its pointer as before, at constant offsets and by scalar loads, and holds no
+// class index and no second pointer.  CLASSES = false, the instantiation a handle without a table launches, has no such move: it
+// is the kernel of before, instruction for instruction; the noinline functions are shared by both.
+template <int P, bool CLASSES>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void backend_kernel(const Params* __restrict__ gp0)
 {
-    if (gp->stamps && blockIdx.x == 0 && threadIdx.x == 0) gp->stamps[63] = (long long)__builtin_readcyclecounter();
-    const Params& prm = *gp;
+    if (gp0->stamps && blockIdx.x == 0 && threadIdx.x == 0) gp0->stamps[63] = (long long)__builtin_readcyclecounter();
     const unsigned lbase = lds_base_of_kernel();
     LDSQ Lds<P>& L = lds<P>(lbase);
     LDSQ EvalCtx& e = L.e;
     const int lane = threadIdx.x;
-    if ((int)blockIdx.x >= prm.count) return;
-    const int b = prm.order ? prm.order[blockIdx.x] : (int)blockIdx.x;
+    if ((int)blockIdx.x >= gp0->count) return;
+    const int b = gp0->order ? gp0->order[blockIdx.x] : (int)blockIdx.x;
     // alore_backend_plan_masked: a slot the mask leaves out keeps its stored plan (nothing below runs, no barrier has been passed)
-    if (prm.mask && *(const int*)((const char*)prm.mask + (size_t)b * prm.mask_stride) == 0) return;
+    if (gp0->mask && *(const int*)((const char*)gp0->mask + (size_t)b * gp0->mask_stride) == 0) return;
+    const Params* gp = CLASSES ? gp0->class_params + gp0->class_of[b] : gp0;
+    const Params& prm = *gp;
     const Config& c = prm.cfg;
     load_problem<P>(prm, lbase, b);
     const int M = uni(e.M), n = uni(e.n), nstride = 3 * prm.prob.P;
@@ -1541,16 +1548,31 @@ size_t lds_bytes(int P)
     return P <= 16 ? sizeof(Lds<16>) : sizeof(Lds<32>);
 }
 
+// block k of class_params <- the launch's block with the config of class k; safe_dis / time_weight of alore_backend_eval / _lbfgs
+// given as NaN (the configured value) become the class's here, so the optimiser reads them as it reads an explicit argument
+__global__ void class_params_kernel(const Params* __restrict__ gp)
+{
+    const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (k >= gp->n_classes) return;
+    Params* out = const_cast<Params*>(gp->class_params) + k;
+    *out = *gp;
+    out->cfg = gp->classes[k];
+    if (gp->safe_dis != gp->safe_dis) out->safe_dis = out->cfg.safe_dis;
+    if (gp->time_weight != gp->time_weight) out->time_weight = out->cfg.w_time;
+}
+
 hipError_t launch(const Params& p, const Params* d_params, int P, hipStream_t s)
 {
-    const void* fn = P <= 16 ? (const void*)backend_kernel<16> : (const void*)backend_kernel<32>;
+    const bool classes = p.class_params != nullptr;
+    const void* fn = classes ? (P <= 16 ? (const void*)backend_kernel<16, true> : (const void*)backend_kernel<32, true>)
+                             : (P <= 16 ? (const void*)backend_kernel<16, false> : (const void*)backend_kernel<32, false>);
     const size_t lds = lds_bytes(P);
-    static size_t configured[16][2] = {{0}};
+    static size_t configured[16][4] = {{0}};
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     dev &= 15;
-    const int v = P <= 16 ? 0 : 1;
+    const int v = (P <= 16 ? 0 : 1) + (classes ? 2 : 0);
     if (lds > configured[dev][v]) {
         e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -1559,6 +1581,10 @@ hipError_t launch(const Params& p, const Params* d_params, int P, hipStream_t s)
     e = hipMemcpyAsync(const_cast<Params*>(d_params), &p, sizeof(Params), hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return e;
     void* args[] = {&d_params};
+    if (classes) {
+        e = hipLaunchKernel((const void*)class_params_kernel, dim3((unsigned)((p.n_classes + 63) / 64)), dim3(64), args, 0, s);
+        if (e != hipSuccess) return e;
+    }
     e = hipLaunchKernel(fn, dim3(p.count), dim3(64), args, lds, s);
     if (e != hipSuccess) return e;
     return hipGetLastError();
@@ -1578,12 +1604,15 @@ __global__ __launch_bounds__(64) void check_plans_kernel(const CheckArgs* __rest
     const int b = blockIdx.x, lane = threadIdx.x;
     if (b >= a.count) return;
     constexpr double BIG = 1.79769313486231570815e+308;
-    const int P = a.P, R = a.R, M = min(max(uni(a.n_pieces[b]), 0), P), NP = R * M;
+    // the slot's robot model (alore_backend_set_classes): wave-uniform, read by scalar loads like the argument block
+    const CSTQ Config* kc = a.classes ? (const CSTQ Config*)a.classes + ((const CSTQ int*)a.class_of)[b] : nullptr;
+    const int P = a.P, R = kc ? kc->final_check_num : a.R, M = min(max(uni(a.n_pieces[b]), 0), P), NP = R * M;
     const GLBQ double* Tg = (const GLBQ double*)a.T + (size_t)b * P;
     const GLBQ double* cg = (const GLBQ double*)a.coef + (size_t)b * P * 12;
-    const double xvI = a.xv, map_inv = 1.0 / a.map.res, thr = a.min_safe_dis;
+    const double xvI = kc ? (kc->standard_diff ? 0.0 : kc->icr_xv) : a.xv, map_inv = 1.0 / a.map.res;
+    const double thr = kc && a.use_class_thr ? kc->final_min_safe_dis : a.min_safe_dis;
     const double t_from = a.t_from ? a.t_from[b] : 0.0, t_to = a.t_to ? a.t_to[b] : __builtin_inf();
-    const int nq = a.body ? a.n_check : 0;
+    const int nq = a.body ? (kc ? kc->n_check : a.n_check) : 0;
     double carry_x = a.plan_start_xyt[(size_t)b * 3], carry_y = a.plan_start_xyt[(size_t)b * 3 + 1], mind = BIG;
     int first = -1, n_checked = 0;
     double first_t = -1.0, first_x = 0.0, first_y = 0.0;
@@ -1618,7 +1647,7 @@ __global__ __launch_bounds__(64) void check_plans_kernel(const CheckArgs* __rest
             double gx, gy;
             dist = esdf(a.map, map_inv, px, py, false, 0.0, gx, gy);
             for (int k = 0; k < nq; ++k) {
-                const double bx = a.check_pts[k][0], by = a.check_pts[k][1];
+                const double bx = kc ? kc->check_pts[k][0] : a.check_pts[k][0], by = kc ? kc->check_pts[k][1] : a.check_pts[k][1];
                 dist = fmin(dist, esdf(a.map, map_inv, px + cy * bx - sy * by, py + sy * bx + cy * by, false, 0.0, gx, gy));
             }
         }

@@ -243,17 +243,24 @@ __global__ void predicted_state_kernel(PredictArgs g)
     const int n = (int)floor((check - start_time) / step);
     const double left = check - n * step - start_time;
     double p1[2], v1[2], p2[2], v2[2], p3[2], v3[2], a3[2], j3[2];
+    bool standard = g.standard_diff;
+    double xv = g.xv;
+    if (g.classes) { // the slot's robot model (alore_backend_set_classes)
+        const Config& k = g.classes[g.class_of[b]];
+        standard = k.standard_diff != 0;
+        xv = k.icr_xv;
+    }
     plan_eval(T, coef, M, start_time, p3, v3, nullptr, nullptr);
     for (int i = 0; i < n; ++i) {
         p1[0] = p3[0]; p1[1] = p3[1]; v1[0] = v3[0]; v1[1] = v3[1];
         plan_eval(T, coef, M, start_time + i * step + step / 2.0, p2, v2, nullptr, nullptr);
         plan_eval(T, coef, M, start_time + i * step + step, p3, v3, nullptr, nullptr);
-        simpson_add(g.standard_diff, g.xv, step / 6.0, p1, v1, p2, v2, p3, v3, xyt);
+        simpson_add(standard, xv, step / 6.0, p1, v1, p2, v2, p3, v3, xyt);
     }
     p1[0] = p3[0]; p1[1] = p3[1]; v1[0] = v3[0]; v1[1] = v3[1];
     plan_eval(T, coef, M, check - left / 2.0, p2, v2, nullptr, nullptr);
     plan_eval(T, coef, M, check, p3, v3, a3, j3);
-    simpson_add(g.standard_diff, g.xv, left / 6.0, p1, v1, p2, v2, p3, v3, xyt);
+    simpson_add(standard, xv, left / 6.0, p1, v1, p2, v2, p3, v3, xyt);
     for (int k = 0; k < 3; ++k) g.xyt_out[(size_t)b * 3 + k] = xyt[k];
     g.oaj_out[(size_t)b * 3] = v3[0]; g.oaj_out[(size_t)b * 3 + 1] = a3[0]; g.oaj_out[(size_t)b * 3 + 2] = j3[0];
     g.vaj_out[(size_t)b * 3] = v3[1]; g.vaj_out[(size_t)b * 3 + 1] = a3[1]; g.vaj_out[(size_t)b * 3 + 2] = j3[1];
@@ -280,6 +287,13 @@ __global__ void path_points_kernel(PathArgs g)
     const double* coef = g.coef + (size_t)b * g.P * 12;
     double px = g.plan_start_xyt[(size_t)b * 3], py = g.plan_start_xyt[(size_t)b * 3 + 1], sumT = 0.0;
     int n = 0;
+    bool standard = g.standard_diff;
+    double xv = g.xv;
+    if (g.classes) { // the slot's robot model (alore_backend_set_classes)
+        const Config& k = g.classes[g.class_of[b]];
+        standard = k.standard_diff != 0;
+        xv = k.icr_xv;
+    }
     for (int i = 0; i < M; ++i) {
         const double step = T[i] / res, halfstep = step / 2.0, C = T[i] / res / 6.0;
         double s1 = 0.0, ax = 0.0, ay = 0.0; // the panel being filled
@@ -289,8 +303,8 @@ __global__ void path_points_kernel(PathArgs g)
             s1 += halfstep;
             sincos(p[0], &sy, &cy);
             if ((j & 1) == 0) {
-                if (g.standard_diff) { fx = C * v[1] * cy; fy = C * v[1] * sy; }
-                else { fx = C * (v[1] * cy + v[0] * g.xv * sy); fy = C * (v[1] * sy - v[0] * g.xv * cy); }
+                if (standard) { fx = C * v[1] * cy; fy = C * v[1] * sy; }
+                else { fx = C * (v[1] * cy + v[0] * xv * sy); fy = C * (v[1] * sy - v[0] * xv * cy); }
                 if (j != 0) { // end term of panel j / 2 - 1: the panel is complete
                     ax += fx; ay += fy;
                     px += ax; py += ay;
@@ -300,8 +314,8 @@ __global__ void path_points_kernel(PathArgs g)
                 }
                 ax = fx; ay = fy; // start term of panel j / 2 (0 + fx in the reference)
             } else {
-                if (g.standard_diff) { fx = 4.0 * C * v[1] * cy; fy = 4.0 * C * v[1] * sy; }
-                else { fx = 4 * C * (v[1] * cy + v[0] * g.xv * sy); fy = 4 * C * (v[1] * sy - v[0] * g.xv * cy); }
+                if (standard) { fx = 4.0 * C * v[1] * cy; fy = 4.0 * C * v[1] * sy; }
+                else { fx = 4 * C * (v[1] * cy + v[0] * xv * sy); fy = 4 * C * (v[1] * sy - v[0] * xv * cy); }
                 ax += fx; ay += fy;
             }
         }

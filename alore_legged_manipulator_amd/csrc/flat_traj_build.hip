@@ -55,7 +55,8 @@ __global__ __launch_bounds__(64) void build_problems_kernel(const BuildArgs* __r
         if (lane == 0) a.status[b] = ft::E_POINTS;
         return;
     }
-    const ft::Params fe = a.fe;
+    // the front-end parameters of the slot's class (alore_backend_set_classes with fe), or the call's
+    const ft::Params fe = a.fe_classes ? a.fe_classes[__builtin_amdgcn_readfirstlane(a.class_of[b])] : a.fe;
     const double* xy = a.xy + (size_t)b * K * 2;
     const double start_yaw = a.start_yaw[b], end_yaw = a.end_yaw[b];
     const double v0 = a.start_vaj ? a.start_vaj[(size_t)b * 3] : 0.0;

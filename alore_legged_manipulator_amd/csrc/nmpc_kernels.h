@@ -144,10 +144,11 @@ struct BackendView {
     const int* ok;
 };
 // mask: null, or DEVICE memory: slot t is written when the int at (char*)mask + t * mask_stride is not 0 (and the plan has ok != 0);
-// status: null, or the per-slot status slab (traj_handoff.h); overflow may be null when status is given
+// status: null, or the per-slot status slab (traj_handoff.h); overflow may be null when status is given;
+// d_xv: null, or DEVICE memory [count]: slot t gets d_xv[t] for its xv and the scalar is not read
 hipError_t launch_traj_from_backend(const RefStore& s, const BackendView& v, int count, double t0, double res, int res_int, double xv,
                                     int* n_panels, double* inc, int* overflow, hipStream_t st, const int* mask = nullptr, int mask_stride = 0,
-                                    int* status = nullptr);
+                                    int* status = nullptr, const double* d_xv = nullptr);
 // promotion of pending trajectories (traj_handoff.hip): active <- pending where traj_handoff::promote_due holds
 struct PromoteArgs {
     RefStore act, pen;

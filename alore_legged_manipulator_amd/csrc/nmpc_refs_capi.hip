@@ -264,10 +264,12 @@ int alore_nmpc_refs_set_pending_polynomes(alore_nmpc_handle h, int count, const 
     return set_polynomes(h, count, robots, msgs, state_seq_res, integral_res_int, stream, true);
 }
 
-int alore_nmpc_refs_set_from_backend(alore_nmpc_handle h, const void* view, int count, double traj_start_time, double xv,
-                                     double state_seq_res, int integral_res_int, void* stream)
+// xv_slot: 0 the scalar xv for every slot, 1 d_xv[t] for slot t (the _xv entry points)
+static int set_from_backend(alore_nmpc_handle h, const void* view, int count, double traj_start_time, double xv, const double* d_xv, int xv_slot,
+                            double state_seq_res, int integral_res_int, void* stream)
 {
     const alore_backend_device_view* v = static_cast<const alore_backend_device_view*>(view);
+    if (xv_slot && !d_xv) return fail(h, ALORE_NMPC_E_INVALID, "refs_set_from_backend_xv: d_xv is null");
     if (!h || !h->refs.store.dur || !v || count < 1 || count > h->refs.B || !(state_seq_res > 0.0) || integral_res_int < 1)
         return fail(h, ALORE_NMPC_E_INVALID, "refs_set_from_backend: bad argument");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -290,7 +292,7 @@ int alore_nmpc_refs_set_from_backend(alore_nmpc_handle h, const void* view, int 
     HIP_TRY(h, hipMemsetAsync(h->poly.d_overflow, 0, sizeof(int), s));
     const nmpc::BackendView bv{v->max_pieces, v->n_pieces, v->T, v->coef, v->start_xytheta, v->ok};
     HIP_TRY(h, nmpc::launch_traj_from_backend(h->refs.store, bv, count, traj_start_time, state_seq_res, integral_res_int, xv, h->poly.d_panels_be,
-                                              h->poly.d_inc, h->poly.d_overflow, s));
+                                              h->poly.d_inc, h->poly.d_overflow, s, nullptr, 0, nullptr, d_xv));
     int ov = 0;
     HIP_TRY(h, hipMemcpyAsync(&ov, h->poly.d_overflow, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
@@ -299,10 +301,24 @@ int alore_nmpc_refs_set_from_backend(alore_nmpc_handle h, const void* view, int 
     return ALORE_NMPC_OK;
 }
 
-int alore_nmpc_refs_set_pending_from_backend(alore_nmpc_handle h, const void* view, int count, const int* mask, int mask_stride_bytes,
-                                             double traj_start_time, double xv, double state_seq_res, int integral_res_int, void* stream)
+int alore_nmpc_refs_set_from_backend(alore_nmpc_handle h, const void* view, int count, double traj_start_time, double xv,
+                                     double state_seq_res, int integral_res_int, void* stream)
+{
+    return set_from_backend(h, view, count, traj_start_time, xv, nullptr, 0, state_seq_res, integral_res_int, stream);
+}
+
+int alore_nmpc_refs_set_from_backend_xv(alore_nmpc_handle h, const void* view, int count, double traj_start_time, const double* d_xv,
+                                        double state_seq_res, int integral_res_int, void* stream)
+{
+    return set_from_backend(h, view, count, traj_start_time, 0.0, d_xv, 1, state_seq_res, integral_res_int, stream);
+}
+
+static int set_pending_from_backend(alore_nmpc_handle h, const void* view, int count, const int* mask, int mask_stride_bytes,
+                                    double traj_start_time, double xv, const double* d_xv, int xv_slot, double state_seq_res,
+                                    int integral_res_int, void* stream)
 {
     const alore_backend_device_view* v = static_cast<const alore_backend_device_view*>(view);
+    if (xv_slot && !d_xv) return fail(h, ALORE_NMPC_E_INVALID, "refs_set_pending_from_backend_xv: d_xv is null");
     if (!h || !h->refs.store.dur || !v || count < 1 || count > h->refs.B || !(state_seq_res > 0.0) || integral_res_int < 1 ||
         (mask && (mask_stride_bytes < (int)sizeof(int) || mask_stride_bytes % (int)sizeof(int))))
         return fail(h, ALORE_NMPC_E_INVALID, "refs_set_pending_from_backend: bad argument");
@@ -332,9 +348,24 @@ int alore_nmpc_refs_set_pending_from_backend(alore_nmpc_handle h, const void* vi
     HIP_TRY(h, nmpc::launch_traj_promote(pa, s));
     const nmpc::BackendView bv{v->max_pieces, v->n_pieces, v->T, v->coef, v->start_xytheta, v->ok};
     HIP_TRY(h, nmpc::launch_traj_from_backend(h->handoff.pending, bv, count, traj_start_time, state_seq_res, integral_res_int, xv,
-                                              h->poly.d_panels_be, h->poly.d_inc, nullptr, s, mask, stride, h->handoff.d_status));
+                                              h->poly.d_panels_be, h->poly.d_inc, nullptr, s, mask, stride, h->handoff.d_status, d_xv));
     h->handoff.times.add(traj_start_time);
     return ALORE_NMPC_OK;
+}
+
+int alore_nmpc_refs_set_pending_from_backend(alore_nmpc_handle h, const void* view, int count, const int* mask, int mask_stride_bytes,
+                                             double traj_start_time, double xv, double state_seq_res, int integral_res_int, void* stream)
+{
+    return set_pending_from_backend(h, view, count, mask, mask_stride_bytes, traj_start_time, xv, nullptr, 0, state_seq_res, integral_res_int,
+                                    stream);
+}
+
+int alore_nmpc_refs_set_pending_from_backend_xv(alore_nmpc_handle h, const void* view, int count, const int* mask, int mask_stride_bytes,
+                                                double traj_start_time, const double* d_xv, double state_seq_res, int integral_res_int,
+                                                void* stream)
+{
+    return set_pending_from_backend(h, view, count, mask, mask_stride_bytes, traj_start_time, 0.0, d_xv, 1, state_seq_res, integral_res_int,
+                                    stream);
 }
 
 int alore_nmpc_refs_promote(alore_nmpc_handle h, int B, double now, void* stream)

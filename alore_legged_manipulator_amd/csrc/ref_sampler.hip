@@ -201,7 +201,7 @@ hipError_t launch_traj_build(const RefStore& s, const PolyBatch& m, int count, d
 //      mask / status (alore_nmpc_refs_set_pending_from_backend): a slot whose mask word is 0 is left alone, and what happened to a
 //      slot that the mask addresses is written to its status word instead of the one overflow flag; both null: the kernel of alore_nmpc_refs_set_from_backend.
 __global__ void traj_from_backend_kernel(RefStore s, BackendView v, int count, double t0, double res, int res_int, double xv,
-                                         int* n_panels, int* overflow, const int* mask, int mask_stride, int* status)
+                                         int* n_panels, int* overflow, const int* mask, int mask_stride, int* status, const double* d_xv)
 {
     const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= (long)count * v.P) return;
@@ -234,19 +234,20 @@ __global__ void traj_from_backend_kernel(RefStore s, BackendView v, int count, d
     const int nck = 1 + seq / res_int;
     if (nck > s.C) { meta[6] = 0.0; if (overflow) atomicOr(overflow, 2); if (status) status[t] = traj_handoff::kTooManyCheckpoints; return; }
     n_panels[t] = seq;
-    meta[0] = t0; meta[1] = total; meta[2] = xv; meta[3] = res;
+    meta[0] = t0; meta[1] = total; meta[2] = d_xv ? d_xv[t] : xv; meta[3] = res;
     meta[4] = (double)M; meta[5] = (double)nck; meta[6] = 1.0; meta[7] = 0.0;
     s.ckpt[(size_t)t * s.C * 2] = v.start_xytheta[(size_t)t * 3];
     s.ckpt[(size_t)t * s.C * 2 + 1] = v.start_xytheta[(size_t)t * 3 + 1];
 }
 
 hipError_t launch_traj_from_backend(const RefStore& s, const BackendView& v, int count, double t0, double res, int res_int, double xv,
-                                    int* n_panels, double* inc, int* overflow, hipStream_t st, const int* mask, int mask_stride, int* status)
+                                    int* n_panels, double* inc, int* overflow, hipStream_t st, const int* mask, int mask_stride, int* status,
+                                    const double* d_xv)
 {
     const int max_panels = s.C * res_int;
     const long threads = (long)count * v.P;
     hipLaunchKernelGGL(traj_from_backend_kernel, dim3((unsigned)((threads + 127) / 128)), dim3(128), 0, st, s, v, count, t0, res, res_int,
-                       xv, n_panels, overflow, mask, mask_stride, status);
+                       xv, n_panels, overflow, mask, mask_stride, status, d_xv);
     PolyBatch m{};
     m.robot = nullptr; // identity: problem t -> store slot t
     const long total = (long)count * max_panels;

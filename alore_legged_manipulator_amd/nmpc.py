@@ -280,10 +280,25 @@ class BatchedNmpc:
         self._refs_shape = (int(max_pieces), int(max_checkpoints))
         self._check(self.lib.alore_nmpc_refs_init(self.h, self.B, max_pieces, max_checkpoints))
 
-    def refs_set_from_backend(self, planner, count: int | None = None, traj_start_time: float = 0.0, xv: float = 0.0,
+    def _xv_slab(self, xv, n):
+        """None for a float; the address of a float64 device tensor with an entry per slot (planner.class_xv())"""
+        if not hasattr(xv, "data_ptr"):
+            return None
+        if not (xv.is_cuda and xv.dtype == self.torch.float64 and xv.dim() == 1 and xv.is_contiguous() and xv.numel() >= n):
+            raise ValueError("xv: a float, or a contiguous float64 device tensor with an entry per slot")
+        return int(xv.data_ptr())
+
+    def refs_set_from_backend(self, planner, count: int | None = None, traj_start_time: float = 0.0, xv=0.0,
                               state_seq_res: float = 0.1, integral_res_int: int = 4) -> None:
-        """Trajectory store <- the plans of a BatchedMSPlanner on the same GPU, device to device (problem t -> slot t)."""
+        """Trajectory store <- the plans of a BatchedMSPlanner on the same GPU, device to device (problem t -> slot t).
+        xv: a float for every slot, or a float64 device tensor with the xv of every slot (planner.class_xv())."""
         view = planner.device_view()
+        slab = self._xv_slab(xv, int(count or planner.count))
+        if slab is not None:
+            self._check(self.lib.alore_nmpc_refs_set_from_backend_xv(self.h, C.addressof(view), int(count or planner.count),
+                                                                     float(traj_start_time), slab, float(state_seq_res),
+                                                                     int(integral_res_int), self._stream()))
+            return
         self._check(self.lib.alore_nmpc_refs_set_from_backend(self.h, C.addressof(view), int(count or planner.count),
                                                               float(traj_start_time), float(xv), float(state_seq_res),
                                                               int(integral_res_int), self._stream()))
@@ -319,14 +334,20 @@ class BatchedNmpc:
         """refs_set_polynomes into the PENDING slots: tracked from msg.traj_start_time on; overflows go to refs_pending_status."""
         self._set_polynomes(self.lib.alore_nmpc_refs_set_pending_polynomes, robots, msgs, state_seq_res, integral_res_int)
 
-    def refs_set_pending_from_backend(self, planner, count: int | None = None, mask=None, traj_start_time: float = 0.0, xv: float = 0.0,
+    def refs_set_pending_from_backend(self, planner, count: int | None = None, mask=None, traj_start_time: float = 0.0, xv=0.0,
                                       state_seq_res: float = 0.1, integral_res_int: int = 4) -> None:
         """Pending slots <- the plans of a BatchedMSPlanner, device to device, nothing waits.  mask: int32 DEVICE tensor (count,) or
-        None = every slot; a slot is written when its mask word is not 0 and its plan has ok != 0."""
+        None = every slot; a slot is written when its mask word is not 0 and its plan has ok != 0.  xv: as refs_set_from_backend."""
         view = planner.device_view()
         n = int(count or planner.count)
         if mask is not None and not (mask.is_cuda and mask.dtype == self.torch.int32 and mask.dim() == 1 and mask.numel() >= n):
             raise ValueError("mask: an int32 device tensor with a word per slot")
+        slab = self._xv_slab(xv, n)
+        if slab is not None:
+            self._check(self.lib.alore_nmpc_refs_set_pending_from_backend_xv(
+                self.h, C.addressof(view), n, None if mask is None else mask.data_ptr(), 0 if mask is None else mask.stride(0) * 4,
+                float(traj_start_time), slab, float(state_seq_res), int(integral_res_int), self._stream()))
+            return
         self._check(self.lib.alore_nmpc_refs_set_pending_from_backend(
             self.h, C.addressof(view), n, None if mask is None else mask.data_ptr(), 0 if mask is None else mask.stride(0) * 4,
             float(traj_start_time), float(xv), float(state_seq_res), int(integral_res_int), self._stream()))

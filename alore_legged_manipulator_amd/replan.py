@@ -40,14 +40,15 @@ class ReplanWork:
 
 
 def replan_cycle(planner, nmpc, now: float, max_replan_time: float, goals_xy, end_yaw, start_times=0.0, work: ReplanWork | None = None,
-                 count: int | None = None, min_safe_dis=None, body: bool = False, xv: float = 0.0, state_seq_res: float = 0.1,
+                 count: int | None = None, min_safe_dis=None, body: bool = False, xv=0.0, state_seq_res: float = 0.1,
                  integral_res_int: int = 4, resolution: float = 0.01, safe_dis=None, params=None, mark=None) -> ReplanWork:
     """Enqueues the seven steps on the stream of `nmpc` (torch's current stream) and returns at once; work.mask is the delivery mask.
 
     goals_xy [count][>= 2], end_yaw [count]: float64 device tensors.  start_times: the start times of the ACTIVE trajectories as the
     caller delivered them (host scalar or array [count]); a robot whose pending entry has been promoted since has that entry's
-    start time.  mark: None, or a callable that is given the name of every step after it has been enqueued (tools/traj_handoff.py
-    records an event there)."""
+    start time.  xv: the ICR offset the store integrates the delivered plans with, a float for every slot or a float64 device
+    tensor with an entry per slot (planner.class_xv() on a handle with object classes).  mark: None, or a callable that is given
+    the name of every step after it has been enqueued (tools/traj_handoff.py records an event there)."""
     mark = mark or (lambda name: None)
     n = int(count or planner.count)
     w = work or ReplanWork(n, goals_xy.device)
@@ -107,7 +108,7 @@ class ManagerWork:
 
 
 def manager_cycle(planner, nmpc, now: float, poses, work: ManagerWork | None = None, count: int | None = None, collision_mask=None,
-                  pose_stride: int = 24, nmpc_plant: bool = True, ltv=None, xv: float = 0.0, state_seq_res: float = 0.1, integral_res_int: int = 4,
+                  pose_stride: int = 24, nmpc_plant: bool = True, ltv=None, xv=0.0, state_seq_res: float = 0.1, integral_res_int: int = 4,
                   resolution: float = 0.01, safe_dis=None, window_margin=None, params=None, mark=None) -> ManagerWork:
     """One period of plan_manager's MainThread for every robot of a BatchedMSPlanner (manager_create first) / BatchedNmpc pair,
     enqueued on the stream of `nmpc` (torch's current stream); returns at once.  Who plans, from where, what is delivered under which
@@ -127,7 +128,8 @@ def manager_cycle(planner, nmpc, now: float, poses, work: ManagerWork | None = N
      11. mission_step             (a handle with missions) with after_plan_mask
 
     poses: float64 device tensor [count][>= 2] or an address with pose_stride bytes between robots (x, y first).  collision_mask: who
-    may replan under replan_on_collision_only (planner.check_mask() after a check_plans of the caller's).  The cold start of a robot
+    may replan under replan_on_collision_only (planner.check_mask() after a check_plans of the caller's).  xv: as for
+    replan_cycle, a float or a float64 device tensor per slot (planner.class_xv()), for both deliveries.  The cold start of a robot
     that had no trajectory stays with the caller (alore_nmpc.h)."""
     mark = mark or (lambda name: None)
     n = int(count or planner.B)

@@ -132,7 +132,8 @@ int alore_backend_device_results(alore_backend_handle h, alore_backend_device_vi
 /* ---- pieces of the optimiser, exposed for parity tests against the CPU oracle ------------------------ */
 /* one cost-callback evaluation per problem: stage 1 = costFunctionCallbackPath (optimizer.cpp:1272-1317),
  * 2 = costFunctionCallback (:631-692).  x, grad: [count][3P-1 stride = 3 * max_pieces]; lam, rho: [count][2] or
- * NULL (config values); cost [count]; xy_err [count][2].  Host pointers; synchronises. */
+ * NULL (config values); cost [count]; xy_err [count][2].  Host pointers; synchronises.  safe_dis, time_weight: the value for
+ * every slot, or NaN for the configured one (config.safe_dis, config.w_time: with a class table the slot's class's). */
 int alore_backend_eval(alore_backend_handle h, int count, int stage, const double *x, const double *lam, const double *rho,
                        double safe_dis, double time_weight, double *cost, double *grad, double *xy_err, void *stream);
 /* lbfgs_optimize on one stage from x (in/out), at most max_iter iterations (0 = the configured limit);
@@ -233,7 +234,9 @@ typedef struct alore_backend_paths {
  * ORDERING.  Between this call and the next plan launch a rebuilt slot holds its new n_pieces and start pose next to the results of
  * its old plan: alore_backend_check_plans, alore_backend_predicted_state[_device], alore_backend_path_points and
  * alore_backend_results on such a slot in that window are the caller's to avoid (alore_backend_set_problems has the same window).
- * In a replan cycle, check and predict first, then set the paths, then plan. */
+ * In a replan cycle, check and predict first, then set the paths, then plan.  With object classes (alore_backend_set_classes) a
+ * handle's stored plans are checked and predicted with the table and the class indices of NOW: changing either between a plan and
+ * its check is the caller's to avoid. */
 int alore_backend_set_paths(alore_backend_handle h, int count, const alore_backend_paths *p, const alore_front_end_params *fe,
                             int device_pointers, const int *mask, int mask_stride_bytes, void *stream);
 /* device slab [max_problems] of the build status of the last alore_backend_set_paths; valid until the handle is destroyed */
@@ -269,6 +272,69 @@ int alore_backend_plan_masked(alore_backend_handle h, int count, const int *mask
  * A robot whose replan failed keeps its colliding trajectory: the reference goes to EMERGENCY_STOP there
  * (plan_manager.hpp:662-666); stopping it stays with the caller, who reads the collision words and this mask. */
 int alore_backend_replan_mask(alore_backend_handle h, int count, int *out_mask, void *stream);
+
+/* ---- object classes: one robot model per problem slot, mixed in one launch ---------------------------------------------- */
+/* A batch of Monte-Carlo poses x object classes plans robots that differ in their model: the ICR offset, the speed and
+ * acceleration limits, the footprint (check_pts), the clearance.  A handle carries a TABLE of whole configs and a CLASS INDEX per
+ * problem slot, and every call that reads robot-model parameters reads them from the slot's class: alore_backend_plan,
+ * _plan_masked, _eval and _lbfgs (an argument of _eval / _lbfgs -- safe_dis, time_weight, lam, rho, max_iter -- overrides the config
+ * for every slot as before; the argument that stands for the configured value -- NULL for lam and rho, 0 for max_iter, NaN for
+ * safe_dis and time_weight -- takes the class's), alore_backend_check_plans (xv,
+ * n_check, check_pts, final_check_num, and final_min_safe_dis when min_safe_dis <= 0; with a table body != 0 is accepted even if
+ * a class has no check points: such a slot checks the reference point alone), alore_backend_predicted_state[_device] and
+ * alore_backend_path_points (icr_xv, standard_diff), and alore_backend_set_paths (the class's front-end parameters, below).
+ * Everything slot b leaves behind equals bit for bit what a handle created with classes[class_of[b]] leaves for the same problem
+ * on the same map, whatever the classes of its batch mates; a table of one class equal to the handle's config equals no table; a
+ * handle without a table enqueues what it enqueued before there were classes.  csrc/backend_classes.h holds the arithmetic.
+ * OUT OF SCOPE, on purpose: alore_backend_search_paths and alore_backend_task_plan keep their per-call safe_dis; the fleet
+ * manager, the mission and the map calls read no robot model. */
+#define ALORE_BE_MAX_CLASSES 256
+/* Uploads the table (HOST pointers; the call synchronises the device).  A class is a complete alore_backend_config: limits, weights,
+ * safe_dis, final_min_safe_dis, n_check / check_pts, icr_xv / standard_diff, ALM and L-BFGS parameters.  Every entry must pass the
+ * checks of alore_backend_create, and the fields that size a device buffer or a launch must equal the handle's: sparse_res (the
+ * L-BFGS history is sized for 256 slots whatever mem_size says, so mem_size may differ).  A class that fails gets
+ * ALORE_BE_E_INVALID with an error text naming the class and the field, and the table of before stays.  fe: the front-end
+ * parameters per class, [n_classes], or NULL: with them alore_backend_set_paths(fe == NULL) builds slot b with its class's (max_vel
+ * and max_acc start the trapezoid, so a heavier class gets a longer init_T); a non-NULL fe argument there applies to every slot as
+ * before.  n_classes: 1 .. ALORE_BE_MAX_CLASSES; 0 removes the table and the handle behaves as without one.  A slot whose index lies
+ * outside the new table becomes class 0.  The first call allocates for ALORE_BE_MAX_CLASSES classes; no later call allocates. */
+int alore_backend_set_classes(alore_backend_handle h, int n_classes, const alore_backend_config *classes,
+                              const alore_front_end_params *fe);
+/* The class of slots 0..count-1: an attribute of the slot (the robot) that survives alore_backend_set_problems, _set_paths and
+ * plans; slots never set are class 0.  device_pointer == 0: class_of is HOST memory; an index outside [0, n_classes) (outside
+ * [0, 1) without a table) is ALORE_BE_E_INVALID and nothing is changed; the call synchronises the stream.  device_pointer != 0:
+ * DEVICE memory read in stream order by a small kernel, nothing waits; the kernel clamps an index into the table (below 0: class 0,
+ * beyond it: the last class) and adds the number it clamped to the counter of the view below. */
+int alore_backend_set_problem_classes(alore_backend_handle h, int count, const int *class_of, int device_pointer, void *stream);
+/* per class, the outcome of the slots 0..count-1 as their status records lie (the last plan launch; slots a masked launch left out
+ * keep the record of their last plan).  Integer sums, minima and maxima only: the result does not depend on the order. */
+typedef struct alore_backend_class_stat {
+    int n;                /* slots of the class */
+    int n_ok;             /* ok != 0 */
+    int n_collision;      /* collision != 0 */
+    int sum_attempts;
+    long long sum_evals;
+    int max_evals;
+    int pad;
+    double min_dist;      /* minimum of min_dist over the slots with ok != 0; DBL_MAX without one */
+    double max_duration;  /* maximum over the same slots of the plan's duration, the sum of its piece times in piece order; 0 without one */
+} alore_backend_class_stat; /* 48 bytes */
+/* device addresses, valid until the handle is destroyed (the first of the four calls of this section allocates them) */
+typedef struct alore_backend_class_view {
+    int n_classes;                            /* 0 without a table */
+    int pad;
+    const int *class_of;                      /* [max_problems] */
+    const double *xv;                         /* [max_problems] the effective ICR offset of every slot: 0 for a standard_diff class,
+                                                 else icr_xv; kept up to date by the two calls above; what the store hand-over reads
+                                                 (alore_nmpc_refs_set_from_backend_xv) */
+    const int *clamped;                       /* one int: indices the device route had to clamp, summed over its calls */
+    const alore_backend_config *classes;      /* [n_classes]; NULL without a table */
+    const alore_backend_class_stat *stats;    /* [max(n_classes, 1)] the records of the last alore_backend_class_stats */
+} alore_backend_class_view;
+int alore_backend_device_classes(alore_backend_handle h, alore_backend_class_view *out);
+/* One kernel on `stream`, one workgroup per class.  out (HOST, [max(n_classes, 1)]) NULL: nothing waits and the records stay in the
+ * slab of the view; otherwise they are copied down and the stream is synchronised.  Without a table: one class, every slot. */
+int alore_backend_class_stats(alore_backend_handle h, int count, alore_backend_class_stat *out, void *stream);
 
 /* ---- the resident occupancy map: point clouds in, ESDF out, on the device ------------------------------------- */
 /* The half of plan_env::SDFmap that runs before updateESDF2d (sdf_map.cpp: updateOccupancyCallback :35-130, raycastProcess

@@ -341,6 +341,10 @@ int alore_nmpc_refs_set_polynomes(alore_nmpc_handle h, int count, const int *rob
  * MSPlanner::minco_plan fails (optimizer.cpp:204-209: nothing is published).  Synchronises the stream; errors as alore_nmpc_refs_set_polynomes. */
 int alore_nmpc_refs_set_from_backend(alore_nmpc_handle h, const void *view, int count, double traj_start_time, double xv,
                                      double state_seq_res, int integral_res_int, void *stream);
+/* The same with an xv per slot: d_xv is DEVICE memory [count], read in stream order, and slot t gets d_xv[t] -- for a planner with
+ * object classes the xv slab of alore_backend_device_classes as it lies.  Everything else is alore_nmpc_refs_set_from_backend. */
+int alore_nmpc_refs_set_from_backend_xv(alore_nmpc_handle h, const void *view, int count, double traj_start_time, const double *d_xv,
+                                        double state_seq_res, int integral_res_int, void *stream);
 /* ---- hand-over to a replanned trajectory at its start time ---------------------------------------------------------
  * The reference plans from the state predicted at current + max_replan_time and stamps the message with that time
  * (plan_manager.hpp:585-588, 686-691); the controller keeps the new trajectory in new_traj_ and goes on tracking traj_
@@ -377,6 +381,10 @@ int alore_nmpc_refs_set_pending_polynomes(alore_nmpc_handle h, int count, const 
 int alore_nmpc_refs_set_pending_from_backend(alore_nmpc_handle h, const void *view, int count, const int *mask, int mask_stride_bytes,
                                              double traj_start_time, double xv, double state_seq_res, int integral_res_int,
                                              void *stream);
+/* the same with an xv per slot, as alore_nmpc_refs_set_from_backend_xv: d_xv DEVICE memory [count] */
+int alore_nmpc_refs_set_pending_from_backend_xv(alore_nmpc_handle h, const void *view, int count, const int *mask, int mask_stride_bytes,
+                                                double traj_start_time, const double *d_xv, double state_seq_res, int integral_res_int,
+                                                void *stream);
 /* active <- pending for every robot b < B with a valid pending entry and now > its start time (strict, as the reference);
  * the pending entry becomes invalid and the robot's promotion counter goes up by one.  Asynchronous. */
 int alore_nmpc_refs_promote(alore_nmpc_handle h, int B, double now, void *stream);
