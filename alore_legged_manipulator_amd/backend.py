@@ -229,6 +229,7 @@ def _bind(L):
                                            C.c_double, C.c_double, C.c_double, DP]
     L.alore_backend_predicted_state.argtypes = [C.c_void_p, C.c_int, C.c_double, DP, DP, DP, DP, DP, DP, C.POINTER(C.c_int)]
     L.alore_backend_path_points.argtypes = [C.c_void_p, C.c_int, C.c_int, DP, DP, C.POINTER(C.c_int)]
+    L.alore_backend_path_points_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.alore_backend_set_problems.argtypes = [C.c_void_p, C.c_int, C.POINTER(FlatTrajC), C.c_void_p]
     L.alore_backend_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.alore_backend_results.argtypes = [C.c_void_p, C.c_int, C.POINTER(StatusC), DP, DP, DP, C.c_void_p]
@@ -844,6 +845,22 @@ class BatchedMSPlanner:
         xy = np.zeros((n, per, 2)); yaw = np.zeros((n, self.P * panels_per_piece)); npts = np.zeros(n, np.int32)
         self._check(self.L.alore_backend_path_points(self.h, n, int(panels_per_piece), _dp(xy), _dp(yaw), npts.ctypes.data_as(C.POINTER(C.c_int))))
         return [(xy[b, :npts[b]].copy(), yaw[b, :(npts[b] // (panels_per_piece + 1)) * panels_per_piece].copy()) for b in range(n)]
+
+    def path_points_device(self, xy, n_points, yaw=None, panels_per_piece: int = 3, count: int | None = None, stream=None):
+        """The same on the caller's device tensors in stream order, nothing waits: xy float64 [count][P (panels_per_piece + 1)][2],
+        n_points int32 [count], yaw float64 [count][P panels_per_piece] or None.  A row is written up to its n_points only.  xy and
+        n_points are what BatchedTaskFsm.set_paths takes"""
+        n = int(count or self.count)
+        per = self.P * (int(panels_per_piece) + 1)
+        if xy.element_size() != 8 or not xy.is_contiguous() or xy.numel() < n * per * 2:
+            raise ValueError(f"xy: a contiguous float64 device tensor of at least [{n}][{per}][2] is needed")
+        if n_points.element_size() != 4 or not n_points.is_contiguous() or n_points.numel() < n:
+            raise ValueError("n_points: a contiguous int32 device tensor [count] is needed")
+        if yaw is not None and (yaw.element_size() != 8 or not yaw.is_contiguous() or yaw.numel() < n * self.P * int(panels_per_piece)):
+            raise ValueError("yaw: a contiguous float64 device tensor [count][P panels_per_piece] is needed")
+        s = None if stream is None else (stream if isinstance(stream, int) else int(stream.cuda_stream))
+        self._check(self.L.alore_backend_path_points_device(self.h, n, int(panels_per_piece), int(xy.data_ptr()),
+                                                            None if yaw is None else int(yaw.data_ptr()), int(n_points.data_ptr()), s))
 
     def check_plans(self, t_from=None, t_to=None, min_safe_dis=None, body=False, count=None, stream=None, fetch=True) -> dict | None:
         """The final collision check of the plans of the last launch against the map as it is NOW (set_map / build_esdf since

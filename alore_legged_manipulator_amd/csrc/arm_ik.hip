@@ -11,15 +11,12 @@
 #include <cstring>
 #include <new>
 
-#include "../../include/alore_arm.h"
-#include "z1_kinematics.h"
+#include "arm_handle.h"
 
 static_assert(sizeof(alore_arm_params) == sizeof(z1::Params), "alore_arm_params mirrors z1::Params");
 static_assert(sizeof(alore_arm_class) == sizeof(z1::Class), "alore_arm_class mirrors z1::Class");
 
 namespace arm {
-
-constexpr int LANES = 64;
 
 template <typename T> __device__ inline const T* row(const T* base, int b, int stride_bytes)
 {
@@ -29,12 +26,6 @@ template <typename T> __device__ inline T* row(T* base, int b, int stride_bytes)
 {
     return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + (size_t)b * (size_t)stride_bytes);
 }
-
-// the grasp state of the handle, structure of arrays
-struct GraspSlab {
-    double *joint_cmd, *robot_vel_cmd, *k, *d_gripper, *gripper_ang, *err_norm; // [.][7], [.][3], [.] ...
-    int *done, *grasp_time, *flag, *stable, *ik_iterations, *ik_status;
-};
 
 __global__ __launch_bounds__(LANES) void ik_kernel(z1::Params P, int count, const double* q_init, int q_stride, const double* target, int target_stride,
                                                    double* q_out, double* err_norm, int* iterations, int* status)
@@ -145,20 +136,7 @@ __global__ __launch_bounds__(LANES) void fk_kernel(z1::Params P, int count, cons
 
 } // namespace arm
 
-// ---- the C ABI ------------------------------------------------------------------------------------------------------------------------
-struct alore_arm {
-    int device, max_problems, n_classes;
-    z1::Params P;
-    z1::Class* d_classes; // [ALORE_ARM_MAX_CLASSES]
-    int* d_class_of;      // [max]
-    double *d_q, *d_err;  // [max][7], [max]
-    int *d_iterations, *d_status;
-    arm::GraspSlab g;
-    double* d_stage; // [max][STAGE_ROW] doubles: host inputs and outputs of a call with device_pointers == 0
-    int* d_stage_int; // [max]
-    char err[256];
-};
-
+// ---- the C ABI (struct alore_arm: arm_handle.h) ----------------------------------------------------------------------------------------
 namespace {
 constexpr int STAGE_ROW = 56; // the widest call: fk, 7 in + 12 + 36 out
 char g_err[256] = "";
@@ -294,6 +272,7 @@ int alore_arm_create(const alore_arm_params* params, int device, int max_problem
 int alore_arm_destroy(alore_arm_handle h)
 {
     if (!h) return ALORE_ARM_OK;
+    if (h->fsm_free) h->fsm_free(h); // the task FSM of alore_fsm_create, if it is still attached
     (void)hipFree(h->d_q);          // the block of doubles
     (void)hipFree(h->d_iterations); // the block of ints
     (void)hipFree(h->d_classes);

@@ -519,6 +519,19 @@ int alore_backend_path_points(alore_backend_handle h, int count, int panels_per_
     return ALORE_BE_OK;
 }
 
+int alore_backend_path_points_device(alore_backend_handle h, int count, int panels_per_piece, double* d_xy, double* d_yaw, int* d_n_points, void* stream)
+{
+    if (!h || count < 1 || count > h->B || panels_per_piece < 1 || !d_xy || !d_n_points)
+        return fail(h, ALORE_BE_E_INVALID, "path_points_device: bad argument");
+    if (!h->timed || count > h->count) return fail(h, ALORE_BE_E_INVALID, "path_points_device: no plan for these slots (alore_backend_plan first)");
+    BE_TRY(h, hipSetDevice(h->device));
+    backend::PathArgs g{count, h->P, panels_per_piece, h->d_M, h->r_ok, h->r_T, h->r_coef, h->d_sxyt, h->cfg.icr_xv, h->cfg.standard_diff != 0,
+                        d_xy, d_yaw, d_n_points};
+    if (h->n_classes) { g.classes = h->k_table; g.class_of = h->k_class_of; }
+    BE_TRY(h, backend::path_points(g, (hipStream_t)stream));
+    return ALORE_BE_OK;
+}
+
 int alore_backend_set_problems(alore_backend_handle h, int count, const alore_flat_traj* pr, void* stream)
 {
     if (!h || count < 1 || count > h->B || !pr) return fail(h, ALORE_BE_E_INVALID, "set_problems: bad argument");

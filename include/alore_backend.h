@@ -161,6 +161,12 @@ int alore_backend_predicted_state(alore_backend_handle h, int count, double reso
  * does not publish it), n_points [count] (n_pieces (panels_per_piece + 1); 0 for a slot whose plan the optimiser rejected).
  * Synchronises. */
 int alore_backend_path_points(alore_backend_handle h, int count, int panels_per_piece, double *xy, double *yaw, int *n_points);
+/* The same kernel on the caller's DEVICE slabs of the same shapes, in stream order: nothing is allocated, nothing is copied and
+ * nothing waits.  A row is written up to its n_points only (alore_backend_path_points zeroes its slabs first: on zeroed slabs the
+ * two leave the same bits).  d_xy with row stride max_pieces (panels_per_piece + 1) 16 bytes and d_n_points are what
+ * alore_fsm_set_paths (alore_fsm.h) reads; max_pieces is the handle's rounded value (alore_backend_status). */
+int alore_backend_path_points_device(alore_backend_handle h, int count, int panels_per_piece, double *d_xy, double *d_yaw_or_null,
+                                     int *d_n_points, void *stream);
 
 /* ---- stored plans against the map of now ------------------------------------------------------------- */
 /* MSPlanner::check_final_collision (optimizer.cpp:474-571) again, on the plans of the last alore_backend_plan and the handle's
