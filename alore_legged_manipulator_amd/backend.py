@@ -144,6 +144,11 @@ class TaskViewC(C.Structure):
                 ("fields", C.c_void_p), ("sweeps", C.c_void_p)]
 
 
+class TaskAssignViewC(C.Structure):
+    """alore_backend_task_assign_view: device addresses of the assignment that TASK_ASSIGNED / TASK_JOINT chose"""
+    _fields_ = [("assignment", C.c_void_p), ("assign_total", C.c_void_p)]
+
+
 class MapEditC(C.Structure):
     """alore_backend_map_edit: a rectangle of the reference's paint* loops and the state it writes"""
     _fields_ = [("cx", C.c_double), ("cy", C.c_double), ("hx", C.c_double), ("hy", C.c_double), ("make_obs", C.c_int), ("reserved", C.c_int)]
@@ -190,7 +195,8 @@ PHASE_NONE, PHASE_ITEM, PHASE_TARGET = 0, 1, 2
 ITEM_SQUARE, ITEM_BOX, ITEM_TABLE, ITEM_CHAIR = 0, 1, 2, 3
 MAX_PATH_POINTS = 31
 TASK_MAX_TASKS, TASK_MAX_POINTS, TASK_MAX_LEGS = 10, 21, 20
-TASK_GREEDY, TASK_OPTIMAL = 0, 1
+TASK_GREEDY, TASK_OPTIMAL, TASK_ASSIGNED, TASK_JOINT = 0, 1, 2, 3
+TASK_JOINT_MAX_TASKS = 5
 TASK_OK, TASK_MASKED, TASK_E_ENDPOINT, TASK_E_WINDOW, TASK_E_TASKS, TASK_E_NO_ORDER = 0, 1, -1, -3, -6, -7
 SEARCH_OK, SEARCH_MASKED, SEARCH_E_ENDPOINT, SEARCH_E_SAME_CELL, SEARCH_E_WINDOW, SEARCH_E_NO_PATH, SEARCH_E_POINTS = 0, 1, -1, -2, -3, -4, -5
 SEARCH_MAX_CELLS = 32768
@@ -282,6 +288,9 @@ def _bind(L):
                                           C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     L.alore_backend_device_task.argtypes = [C.c_void_p, C.POINTER(TaskViewC)]
     L.alore_backend_get_task.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_int)] * 5 + [DP, DP] + [C.POINTER(C.c_int)] * 2
+    L.alore_backend_task_reorder.argtypes = [C.c_void_p, C.c_void_p]
+    L.alore_backend_device_task_assign.argtypes = [C.c_void_p, C.POINTER(TaskAssignViewC)]
+    L.alore_backend_get_task_assign.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_int)] * 2
     L.alore_backend_map_paint.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     L.alore_backend_device_paint_counters.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.alore_backend_map_paint_counters.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
@@ -1107,7 +1116,9 @@ class BatchedMSPlanner:
     def task_plan(self, n_tasks, points, assignment=None, mode=None, safe_dis=None, window_margin=None, mask=None, check=True):
         """plan_manager's task planning for a batch of missions (NumPy in): n_tasks [count]; points [count][1 + 2 max_tasks][2], per
         mission the robot, its n items, its n targets, packed at the beginning of the row; assignment [count][max_tasks] (optimal
-        mode; None: the identity); mode TASK_GREEDY (None) or TASK_OPTIMAL; safe_dis / window_margin None: 0.3 / 3.0; mask: per
+        mode; None: the identity); mode TASK_GREEDY (None), TASK_OPTIMAL, TASK_ASSIGNED (the assignment of least carrying distance,
+        then the optimal order for it) or TASK_JOINT (assignment and order together, n <= 5), the last two with their choice in
+        task_assignment(); safe_dis / window_margin None: 0.3 / 3.0; mask: per
         mission, 0 leaves it out.  Waits.  Raises when a mission fails unless check is False; task_result() has the outcome."""
         pts = np.ascontiguousarray(np.asarray(points, np.float64))
         nt = np.ascontiguousarray(np.asarray(n_tasks, np.int32).reshape(-1))
@@ -1168,6 +1179,26 @@ class BatchedMSPlanner:
         if res is not None:
             a, b = out["matrix"][..., 0].astype(np.float64), out["matrix"][..., 1].astype(np.float64)
             out["cost_m"] = np.where(out["matrix"][..., 0] < 0, np.inf, (a + b * np.sqrt(2.0)) * res)
+        return out
+
+    def task_reorder(self, stream=None):
+        """diagnostic: the order phase of the last task_plan / task_plan_device launch again, alone, on the matrices in the slab"""
+        self._check(self.L.alore_backend_task_reorder(self.h, _stream(stream)))
+
+    def device_task_assign(self) -> TaskAssignViewC:
+        """the device rows of the assignment that the last TASK_ASSIGNED / TASK_JOINT launch chose (alore_backend_task_assign_view)"""
+        v = TaskAssignViewC()
+        self._check(self.L.alore_backend_device_task_assign(self.h, C.byref(v)))
+        return v
+
+    def task_assignment(self, count: int | None = None) -> dict:
+        """those rows copied to the host (waits): assignment [count][10], the target of item i for i < n, and assign_total
+        [count][2], the pair (a, b) of the sum of its carry legs.  Written by missions that are OK in the mode TASK_ASSIGNED or
+        TASK_JOINT (TASK_ASSIGNED: also where the chosen assignment has no finite order); untouched otherwise"""
+        n = int(count or getattr(self, "task_count", 0))
+        out = {"assignment": np.zeros((n, TASK_MAX_TASKS), np.int32), "assign_total": np.zeros((n, 2), np.int32)}
+        ip = C.POINTER(C.c_int)
+        self._check(self.L.alore_backend_get_task_assign(self.h, n, out["assignment"].ctypes.data_as(ip), out["assign_total"].ctypes.data_as(ip)))
         return out
 
     def predicted_state_device(self, count, times, xytheta, vaj, oaj, forward, resolution: float = 0.01, start_times=None, start_xytheta=None,

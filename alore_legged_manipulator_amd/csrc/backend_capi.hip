@@ -80,10 +80,11 @@ struct alore_backend_planner {
     // the slab of the missions
     char *h_task = nullptr, *d_task_in = nullptr;
     int *t_status = nullptr, *t_matrix = nullptr, *t_order = nullptr, *t_n_order = nullptr, *t_total = nullptr, *t_fields = nullptr,
-        *t_sweeps = nullptr, *t_src_fields = nullptr, *t_src_sweeps = nullptr;
+        *t_sweeps = nullptr, *t_src_fields = nullptr, *t_src_sweeps = nullptr, *t_assignment = nullptr, *t_assign_total = nullptr;
     double *t_leg_start = nullptr, *t_leg_goal = nullptr;
     hipEvent_t ev_task = nullptr; // the upload of the previous call has left h_task
     bool task_pending = false;
+    int task_last_count = 0, task_last_mode = 0; // of the launch whose argument block lies in d_task_in
     // alore_backend_laser_*: the sensor (alore_backend_laser_create), its world cloud and the slabs of the scans; the argument
     // block is followed by the staged poses of the host route, pinned and on the device
     bool has_laser = false, has_cloud = false;
@@ -215,7 +216,7 @@ void free_all(alore_backend_handle h)
                     h->d_cost, h->d_err, h->d_ret, h->d_params, h->d_order, h->d_check_in, h->d_check, h->d_build_in, h->d_build_status,
                     h->d_search_in, h->d_path_n, h->d_path_cost, h->d_search_status, h->d_search_sweeps, h->d_path_xy,
                     h->d_task_in, h->t_status, h->t_matrix, h->t_order, h->t_n_order, h->t_total, h->t_fields, h->t_sweeps, h->t_src_fields,
-                    h->t_src_sweeps, h->t_leg_start, h->t_leg_goal, h->p_desc, h->p_counters, h->p_host_edits, h->m_slab_mem, h->m_stage, h->m_edits,
+                    h->t_src_sweeps, h->t_assignment, h->t_assign_total, h->t_leg_start, h->t_leg_goal, h->p_desc, h->p_counters, h->p_host_edits, h->m_slab_mem, h->m_stage, h->m_edits,
                     h->g_mem, h->g_stage, h->k_table, h->k_fe, h->k_class_of, h->k_clamped, h->k_stage, h->k_xv, h->k_stats, h->k_params};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -382,6 +383,7 @@ int alore_backend_create(const alore_backend_config* cfg, int device, int max_pi
     A(dalloc(&h->t_n_order, B)); A(dalloc(&h->t_total, B * 2)); A(dalloc(&h->t_fields, B)); A(dalloc(&h->t_sweeps, B));
     A(dalloc(&h->t_src_fields, B * tplan::MAX_LEGS)); A(dalloc(&h->t_src_sweeps, B * tplan::MAX_LEGS));
     A(dalloc(&h->t_leg_start, B * tplan::MAX_LEGS * 2)); A(dalloc(&h->t_leg_goal, B * tplan::MAX_LEGS * 2));
+    A(dalloc(&h->t_assignment, B * tplan::MAX_TASKS)); A(dalloc(&h->t_assign_total, B * 2));
     A(dalloc(&h->d_task_in, task_in_bytes(B, tplan::MAX_TASKS)));
     if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_task, task_in_bytes(B, tplan::MAX_TASKS), hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_task, hipEventDisableTiming);
@@ -1561,7 +1563,8 @@ int alore_backend_task_plan(alore_backend_handle h, int count, int max_tasks, co
     if (params) prm = *params; else alore_backend_task_default_params(&prm);
     if (!std::isfinite(prm.safe_dis) || !std::isfinite(prm.window_margin) || prm.window_margin < 0.0)
         return fail(h, ALORE_BE_E_INVALID, "task_plan: safe_dis must be finite, window_margin finite and not negative");
-    if (prm.mode != tplan::GREEDY && prm.mode != tplan::OPTIMAL) return fail(h, ALORE_BE_E_INVALID, "task_plan: unknown mode");
+    if (prm.mode < tplan::GREEDY || prm.mode > tplan::JOINT) return fail(h, ALORE_BE_E_INVALID, "task_plan: unknown mode");
+    if (prm.mode != tplan::OPTIMAL) assignment_or_null = nullptr; // read in the optimal mode only
     if (!h->d_map) return fail(h, ALORE_BE_E_INVALID, "task_plan: no map (alore_backend_set_map / alore_backend_build_esdf / alore_backend_map_create)");
     BE_TRY(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
@@ -1570,7 +1573,7 @@ int alore_backend_task_plan(alore_backend_handle h, int count, int max_tasks, co
     const size_t n = count, T = max_tasks;
     backend::TaskArgs g{};
     g.count = count;
-    g.max_tasks = max_tasks;
+    g.max_tasks = tplan::task_limit(prm.mode, max_tasks); // the rows of the caller keep their stride; an assignment is not read then
     g.mode = prm.mode;
     g.map = h->map;
     g.safe_dis = prm.safe_dis;
@@ -1604,22 +1607,33 @@ int alore_backend_task_plan(alore_backend_handle h, int count, int max_tasks, co
     g.status = h->t_status; g.matrix = h->t_matrix; g.order = h->t_order; g.n_order = h->t_n_order; g.total = h->t_total;
     g.leg_start_xy = h->t_leg_start; g.leg_goal_xy = h->t_leg_goal; g.fields = h->t_fields; g.sweeps = h->t_sweeps;
     g.src_fields = h->t_src_fields; g.src_sweeps = h->t_src_sweeps;
+    g.assignment = h->t_assignment; g.assign_total = h->t_assign_total;
     std::memcpy(h->h_task, &g, sizeof(g));
     BE_TRY(h, hipMemcpyAsync(h->d_task_in, h->h_task, up, hipMemcpyHostToDevice, s));
     BE_TRY(h, hipEventRecord(h->ev_task, s));
     h->task_pending = true;
-    BE_TRY(h, backend::task_plan((const backend::TaskArgs*)h->d_task_in, count, max_tasks, prm.mode, g.lds_cells, s));
+    BE_TRY(h, backend::task_plan((const backend::TaskArgs*)h->d_task_in, count, g.max_tasks, prm.mode, g.lds_cells, s));
+    h->task_last_count = count;
+    h->task_last_mode = prm.mode;
     if (!device_pointers) {
         int* hst = (int*)h->h_stage;
         BE_TRY(h, hipMemcpyAsync(hst, h->t_status, sizeof(int) * n, hipMemcpyDeviceToHost, s));
         BE_TRY(h, hipStreamSynchronize(s));
         for (size_t b = 0; b < n; ++b) {
-            if (hst[b] == tplan::E_TASKS) return fail(h, ALORE_BE_E_INVALID, "task_plan: mission failed: a task count is outside 1..max_tasks, or an assignment is no permutation");
+            if (hst[b] == tplan::E_TASKS) return fail(h, ALORE_BE_E_INVALID, "task_plan: mission failed: a task count is outside 1..max_tasks (joint mode: 1..5), or an assignment is no permutation");
             if (hst[b] == tplan::E_ENDPOINT) return fail(h, ALORE_BE_E_INVALID, "task_plan: mission failed: a point is not finite or outside the map");
             if (hst[b] == tplan::E_NO_ORDER) return fail(h, ALORE_BE_E_INVALID, "task_plan: mission failed: no order has a finite cost");
             if (hst[b] == tplan::E_WINDOW) return fail(h, ALORE_BE_E_UNSUPPORTED, "task_plan: mission failed: the window has more than 32768 cells");
         }
     }
+    return ALORE_BE_OK;
+}
+
+int alore_backend_task_reorder(alore_backend_handle h, void* stream)
+{
+    if (!h || h->task_last_count < 1) return fail(h, ALORE_BE_E_INVALID, "task_reorder: no alore_backend_task_plan launch on this handle");
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, backend::task_order((const backend::TaskArgs*)h->d_task_in, h->task_last_count, h->task_last_mode, (hipStream_t)stream));
     return ALORE_BE_OK;
 }
 
@@ -1647,6 +1661,27 @@ int alore_backend_get_task(alore_backend_handle h, int count, int* status, int* 
     if (leg_goal_xy) BE_TRY(h, hipMemcpy(leg_goal_xy, h->t_leg_goal, sizeof(double) * n * L * 2, hipMemcpyDeviceToHost));
     if (fields) BE_TRY(h, hipMemcpy(fields, h->t_fields, sizeof(int) * n, hipMemcpyDeviceToHost));
     if (sweeps) BE_TRY(h, hipMemcpy(sweeps, h->t_sweeps, sizeof(int) * n, hipMemcpyDeviceToHost));
+    return ALORE_BE_OK;
+}
+
+static_assert(ALORE_BE_TASK_ASSIGNED == tplan::ASSIGNED && ALORE_BE_TASK_JOINT == tplan::JOINT &&
+              ALORE_BE_TASK_JOINT_MAX_TASKS == tplan::JOINT_MAX_TASKS && ALORE_BE_TASK_MAX_TASKS == tplan::MAX_TASKS, "task_plan.h");
+
+int alore_backend_device_task_assign(alore_backend_handle h, alore_backend_task_assign_view* out)
+{
+    if (!h || !out) return fail(h, ALORE_BE_E_INVALID, "device_task_assign: bad argument");
+    *out = alore_backend_task_assign_view{h->t_assignment, h->t_assign_total};
+    return ALORE_BE_OK;
+}
+
+int alore_backend_get_task_assign(alore_backend_handle h, int count, int* assignment, int* assign_total)
+{
+    if (!h || count < 1 || count > h->B) return fail(h, ALORE_BE_E_INVALID, "get_task_assign: bad argument");
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, hipDeviceSynchronize());
+    const size_t n = count;
+    if (assignment) BE_TRY(h, hipMemcpy(assignment, h->t_assignment, sizeof(int) * n * tplan::MAX_TASKS, hipMemcpyDeviceToHost));
+    if (assign_total) BE_TRY(h, hipMemcpy(assign_total, h->t_assign_total, sizeof(int) * n * 2, hipMemcpyDeviceToHost));
     return ALORE_BE_OK;
 }
 

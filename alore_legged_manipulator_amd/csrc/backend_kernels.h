@@ -175,9 +175,14 @@ struct TaskArgs {
     double *leg_start_xy, *leg_goal_xy; // [count][20][2]
     int *fields, *sweeps;          // [count]
     int *src_fields, *src_sweeps;  // [count][20] per source point: what task_order_kernel adds up (no atomics)
+    int* assignment;               // [count][10], modes ASSIGNED and JOINT: the target of item i
+    int* assign_total;             // [count][2], the sum of its carry legs
 };
-// both kernels read their arguments from d_args (device memory, filled in stream order before the launch)
+// task_assign_order_kernel (mode ASSIGNED) and task_joint_kernel (mode JOINT) stand in for task_order_kernel in a launch of their mode.
+// The kernels read their arguments from d_args (device memory, filled in stream order before the launch)
 hipError_t task_plan(const TaskArgs* d_args, int count, int max_tasks, int mode, int lds_cells, hipStream_t s);
+// the order phase alone, on the matrices that lie in the slab: the second launch of task_plan
+hipError_t task_order(const TaskArgs* d_args, int count, int mode, hipStream_t s);
 // registers the LDS sizes with the runtime (once per device, not in stream order: call before the first task_plan)
 hipError_t task_configure();
 

@@ -5,7 +5,9 @@
 // solvePathWithGreedy (:347-432, the live call) or BranchAndBoundCombined::solve with a fixed assignment (:252-345,
 // branch_and_bound.hpp).  Stated so that the matrix and both orders have exactly one answer each.  The small functions are what the
 // kernels of task_plan.hip run; plan_one() strings them together serially and is what tests/harness/task_plan_check.cpp and
-// tools/task_plan.py (one host core) run.  The oracle is tests/task_plan_cases.py; harness and device equal it bit for bit.
+// tools/task_plan.py (one host core) run; plan_one_assigned() does the same for the modes that choose the assignment
+// (tests/harness/task_assign_check.cpp).  The oracles are tests/task_plan_cases.py and tests/task_assign_cases.py; harness and device
+// equal them bit for bit.
 //
 // THE CONTRACT
 //   mission  n tasks, 1 <= n <= max_tasks <= MAX_TASKS = 10, and P = 1 + 2 n points (x, y): index 0 the robot, 1..n the items,
@@ -13,7 +15,8 @@
 //            a row of 1 + 2 max_tasks points, (char*)points + m * row stride, its n at n_tasks[m], its assignment (optimal mode, may
 //            be absent) at assign[m * max_tasks + i].
 //   status   OK 0, MASKED 1, E_ENDPOINT -1 and E_WINDOW -3 as in path_search.h; E_TASKS -6: n outside 1..max_tasks, or (optimal
-//            mode) a given assignment that is no permutation of 0..n-1; E_NO_ORDER -7 (optimal mode): no order has a finite cost.
+//            mode) a given assignment that is no permutation of 0..n-1, or (joint mode) n > 5; E_NO_ORDER -7 (every mode but
+//            greedy): no order has a finite cost.
 //            A point of the mission that is not finite or outside [lo, hi] is E_ENDPOINT.  The checks come in the order tasks,
 //            end point, window.  A mission that fails a check writes its status and n_order = 0 and nothing else; a masked-out
 //            mission writes status 1 and nothing else.  E_NO_ORDER is found after the matrix: status, n_order = 0, the matrix and
@@ -44,9 +47,34 @@
 //            leg_start_xy, leg_goal_xy [2 MAX_TASKS][2], the end points of the legs in visit order, rows beyond n_order untouched;
 //            fields, the number of cost fields computed for the mission (per source k < P - 1 the number of distinct safe_kj over
 //            j > k), and sweeps, the most any of them needed.
+//   ASSIGNED the item-to-target assignment, then the OPTIMAL routing for it.  The assignment is the bijection sigma of items to
+//            targets of least carrying distance, sum_i d(1 + i, n + 1 + sigma(i)), by the sums and the order above; among optimal
+//            bijections the one whose vector (sigma(0), sigma(1), ...) is lexicographically smallest.  It is what the reference's
+//            hungarian.hpp (included by plan_manager.hpp, never called) would feed the fixed_assignment of
+//            solvePathWithBranchAndBound (:273-306) with, up to ties; the tie rule is ours.  Dynamic programming over target
+//            subsets: rest[T], the least cost of giving the items popcount(T) .. n-1 the targets outside T; going forward, item k
+//            takes the lowest target that still attains rest.  No bijection with a finite sum: E_NO_ORDER, the matrix and the
+//            diagnostics written as in the optimal mode.  THE ASSIGNMENT IS DECIDED ON THE CARRY LEGS ALONE: the legs from the
+//            robot and between a target and the next item play no part in it, so the routing of sigma (exactly OPTIMAL with
+//            assign = sigma) can be without a finite order where another bijection has one; that mission is E_NO_ORDER too, with
+//            its assignment rows written.  A given assignment is not read in this mode, neither for values nor for validity.
+//   JOINT    the assignment and the order together: minimise sum_k d(prev_k, item pi_k) + d(item pi_k, target sigma(pi_k)), prev_1
+//            the robot, prev_k+1 the target just served, over all item orders pi and all bijections sigma -- the problem the
+//            greedy mode is a heuristic for.  Dynamic programming over (served items Si, used targets St, last target), |Si| =
+//            |St|: togo[Si][St][last], indexed (Si * 32 + St) * 5 + last.  n <= JOINT_MAX_TASKS = 5 (5120 states, 40 KiB); a
+//            mission with more tasks in this mode is E_TASKS, whatever max_tasks the launch has (task_limit).  Among optimal routes the one
+//            whose published order (item, target, item, target, ...) is lexicographically smallest: going forward, the lowest
+//            item, then the lowest target, that still attains the optimum.  No finite route: E_NO_ORDER.  A given assignment is
+//            not read.
+//   outputs of ASSIGNED and JOINT: all of the above exactly as OPTIMAL writes them (total: the cost of the route), and
+//            assignment[MAX_TASKS], the target of item i for i < n, entries beyond n untouched, with assign_total[2], the sum of
+//            its carry legs.  Both rows are written by a mission with status OK, and in the ASSIGNED mode by a mission whose
+//            assignment is finite and whose routing is not (E_NO_ORDER); by no other mission, and never in the other two modes.
 // DEVIATIONS FROM THE REFERENCE
 //   the window: the reference searches the whole map;  an end point outside the map is refused, the reference clamps it;  the tie
-//   rule of the optimal mode;  a leg searched later by psearch uses that pair's own, smaller window, so its cost can exceed d(i, j).
+//   rules of the optimal, assigned and joint modes;  the assigned and joint modes themselves: the reference has the pieces
+//   (hungarian.hpp, fixed_assignment) and calls neither;  a leg searched later by psearch uses that pair's own, smaller window, so
+//   its cost can exceed d(i, j).
 #ifndef ALORE_TASK_PLAN_H
 #define ALORE_TASK_PLAN_H
 
@@ -60,8 +88,12 @@ namespace tplan {
 
 constexpr int MAX_TASKS = 10, P_MAX = 1 + 2 * MAX_TASKS, MAX_LEGS = 2 * MAX_TASKS;
 constexpr int OK = 0, MASKED = 1, E_ENDPOINT = -1, E_WINDOW = -3, E_TASKS = -6, E_NO_ORDER = -7;
-constexpr int GREEDY = 0, OPTIMAL = 1;
+constexpr int GREEDY = 0, OPTIMAL = 1, ASSIGNED = 2, JOINT = 3;
 constexpr int STATES = (1 << MAX_TASKS) * MAX_TASKS; // togo[S * MAX_TASKS + last]: 80 KiB
+constexpr int REST_STATES = 1 << MAX_TASKS;          // rest[T]: 8 KiB
+constexpr int ASSIGNED_STATES = STATES + REST_STATES; // the assigned mode: togo, then rest
+constexpr int JOINT_MAX_TASKS = 5, JOINT_SETS = 1 << JOINT_MAX_TASKS;
+constexpr int JOINT_STATES = JOINT_SETS * JOINT_SETS * JOINT_MAX_TASKS; // togo[(Si * 32 + St) * 5 + last]: 40 KiB
 
 struct Params {
     double safe_dis, window_margin;
@@ -95,6 +127,9 @@ struct Mission {
     int x0, y0, wx, wy; // the window: origin in the map and size in cells
 };
 
+// the most tasks a mission may have in a launch for rows of max_tasks: what the joint mode hands check_mission as max_tasks, so
+// that n > JOINT_MAX_TASKS is E_TASKS there by the check of n that every mode has
+PS_HD int task_limit(int mode, int max_tasks) { return (mode == JOINT && max_tasks > JOINT_MAX_TASKS) ? JOINT_MAX_TASKS : max_tasks; }
 // the checks of a mission, in the order tasks, end point, window; pts: the mission's row of points
 PS_HD Mission check_mission(const psearch::Grid& g, int n, int max_tasks, const double* pts, const int* assign, int mode, double window_margin)
 {
@@ -259,6 +294,111 @@ PS_HD int optimal_order(const int* mat, int n, const int* assign, const Cost* to
     *n_order = 2 * n;
     return OK;
 }
+// ---- the assigned mode: the matching by dynamic programming over target subsets ------------------------------------------------
+// rest[T] from the sets with one more target: item popcount(T) takes a target outside T
+PS_HD Cost rest_state(const int* mat, int n, const Cost* rest, unsigned T)
+{
+    const int k = popcount(T);
+    if (k == n) return Cost{0, 0};
+    Cost best = inf_cost();
+    for (int t = 0; t < n; ++t) {
+        if ((T >> t) & 1u) continue;
+        const Cost c = add(entry(mat, 1 + k, n + 1 + t), rest[T | (1u << t)]);
+        if (less(c, best)) best = c;
+    }
+    return best;
+}
+// forward through the filled table: the lexicographically smallest optimal bijection.  E_NO_ORDER writes nothing
+PS_HD int matching(const int* mat, int n, const Cost* rest, int* assign, int* assign_total)
+{
+    Cost want = rest[0];
+    if (is_inf(want)) return E_NO_ORDER;
+    assign_total[0] = want.a;
+    assign_total[1] = want.b;
+    unsigned T = 0;
+    for (int k = 0; k < n; ++k) {
+        int pick = -1;
+        for (int t = 0; t < n && pick < 0; ++t)
+            if (!((T >> t) & 1u) && same(add(entry(mat, 1 + k, n + 1 + t), rest[T | (1u << t)]), want)) pick = t;
+        if (pick < 0) return E_NO_ORDER; // never: the optimum of a state is attained by one of its steps
+        assign[k] = pick;
+        T |= 1u << pick;
+        want = rest[T];
+    }
+    return OK;
+}
+
+// ---- the joint mode: togo[(Si * JOINT_SETS + St) * JOINT_MAX_TASKS + last], Si the served items, St the used targets --------------
+PS_HD unsigned joint_index(unsigned Si, unsigned St, int last) { return (Si * JOINT_SETS + St) * JOINT_MAX_TASKS + (unsigned)last; }
+// the indices below joint_span(n) hold every state of a mission of n tasks
+PS_HD unsigned joint_span(int n) { return joint_index((1u << n) - 1u, (1u << n) - 1u, JOINT_MAX_TASKS - 1) + 1u; }
+// index e is a state of the level: as many items served as targets used, `level` of them, the last target among the used
+PS_HD bool joint_on_level(int n, unsigned e, int level)
+{
+    const unsigned sets = e / JOINT_MAX_TASKS, last = e - sets * JOINT_MAX_TASKS, Si = sets / JOINT_SETS, St = sets - Si * JOINT_SETS;
+    return (int)last < n && St < (1u << n) && popcount(Si) == level && popcount(St) == level && ((St >> last) & 1u);
+}
+// serve item i next and carry it to target t, standing at point `from`: the two legs and what is left
+PS_HD Cost joint_step(const int* mat, int n, const Cost* togo, int from, unsigned Si, unsigned St, int i, int t)
+{
+    const Cost legs = add(entry(mat, from, 1 + i), entry(mat, 1 + i, n + 1 + t));
+    return add(legs, togo[joint_index(Si | (1u << i), St | (1u << t), t)]);
+}
+// the least over the free items and targets
+PS_HD Cost joint_best(const int* mat, int n, const Cost* togo, int from, unsigned Si, unsigned St)
+{
+    Cost best = inf_cost();
+    for (int i = 0; i < n; ++i) {
+        if ((Si >> i) & 1u) continue;
+        for (int t = 0; t < n; ++t) {
+            if ((St >> t) & 1u) continue;
+            const Cost c = joint_step(mat, n, togo, from, Si, St, i, t);
+            if (less(c, best)) best = c;
+        }
+    }
+    return best;
+}
+// the state at index e (joint_on_level) from the states with one more task done
+PS_HD Cost joint_state(const int* mat, int n, const Cost* togo, unsigned e)
+{
+    const unsigned sets = e / JOINT_MAX_TASKS, last = e - sets * JOINT_MAX_TASKS, Si = sets / JOINT_SETS, St = sets - Si * JOINT_SETS;
+    if (Si == (1u << n) - 1u) return Cost{0, 0};
+    return joint_best(mat, n, togo, n + 1 + (int)last, Si, St);
+}
+// forward through the filled table: the lexicographically smallest optimal published order, its assignment and the sum of its
+// carry legs.  E_NO_ORDER writes nothing but *n_order
+PS_HD int joint_order(const int* mat, int n, const Cost* togo, int* order, int* n_order, int* total, int* assign, int* assign_total)
+{
+    *n_order = 0;
+    Cost want = joint_best(mat, n, togo, 0, 0u, 0u);
+    if (is_inf(want)) return E_NO_ORDER;
+    total[0] = want.a;
+    total[1] = want.b;
+    unsigned Si = 0, St = 0;
+    int from = 0;
+    Cost carry{0, 0};
+    for (int step = 0; step < n; ++step) {
+        int pi = -1, pt = -1;
+        for (int i = 0; i < n && pi < 0; ++i) {
+            if ((Si >> i) & 1u) continue;
+            for (int t = 0; t < n && pi < 0; ++t)
+                if (!((St >> t) & 1u) && same(joint_step(mat, n, togo, from, Si, St, i, t), want)) { pi = i; pt = t; }
+        }
+        if (pi < 0) return E_NO_ORDER; // never: the optimum of a state is attained by one of its steps
+        order[2 * step] = pi;
+        order[2 * step + 1] = pt;
+        assign[pi] = pt;
+        carry = add(carry, entry(mat, 1 + pi, n + 1 + pt));
+        Si |= 1u << pi;
+        St |= 1u << pt;
+        from = n + 1 + pt;
+        want = togo[joint_index(Si, St, pt)];
+    }
+    *n_order = 2 * n;
+    assign_total[0] = carry.a;
+    assign_total[1] = carry.b;
+    return OK;
+}
 // the end points of the legs in visit order
 PS_HD void write_legs(const double* pts, int n, const int* order, int n_order, double* leg_start_xy, double* leg_goal_xy)
 {
@@ -281,11 +421,9 @@ struct Out {
     double* leg_goal_xy;
     int *fields, *sweeps;
 };
-inline int plan_one(const psearch::Grid& g, int n, int max_tasks, const double* pts, const int* assign, const Params& p, unsigned* words,
-                    Cost* togo, const Out& o)
+// the matrix and the diagnostics of a checked mission
+inline void fill_matrix(const psearch::Grid& g, const Mission& m, const double* pts, const Params& p, unsigned* words, const Out& o)
 {
-    const Mission m = check_mission(g, n, max_tasks, pts, assign, p.mode, p.window_margin);
-    if (m.status != OK) { *o.n_order = 0; return m.status; }
     int cell[P_MAX];
     double dist[P_MAX], safe[P_MAX];
     for (int j = 0; j < m.P; ++j) cell[j] = point_cell(g, m, pts, j, &dist[j]);
@@ -324,17 +462,57 @@ inline int plan_one(const psearch::Grid& g, int n, int max_tasks, const double* 
     }
     *o.fields = fields;
     *o.sweeps = most;
+}
+// togo[] of the optimal routing for `assign`, level by level, then the order
+inline int route_one(const int* mat, int n, const int* assign, Cost* togo, const Out& o)
+{
+    for (int level = n; level >= 1; --level)
+        for (unsigned S = 1; S < (1u << n); ++S) {
+            if (popcount(S) != level) continue;
+            for (int last = 0; last < n; ++last)
+                if ((S >> last) & 1u) togo[S * MAX_TASKS + last] = togo_state(mat, n, assign, togo, S, last);
+        }
+    return optimal_order(mat, n, assign, togo, o.order, o.n_order, o.total);
+}
+inline int plan_one(const psearch::Grid& g, int n, int max_tasks, const double* pts, const int* assign, const Params& p, unsigned* words,
+                    Cost* togo, const Out& o)
+{
+    const Mission m = check_mission(g, n, max_tasks, pts, assign, p.mode, p.window_margin);
+    if (m.status != OK) { *o.n_order = 0; return m.status; }
+    fill_matrix(g, m, pts, p, words, o);
     int status = OK;
-    if (p.mode == OPTIMAL) {
+    if (p.mode == OPTIMAL) status = route_one(o.matrix, n, assign, togo, o);
+    else greedy_order(o.matrix, n, o.order, o.n_order, o.total);
+    if (status == OK) write_legs(pts, n, o.order, *o.n_order, o.leg_start_xy, o.leg_goal_xy);
+    return status;
+}
+// the modes that choose the assignment (p.mode ASSIGNED or JOINT).  table[]: ASSIGNED_STATES pairs, togo then rest (ASSIGNED), or
+// JOINT_STATES pairs (JOINT).  assignment[MAX_TASKS] and assign_total[2] are written as the contract says
+inline int plan_one_assigned(const psearch::Grid& g, int n, int max_tasks, const double* pts, const Params& p, unsigned* words, Cost* table,
+                             const Out& o, int* assignment, int* assign_total)
+{
+    const Mission m = check_mission(g, n, task_limit(p.mode, max_tasks), pts, nullptr, p.mode, p.window_margin);
+    if (m.status != OK) { *o.n_order = 0; return m.status; }
+    fill_matrix(g, m, pts, p, words, o);
+    int status;
+    if (p.mode == JOINT) {
         for (int level = n; level >= 1; --level)
-            for (unsigned S = 1; S < (1u << n); ++S) {
-                if (popcount(S) != level) continue;
-                for (int last = 0; last < n; ++last)
-                    if ((S >> last) & 1u) togo[S * MAX_TASKS + last] = togo_state(o.matrix, n, assign, togo, S, last);
-            }
-        status = optimal_order(o.matrix, n, assign, togo, o.order, o.n_order, o.total);
+            for (unsigned e = 0; e < joint_span(n); ++e)
+                if (joint_on_level(n, e, level)) table[e] = joint_state(o.matrix, n, table, e);
+        int asg[JOINT_MAX_TASKS], sum[2];
+        status = joint_order(o.matrix, n, table, o.order, o.n_order, o.total, asg, sum);
+        if (status == OK) {
+            for (int i = 0; i < n; ++i) assignment[i] = asg[i];
+            assign_total[0] = sum[0]; assign_total[1] = sum[1];
+        }
     } else {
-        greedy_order(o.matrix, n, o.order, o.n_order, o.total);
+        Cost* rest = table + STATES;
+        for (int level = n; level >= 0; --level)
+            for (unsigned T = 0; T < (1u << n); ++T)
+                if (popcount(T) == level) rest[T] = rest_state(o.matrix, n, rest, T);
+        *o.n_order = 0;
+        status = matching(o.matrix, n, rest, assignment, assign_total);
+        if (status == OK) status = route_one(o.matrix, n, assignment, table, o);
     }
     if (status == OK) write_legs(pts, n, o.order, *o.n_order, o.leg_start_xy, o.leg_goal_xy);
     return status;

@@ -18,6 +18,13 @@
 // The optimal mode fills togo[S][last] (80 KiB of LDS, requested in that mode alone: a greedy launch takes 3.5 KiB) level by level in the size of the served set, from n down to 1, a barrier
 // per level: the states of a level read the level above only.  Thread 0 then runs the reconstruction, or the greedy mode, and
 // writes order, total and legs; it also adds up the diagnostics.
+//
+// task_assign_order_kernel (mode ASSIGNED) and task_joint_kernel (mode JOINT) take task_order_kernel's place in a launch of their
+// mode: the same workgroup per mission, the same matrix in LDS, the same publishing by thread 0.  The first fills rest[T] (8 KiB)
+// level by level in the number of targets given away, from n down to 0; thread 0 reconstructs the assignment into LDS, and the
+// workgroup goes on with the optimal mode's togo (80 KiB) for it: 91.6 KiB in all.  The second fills togo[Si][St][last] (40 KiB,
+// directly indexed, no ranking) level by level in the number of tasks done; 43.6 KiB.  A launch in the greedy or optimal mode
+// enqueues what it always did.
 #include "backend_kernels.h"
 #include "task_plan.h"
 
@@ -34,6 +41,12 @@ constexpr int MATRIX_INTS = tp::P_MAX * tp::P_MAX * 2;
 constexpr int ORDER_AT = (MATRIX_INTS * (int)sizeof(int) + 15) & ~15;
 constexpr int TOGO_AT = ORDER_AT + ((tp::MAX_LEGS * (int)sizeof(int) + 15) & ~15);
 constexpr int GREEDY_LDS_BYTES = TOGO_AT, OPTIMAL_LDS_BYTES = TOGO_AT + TOGO_BYTES;
+// LDS of the kernels that choose the assignment: matrix and order as above, 64 bytes for the chosen assignment, its total and the
+// matching's status, then the tables: togo and rest (88 KiB) in the assigned mode, the joint togo (40 KiB) in the joint mode
+constexpr int CHOSEN_AT = TOGO_AT, TABLE_AT = CHOSEN_AT + 64;
+constexpr int ASSIGNED_LDS_BYTES = TABLE_AT + tp::ASSIGNED_STATES * (int)sizeof(tp::Cost);
+constexpr int JOINT_LDS_BYTES = TABLE_AT + tp::JOINT_STATES * (int)sizeof(tp::Cost);
+static_assert((tp::MAX_TASKS + 3) * (int)sizeof(int) <= 64 && ASSIGNED_LDS_BYTES <= 160 * 1024, "task_plan.hip: LDS of the assigned mode");
 
 extern __shared__ __align__(16) unsigned char task_lds[];
 
@@ -142,40 +155,41 @@ __global__ __launch_bounds__(COST_THREADS) void task_costs_kernel(const TaskArgs
     }
 }
 
-__global__ __launch_bounds__(ORDER_THREADS) void task_order_kernel(const TaskArgs* __restrict__ gp)
+// ---- what the three order kernels share --------------------------------------------------------------------------------------
+// the mission of an order kernel's workgroup; false where task_costs_kernel wrote the status and there is nothing to order
+__device__ inline bool order_mission(const TaskArgs& a, int m, MissionIn* in, tp::Mission* ms)
 {
-    const TaskArgs& a = *gp;
-    const int m = blockIdx.x, tid = threadIdx.x;
-    const MissionIn in = mission_in(a, m);
-    if (in.masked) return; // task_costs_kernel wrote the status
+    *in = mission_in(a, m);
+    if (in->masked) return false;
     const ps::Grid g = ps::make_grid(a.map.dist, a.map.nx, a.map.ny, a.map.x_lo, a.map.y_lo, a.map.x_hi, a.map.y_hi, a.map.res);
-    const tp::Mission ms = tp::check_mission(g, in.n, a.max_tasks, in.pts, in.assign, a.mode, a.window_margin);
-    if (ms.status != tp::OK || ms.wx * ms.wy > a.lds_cells) return; // likewise
-    const int n = in.n, P = ms.P;
-    int* mat = (int*)task_lds;
-    tp::Cost* togo = a.mode == tp::OPTIMAL ? (tp::Cost*)(task_lds + TOGO_AT) : nullptr; // a greedy launch has no LDS for the states
+    *ms = tp::check_mission(g, in->n, a.max_tasks, in->pts, in->assign, a.mode, a.window_margin);
+    return ms->status == tp::OK && ms->wx * ms->wy <= a.lds_cells;
+}
+// the matrix of the mission to LDS; the barrier behind it is the caller's
+__device__ inline void load_matrix(const TaskArgs& a, int m, int P, int* mat, int tid)
+{
     const int* gm = a.matrix + (size_t)m * MATRIX_INTS;
     for (int e = tid; e < P * P; e += ORDER_THREADS) {
         const int i = e / P, j = e - i * P, at = (i * tp::P_MAX + j) * 2;
         mat[at] = gm[at];
         mat[at + 1] = gm[at + 1];
     }
-    __syncthreads();
-    if (a.mode == tp::OPTIMAL) {
-        for (int level = n; level >= 1; --level) {
-            for (unsigned S = tid; S < (1u << n); S += ORDER_THREADS) {
-                if (__popc(S) != level) continue;
-                for (int last = 0; last < n; ++last)
-                    if ((S >> last) & 1u) togo[S * tp::MAX_TASKS + last] = tp::togo_state(mat, n, in.assign, togo, S, last);
-            }
-            __syncthreads();
+}
+// togo[S][last] of the routing for `assign`, level by level; ends behind a barrier
+__device__ inline void fill_togo(const int* mat, int n, const int* assign, tp::Cost* togo, int tid)
+{
+    for (int level = n; level >= 1; --level) {
+        for (unsigned S = tid; S < (1u << n); S += ORDER_THREADS) {
+            if (__popc(S) != level) continue;
+            for (int last = 0; last < n; ++last)
+                if ((S >> last) & 1u) togo[S * tp::MAX_TASKS + last] = tp::togo_state(mat, n, assign, togo, S, last);
         }
+        __syncthreads();
     }
-    if (tid != 0) return;
-    int* order = (int*)(task_lds + ORDER_AT);
-    int n_order = 0, total[2] = {0, 0}, status = tp::OK;
-    if (a.mode == tp::OPTIMAL) status = tp::optimal_order(mat, n, in.assign, togo, order, &n_order, total);
-    else tp::greedy_order(mat, n, order, &n_order, total);
+}
+// thread 0 publishes its mission: the diagnostics added up, status and n_order, and with status OK the total, the order and the legs
+__device__ inline void publish(const TaskArgs& a, int m, const double* pts, int n, int P, int status, const int* order, int n_order, const int* total)
+{
     int fields = 0, most = 0;
     for (int k = 0; k < P - 1; ++k) {
         fields += a.src_fields[(size_t)m * tp::MAX_LEGS + k];
@@ -189,7 +203,99 @@ __global__ __launch_bounds__(ORDER_THREADS) void task_order_kernel(const TaskArg
     a.total[2 * (size_t)m] = total[0];
     a.total[2 * (size_t)m + 1] = total[1];
     for (int e = 0; e < n_order; ++e) a.order[(size_t)m * tp::MAX_LEGS + e] = order[e];
-    tp::write_legs(in.pts, n, order, n_order, a.leg_start_xy + (size_t)m * tp::MAX_LEGS * 2, a.leg_goal_xy + (size_t)m * tp::MAX_LEGS * 2);
+    tp::write_legs(pts, n, order, n_order, a.leg_start_xy + (size_t)m * tp::MAX_LEGS * 2, a.leg_goal_xy + (size_t)m * tp::MAX_LEGS * 2);
+}
+// the two rows of the modes that choose the assignment
+__device__ inline void publish_assignment(const TaskArgs& a, int m, int n, const int* assign, const int* assign_total)
+{
+    for (int i = 0; i < n; ++i) a.assignment[(size_t)m * tp::MAX_TASKS + i] = assign[i];
+    a.assign_total[2 * (size_t)m] = assign_total[0];
+    a.assign_total[2 * (size_t)m + 1] = assign_total[1];
+}
+
+__global__ __launch_bounds__(ORDER_THREADS) void task_order_kernel(const TaskArgs* __restrict__ gp)
+{
+    const TaskArgs& a = *gp;
+    const int m = blockIdx.x, tid = threadIdx.x;
+    MissionIn in;
+    tp::Mission ms;
+    if (!order_mission(a, m, &in, &ms)) return;
+    const int n = in.n, P = ms.P;
+    int* mat = (int*)task_lds;
+    tp::Cost* togo = a.mode == tp::OPTIMAL ? (tp::Cost*)(task_lds + TOGO_AT) : nullptr; // a greedy launch has no LDS for the states
+    load_matrix(a, m, P, mat, tid);
+    __syncthreads();
+    if (a.mode == tp::OPTIMAL) fill_togo(mat, n, in.assign, togo, tid);
+    if (tid != 0) return;
+    int* order = (int*)(task_lds + ORDER_AT);
+    int n_order = 0, total[2] = {0, 0}, status = tp::OK;
+    if (a.mode == tp::OPTIMAL) status = tp::optimal_order(mat, n, in.assign, togo, order, &n_order, total);
+    else tp::greedy_order(mat, n, order, &n_order, total);
+    publish(a, m, in.pts, n, P, status, order, n_order, total);
+}
+
+// the assigned mode: rest[T] level by level, the matching by thread 0, then the optimal mode's states and order for it
+__global__ __launch_bounds__(ORDER_THREADS) void task_assign_order_kernel(const TaskArgs* __restrict__ gp)
+{
+    const TaskArgs& a = *gp;
+    const int m = blockIdx.x, tid = threadIdx.x;
+    MissionIn in;
+    tp::Mission ms;
+    if (!order_mission(a, m, &in, &ms)) return; // the same in every thread
+    const int n = in.n, P = ms.P;
+    int* mat = (int*)task_lds;
+    int* chosen = (int*)(task_lds + CHOSEN_AT); // the assignment, its total at [MAX_TASKS], the matching's status behind it
+    tp::Cost* togo = (tp::Cost*)(task_lds + TABLE_AT);
+    tp::Cost* rest = togo + tp::STATES;
+    load_matrix(a, m, P, mat, tid);
+    __syncthreads();
+    for (int level = n; level >= 0; --level) {
+        for (unsigned T = tid; T < (1u << n); T += ORDER_THREADS)
+            if (__popc(T) == level) rest[T] = tp::rest_state(mat, n, rest, T);
+        __syncthreads();
+    }
+    if (tid == 0) chosen[tp::MAX_TASKS + 2] = tp::matching(mat, n, rest, chosen, chosen + tp::MAX_TASKS);
+    __syncthreads();
+    const int matched = chosen[tp::MAX_TASKS + 2];
+    int* order = (int*)(task_lds + ORDER_AT);
+    int n_order = 0, total[2] = {0, 0};
+    if (matched != tp::OK) { // uniform
+        if (tid == 0) publish(a, m, in.pts, n, P, matched, order, n_order, total);
+        return;
+    }
+    fill_togo(mat, n, chosen, togo, tid);
+    if (tid != 0) return;
+    const int status = tp::optimal_order(mat, n, chosen, togo, order, &n_order, total);
+    publish_assignment(a, m, n, chosen, chosen + tp::MAX_TASKS);
+    publish(a, m, in.pts, n, P, status, order, n_order, total);
+}
+
+// the joint mode: togo[Si][St][last] level by level in the number of tasks done, the reconstruction by thread 0
+__global__ __launch_bounds__(ORDER_THREADS) void task_joint_kernel(const TaskArgs* __restrict__ gp)
+{
+    const TaskArgs& a = *gp;
+    const int m = blockIdx.x, tid = threadIdx.x;
+    MissionIn in;
+    tp::Mission ms;
+    if (!order_mission(a, m, &in, &ms)) return; // n <= JOINT_MAX_TASKS behind this: max_tasks of the block is tp::task_limit, more is E_TASKS
+    const int n = in.n, P = ms.P;
+    int* mat = (int*)task_lds;
+    int* chosen = (int*)(task_lds + CHOSEN_AT);
+    tp::Cost* togo = (tp::Cost*)(task_lds + TABLE_AT);
+    load_matrix(a, m, P, mat, tid);
+    __syncthreads();
+    const unsigned span = tp::joint_span(n);
+    for (int level = n; level >= 1; --level) {
+        for (unsigned e = tid; e < span; e += ORDER_THREADS)
+            if (tp::joint_on_level(n, e, level)) togo[e] = tp::joint_state(mat, n, togo, e);
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    int* order = (int*)(task_lds + ORDER_AT);
+    int n_order = 0, total[2] = {0, 0};
+    const int status = tp::joint_order(mat, n, togo, order, &n_order, total, chosen, chosen + tp::MAX_TASKS);
+    if (status == tp::OK) publish_assignment(a, m, n, chosen, chosen + tp::MAX_TASKS);
+    publish(a, m, in.pts, n, P, status, order, n_order, total);
 }
 
 static size_t cost_lds_bytes(int lds_cells) { return TABLE_BYTES + sizeof(unsigned) * (size_t)lds_cells; }
@@ -198,7 +304,11 @@ hipError_t task_configure()
 {
     hipError_t e = hipFuncSetAttribute((const void*)task_costs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cost_lds_bytes(ps::MAX_CELLS));
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute((const void*)task_order_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, OPTIMAL_LDS_BYTES);
+    e = hipFuncSetAttribute((const void*)task_order_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, OPTIMAL_LDS_BYTES);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute((const void*)task_assign_order_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ASSIGNED_LDS_BYTES);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute((const void*)task_joint_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, JOINT_LDS_BYTES);
 }
 
 hipError_t task_plan(const TaskArgs* d_args, int count, int max_tasks, int mode, int lds_cells, hipStream_t s)
@@ -206,8 +316,17 @@ hipError_t task_plan(const TaskArgs* d_args, int count, int max_tasks, int mode,
     void* args[] = {&d_args};
     hipError_t e = hipLaunchKernel((const void*)task_costs_kernel, dim3(count * 2 * max_tasks), dim3(COST_THREADS), args, cost_lds_bytes(lds_cells), s);
     if (e != hipSuccess) return e;
-    e = hipLaunchKernel((const void*)task_order_kernel, dim3(count), dim3(ORDER_THREADS), args,
-                        mode == tp::OPTIMAL ? OPTIMAL_LDS_BYTES : GREEDY_LDS_BYTES, s);
+    return task_order(d_args, count, mode, s);
+}
+
+hipError_t task_order(const TaskArgs* d_args, int count, int mode, hipStream_t s)
+{
+    void* args[] = {&d_args};
+    hipError_t e;
+    if (mode == tp::ASSIGNED) e = hipLaunchKernel((const void*)task_assign_order_kernel, dim3(count), dim3(ORDER_THREADS), args, ASSIGNED_LDS_BYTES, s);
+    else if (mode == tp::JOINT) e = hipLaunchKernel((const void*)task_joint_kernel, dim3(count), dim3(ORDER_THREADS), args, JOINT_LDS_BYTES, s);
+    else e = hipLaunchKernel((const void*)task_order_kernel, dim3(count), dim3(ORDER_THREADS), args,
+                             mode == tp::OPTIMAL ? OPTIMAL_LDS_BYTES : GREEDY_LDS_BYTES, s);
     if (e != hipSuccess) return e;
     return hipGetLastError();
 }

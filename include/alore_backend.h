@@ -559,31 +559,45 @@ int alore_backend_search_sweeps(alore_backend_handle h, int count, int *out);
  * lexicographically smallest item sequence (the reference's best-first search returns an optimum); a leg searched afterwards by
  * alore_backend_search_paths uses that pair's own smaller window, so its cost_ab can exceed the matrix entry.  Two kernels
  * (csrc/task_plan.hip): one workgroup per (mission, source point) fills the matrices, one cost-to-source field serving every
- * other point of the mission; one workgroup per mission then finds the order. */
+ * other point of the mission; one workgroup per mission then finds the order.
+ * Two further modes choose the item-to-target assignment on the device, which the optimal mode takes from the caller (the
+ * reference ships hungarian.hpp for it and a fixed_assignment argument, plan_manager.hpp:273-306, and calls neither).
+ * ALORE_BE_TASK_ASSIGNED: the bijection of items to targets with the least sum of carry legs d(item i, target sigma(i)), among
+ * those the lexicographically smallest vector (sigma(0), sigma(1), ...), then exactly the optimal mode's routing for it.  The
+ * assignment is decided on the carry legs ALONE: if its routing has no finite order the mission is ALORE_BE_TASK_E_NO_ORDER, even
+ * where another bijection could be routed.  ALORE_BE_TASK_JOINT: assignment and order together, the least cost of the whole route
+ * over all item orders and all bijections, for at most ALORE_BE_TASK_JOINT_MAX_TASKS tasks per mission (max_tasks of the launch
+ * may still be 10); among optimal routes the lexicographically smallest published order (item, target, item, target, ...).
+ * Neither mode reads assignment_or_null.  Both write everything the optimal mode writes, in the same way, and the two rows of
+ * alore_backend_task_assign_view. */
 #define ALORE_BE_TASK_MAX_TASKS 10
 #define ALORE_BE_TASK_MAX_POINTS 21 /* 1 + 2 * ALORE_BE_TASK_MAX_TASKS */
 #define ALORE_BE_TASK_MAX_LEGS 20
 #define ALORE_BE_TASK_GREEDY 0
 #define ALORE_BE_TASK_OPTIMAL 1
+#define ALORE_BE_TASK_ASSIGNED 2        /* least carrying distance, then the optimal order for that assignment */
+#define ALORE_BE_TASK_JOINT 3           /* assignment and order together; n <= ALORE_BE_TASK_JOINT_MAX_TASKS */
+#define ALORE_BE_TASK_JOINT_MAX_TASKS 5
 /* task status of a mission */
 #define ALORE_BE_TASK_OK 0
 #define ALORE_BE_TASK_MASKED 1          /* the mask left the mission out: only its status was written */
 #define ALORE_BE_TASK_E_ENDPOINT (-1)   /* a point of the mission is not finite or outside [lo, hi] of the map */
 #define ALORE_BE_TASK_E_WINDOW (-3)     /* the mission's window has more than ALORE_BE_SEARCH_MAX_CELLS cells */
-#define ALORE_BE_TASK_E_TASKS (-6)      /* n outside 1..max_tasks, or (optimal mode) an assignment that is no permutation */
-#define ALORE_BE_TASK_E_NO_ORDER (-7)   /* optimal mode: no order has a finite cost (the matrix is written) */
+#define ALORE_BE_TASK_E_TASKS (-6)      /* n outside 1..max_tasks, (optimal mode) an assignment that is no permutation, (joint mode) n > 5 */
+#define ALORE_BE_TASK_E_NO_ORDER (-7)   /* optimal and joint mode: no order has a finite cost; assigned mode: no assignment has a finite
+                                           sum of carry legs, or the one chosen has no finite order (the matrix is written) */
 typedef struct alore_backend_task_params {
     double safe_dis;      /* jps_safe_dis */
     double window_margin; /* metres round the bounding box of the mission's points */
-    int mode;             /* ALORE_BE_TASK_GREEDY or ALORE_BE_TASK_OPTIMAL */
+    int mode;             /* ALORE_BE_TASK_GREEDY, _OPTIMAL, _ASSIGNED or _JOINT */
 } alore_backend_task_params;
 /* 0.3, 3.0 and ALORE_BE_TASK_GREEDY */
 void alore_backend_task_default_params(alore_backend_task_params *p);
 /* Plans missions 0..count-1 (count <= max_problems) on the handle's current map.  Mission m has n_tasks[m] tasks, 1..max_tasks
  * (max_tasks <= ALORE_BE_TASK_MAX_TASKS); its points are packed at the beginning of a row of 1 + 2 max_tasks (x, y) pairs at
  * (char *)points + m * point_row_stride_bytes (a multiple of 8, at least 16 (1 + 2 max_tasks)).  assignment_or_null:
- * [count][max_tasks] ints, item i of mission m goes to target assignment[m * max_tasks + i]; read in the optimal mode only; NULL:
- * the identity.  params NULL: the defaults.  The mask is read as alore_backend_search_paths reads its mask.
+ * [count][max_tasks] ints, item i of mission m goes to target assignment[m * max_tasks + i]; read in the optimal mode only (the
+ * assigned and joint modes choose their own and read it neither for values nor for validity); NULL: the identity.  params NULL: the defaults.  The mask is read as alore_backend_search_paths reads its mask.
  * A failed mission has a negative status and n_order = 0, nothing else of it is written (ALORE_BE_TASK_E_NO_ORDER: its matrix and
  * diagnostics are).  device_pointers != 0: n_tasks, points, assignment and mask are DEVICE memory read in stream order; nothing
  * crosses the bus but the argument block and nothing waits.  device_pointers == 0: they are HOST memory; they are uploaded, the
@@ -595,6 +609,10 @@ void alore_backend_task_default_params(alore_backend_task_params *p);
 int alore_backend_task_plan(alore_backend_handle h, int count, int max_tasks, const int *n_tasks, const double *points,
                             int point_row_stride_bytes, const int *assignment_or_null, const alore_backend_task_params *params,
                             int device_pointers, const int *mask, int mask_stride_bytes, void *stream);
+/* Diagnostic: launches the order phase of the last alore_backend_task_plan call of this handle again, alone, on the matrices that
+ * lie in the slab, with that call's arguments (for device_pointers != 0 its inputs must still be as they were); it writes what that
+ * call wrote.  Nothing waits.  What tools/task_assign.py times the order kernels with. */
+int alore_backend_task_reorder(alore_backend_handle h, void *stream);
 /* The handle's device slab of the missions [max_problems].  Leg l of every mission goes into alore_backend_search_paths
  * (device_pointers = 1) as it lies: start_xy = leg_start_xy + 2 l, goal_xy = leg_goal_xy + 2 l, both strides
  * ALORE_BE_TASK_MAX_LEGS * 16 bytes.  Rows of order and of the legs beyond n_order are left untouched. */
@@ -613,6 +631,17 @@ int alore_backend_device_task(alore_backend_handle h, alore_backend_task_view *o
 /* The slab copied to HOST arrays with the shapes above and [count] rows (any pointer may be NULL).  Waits for the device. */
 int alore_backend_get_task(alore_backend_handle h, int count, int *status, int *matrix, int *order, int *n_order, int *total,
                            double *leg_start_xy, double *leg_goal_xy, int *fields, int *sweeps);
+/* The assignment that ALORE_BE_TASK_ASSIGNED or ALORE_BE_TASK_JOINT chose, a slab of its own beside the one above.  A mission with
+ * status ALORE_BE_TASK_OK in one of these modes writes both rows; so does, in the assigned mode, a mission whose assignment is
+ * finite and whose routing is not (ALORE_BE_TASK_E_NO_ORDER).  Every other failure, a masked mission and every launch in the greedy
+ * or optimal mode leave them untouched. */
+typedef struct alore_backend_task_assign_view {
+    const int *assignment;   /* [.][10]: the target of item i, i < n; entries beyond n are untouched */
+    const int *assign_total; /* [.][2]: (a, b) of the sum of the carry legs d(item i, target assignment[i]) */
+} alore_backend_task_assign_view;
+int alore_backend_device_task_assign(alore_backend_handle h, alore_backend_task_assign_view *out);
+/* Both rows copied to HOST arrays [count][10] and [count][2] (either pointer may be NULL).  Waits for the device. */
+int alore_backend_get_task_assign(alore_backend_handle h, int count, int *assignment, int *assign_total);
 
 /* ---- the edits a mission makes to the resident map: item and target footprints, on the device -------------------------- */
 /* What plan_manager does to its map while a mission runs (plan_manager.hpp: paintSquare / paintBox / paintTable / paintChair
