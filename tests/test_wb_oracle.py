@@ -290,6 +290,35 @@ def test_contact_rows_restatement_is_the_limit_of_the_penalty_and_holds_the_rows
     assert e[1] < 0.02 * e[0] and e[1] < 1e-3 * max(np.max(np.abs(dx)), np.max(np.abs(du)))
 
 
+@pytest.mark.parametrize("N", (1, 2, 3, 5))
+def test_stage_varying_problems_suit_float32_and_tell_stage_bugs_apart(model, N):
+    """The inputs of tests/test_wb_stages_gpu.py (tests/wb_cases.py: make_varied_problems, its seed and amplitude) with
+    the oracle's own linearisation, on the problems of its parts b (unconstrained), c (torque limits) and d (friction
+    pyramid with a lifted foot): the float32 restatement of the sweep stays within half the 1e-4 bound of the float64
+    solve, and the solve with A, B rolled by one stage or with dx0 = 0 is at least 1e-2 away from it."""
+    from tests import test_wb_stages_gpu as S
+    from oracle.wb_oracle import solve_lq_clamped
+    x0, xref, uref, xi, ui, Q, R, QN, stance = S.scenario(model, N, "plain")
+    lin = S.oracle_lin(model, xi, ui)                      # the same iterate in every part
+    for kind in ("plain", "torque", "pyramid"):
+        x0, xref, uref, xi, ui, Q, R, QN, stance = S.scenario(model, N, kind)
+        prob = (x0, xref, uref, xi, ui, Q, R, QN)
+        effort = model.effort if kind == "torque" else None
+        mu, st = (S.MU, stance) if kind == "pyramid" else (None, None)
+        clamps, worst = 0, [0.0, np.inf, np.inf]
+        for b in range(S.B):
+            args = S.lq_inputs(lin, *prob, b)
+            if kind == "plain":
+                ref = solve_lq(*args)
+            else:
+                rx, ru, nc = solve_lq_clamped(*args, list(ui[b]), effort, mu=mu, stance=None if st is None else st[b])
+                ref, clamps = (rx, ru), clamps + sum(nc)
+            f32, roll, no_dx0 = S.check_inputs(lin, prob, b, ref, effort, mu, st)
+            worst = [max(worst[0], f32), min(worst[1], roll), min(worst[2], no_dx0)]
+        print(f"N={N} {kind}: riccati_f32 vs float64 {worst[0]:.2e}; discriminators: A, B rolled {worst[1]:.2e}, dx0 = 0 {worst[2]:.2e}; clamps {clamps}")
+        assert kind == "plain" or clamps > 0
+
+
 def test_inequality_constrained_lq_solver_satisfies_its_kkt_conditions():
     """oracle/wb_oracle.py: solve_lq_inequality (the checker of the kernels' exact working-set mode) on a random LQ problem with
     torque boxes, a friction pyramid per stance foot and a foot in the air: stationarity, feasibility and the signs of the

@@ -52,6 +52,22 @@ def make_problems(model, B, N, seed=0, spread=1.0):
     return x0, xref, uref, xinit, uinit
 
 
+def make_varied_problems(model, B, N, seed=0, amp=0.25, spread=1.0):
+    """make_problems with an iterate and a reference that change from stage to stage, so that a stage off by one in the
+    kernels changes their result: independent draws per problem and per stage of amp * (0.05 rad on the joints, 0.1 on
+    the velocities, 2 Nm on the torques, 5 N on the foot forces) on the iterate -- stage 0 included, so that
+    dx0 = x0 - x_0 is not zero -- and a ramp of 4 mm per stage on the lateral base position of the reference."""
+    x0, xref, uref, xi, ui = make_problems(model, B, N, seed=seed, spread=spread)
+    rng = np.random.default_rng([seed, 1])
+    xi, ui, xref = xi.copy(), ui.copy(), xref.copy()
+    xi[:, :, 6:24] += amp * 0.05 * rng.normal(size=(B, N + 1, 18))
+    xi[:, :, 24:] += amp * 0.1 * rng.normal(size=(B, N + 1, 24))
+    ui[:, :, :18] += amp * 2.0 * rng.normal(size=(B, N, 18))
+    ui[:, :, 18:] += amp * 5.0 * rng.normal(size=(B, N, 12))
+    xref[:, :, 1] += 0.004 * np.arange(N + 1)
+    return x0, xref, uref, xi, ui
+
+
 # equilibrium inputs of stand_q() (oracle.wb_oracle.Model + equilibrium_inputs above; frozen here so that bench.py does
 # not import the oracle for input generation) -- checked against the oracle in tests/test_wb_oracle.py
 def make_problems_fast(B, N, seed=0, spread=1.0, ueq=None):
