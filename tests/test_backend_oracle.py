@@ -7,6 +7,7 @@ from scipy.integrate import quad
 
 from alore_legged_manipulator_amd.flat_traj import monte_carlo_goals, straight_goal, waypoint_path
 from oracle.backend_driver import BackendOracle, EsdfGrid
+from tests.backend_eval_cases import fd_grad
 
 
 @pytest.fixture(scope="module")
@@ -164,15 +165,6 @@ def test_esdf_bilinear_against_analytic_field(orc):
     # mode 1 leaves the gradient alone beyond mindis
     d, gr = orc.esdf(g, 5.0, 5.0, mode=1, mindis=0.6)
     assert d > 0.6 and np.all(gr == 0.0)
-
-
-def fd_grad(orc, grid, ft, stage, x, **kw):
-    g = np.zeros_like(x)
-    for i in range(len(x)):
-        h = 1e-6 * max(1.0, abs(x[i]))
-        xp = x.copy(); xp[i] += h; xm = x.copy(); xm[i] -= h
-        g[i] = (orc.eval(grid, ft, stage, xp, **kw)["cost"] - orc.eval(grid, ft, stage, xm, **kw)["cost"]) / (2 * h)
-    return g
 
 
 @pytest.mark.parametrize("stage", [1, 2])
