@@ -199,6 +199,7 @@ TASK_GREEDY, TASK_OPTIMAL, TASK_ASSIGNED, TASK_JOINT = 0, 1, 2, 3
 TASK_JOINT_MAX_TASKS = 5
 TASK_OK, TASK_MASKED, TASK_E_ENDPOINT, TASK_E_WINDOW, TASK_E_TASKS, TASK_E_NO_ORDER = 0, 1, -1, -3, -6, -7
 SEARCH_OK, SEARCH_MASKED, SEARCH_E_ENDPOINT, SEARCH_E_SAME_CELL, SEARCH_E_WINDOW, SEARCH_E_NO_PATH, SEARCH_E_POINTS = 0, 1, -1, -2, -3, -4, -5
+SEARCH_E_RANGE = -6  # wide route only (search_reserve): a cost in the window has a component of 32767 or more
 SEARCH_MAX_CELLS = 32768
 LASER_OK, LASER_E_POSE, LASER_E_CAPACITY = 0, -1, -2
 LASER_MAX_BINS = 8192
@@ -281,6 +282,9 @@ def _bind(L):
     L.alore_backend_device_search_status.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.alore_backend_search_status.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.alore_backend_search_sweeps.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.alore_backend_search_reserve.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.alore_backend_search_reserved.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.alore_backend_search_wide_ticks.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_longlong)]
     L.alore_backend_get_paths.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), DP, C.POINTER(C.c_int)]
     L.alore_backend_task_default_params.argtypes = [C.POINTER(TaskParamsC)]
     L.alore_backend_task_default_params.restype = None
@@ -1078,6 +1082,19 @@ class BatchedMSPlanner:
         self._check(self.L.alore_backend_search_paths(self.h, int(count), _dev(start_xy), stride(start_xy, start_stride), _dev(goal_xy),
                                                       stride(goal_xy, goal_stride), C.byref(p), 1, mp, ms, _stream(stream)))
 
+    def search_reserve(self, max_cells: int, slots: int = 1):
+        """Opt in to windows of more than SEARCH_MAX_CELLS cells: reserves `slots` slabs of max_cells words of device memory
+        (max_cells in (32768, 1 << 22], slots in [1, 1024], at most 1 GiB in all).  From then on search_paths and
+        search_paths_device search a slot whose window has up to max_cells cells instead of giving it SEARCH_E_WINDOW, `slots`
+        of them at a time; smaller windows go the way they went.  A second call replaces the first, max_cells = 0 releases it."""
+        self._check(self.L.alore_backend_search_reserve(self.h, int(max_cells), int(slots)))
+
+    def search_reserved(self) -> tuple:
+        """(max_cells, slots) of the reservation, (0, 0) without one"""
+        a, b = C.c_int(), C.c_int()
+        self._check(self.L.alore_backend_search_reserved(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def device_paths(self) -> PathsC:
         """the device slab of searched paths as alore_backend_paths: max_points 31, n_points and xy set, the yaws and start
         derivatives None for the caller to fill (set_paths_device(count, v.max_points, v.n_points, v.xy, start_yaw, end_yaw, ...))"""
@@ -1091,17 +1108,27 @@ class BatchedMSPlanner:
         return p.value
 
     def search_status(self, count: int | None = None) -> np.ndarray:
-        """per slot of the last search: 0 found, 1 masked out, -1 end point, -2 same cell, -3 window, -4 no path, -5 points (waits)"""
+        """per slot of the last search: 0 found, 1 masked out, -1 end point, -2 same cell, -3 window, -4 no path, -5 points,
+        -6 range (wide route only) (waits)"""
         n = int(count or getattr(self, "search_count", 0))
         out = np.zeros(n, np.int32)
         self._check(self.L.alore_backend_search_status(self.h, n, out.ctypes.data_as(C.POINTER(C.c_int))))
         return out
 
     def search_sweeps(self, count: int | None = None) -> np.ndarray:
-        """diagnostic: sweeps over the window until the field stood still, per slot of the last search (waits)"""
+        """diagnostic: sweeps over the window until the field stood still, per slot of the last search; visits of tiles for a slot
+        searched on the wide route (waits)"""
         n = int(count or getattr(self, "search_count", 0))
         out = np.zeros(n, np.int32)
         self._check(self.L.alore_backend_search_sweeps(self.h, n, out.ctypes.data_as(C.POINTER(C.c_int))))
+        return out
+
+    def search_wide_ticks(self, count: int | None = None) -> np.ndarray:
+        """diagnostic, reserved handles: [count][2] ticks of the 100 MHz device clock of the slots searched on the wide route, whole
+        slot and its walk and pruning (waits)"""
+        n = int(count or getattr(self, "search_count", 0))
+        out = np.zeros((n, 2), np.int64)
+        self._check(self.L.alore_backend_search_wide_ticks(self.h, n, out.ctypes.data_as(C.POINTER(C.c_longlong))))
         return out
 
     def paths(self, count: int | None = None) -> dict:

@@ -14,6 +14,7 @@
 #include "laser_scan_launch.h"
 #include "mission_map.h"
 #include "path_search.h"
+#include "path_search_wide.h"
 #include "task_plan.h"
 
 struct alore_backend_planner {
@@ -76,6 +77,12 @@ struct alore_backend_planner {
     double* d_path_xy = nullptr;
     hipEvent_t ev_search = nullptr; // the upload of the previous call has left h_search
     bool search_pending = false;
+    // alore_backend_search_reserve: wide_slots slabs of wide_cells words for windows of more than psearch::MAX_CELLS cells
+    unsigned* d_wide = nullptr;
+    long long* d_wide_ticks = nullptr; // [B][2] diagnostic of the wide kernel
+    int wide_cells = 0, wide_slots = 0;
+    hipEvent_t ev_wide = nullptr; // the last search that read the slabs has ended
+    bool wide_pending = false;
     // alore_backend_task_plan: the argument block followed by the staged inputs of the host route, pinned and on the device, and
     // the slab of the missions
     char *h_task = nullptr, *d_task_in = nullptr;
@@ -228,6 +235,9 @@ void free_all(alore_backend_handle h)
     if (h->h_params) (void)hipHostFree(h->h_params);
     if (h->h_search) (void)hipHostFree(h->h_search);
     if (h->ev_search) (void)hipEventDestroy(h->ev_search);
+    if (h->d_wide) (void)hipFree(h->d_wide);
+    if (h->d_wide_ticks) (void)hipFree(h->d_wide_ticks);
+    if (h->ev_wide) (void)hipEventDestroy(h->ev_wide);
     if (h->ev_build) (void)hipEventDestroy(h->ev_build);
     if (h->ev_params) (void)hipEventDestroy(h->ev_params);
     if (h->ev_check) (void)hipEventDestroy(h->ev_check);
@@ -379,6 +389,7 @@ int alore_backend_create(const alore_backend_config* cfg, int device, int max_pi
     if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_search, search_in_bytes(B), hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_search, hipEventDisableTiming);
     if (e == hipSuccess) e = backend::search_configure();
+    if (e == hipSuccess) e = backend::search_wide_configure();
     A(dalloc(&h->t_status, B)); A(dalloc(&h->t_matrix, B * TASK_MATRIX_INTS)); A(dalloc(&h->t_order, B * tplan::MAX_LEGS));
     A(dalloc(&h->t_n_order, B)); A(dalloc(&h->t_total, B * 2)); A(dalloc(&h->t_fields, B)); A(dalloc(&h->t_sweeps, B));
     A(dalloc(&h->t_src_fields, B * tplan::MAX_LEGS)); A(dalloc(&h->t_src_sweeps, B * tplan::MAX_LEGS));
@@ -1475,11 +1486,17 @@ int alore_backend_search_paths(alore_backend_handle h, int count, const double* 
     const long long map_cells = (long long)h->map.nx * h->map.ny;
     g.lds_cells = map_cells < psearch::MAX_CELLS ? (int)map_cells : psearch::MAX_CELLS;
     g.n_points = h->d_path_n; g.xy = h->d_path_xy; g.cost_ab = h->d_path_cost; g.status = h->d_search_status; g.sweeps = h->d_search_sweeps;
+    g.wide_slabs = h->d_wide; g.wide_cells = h->wide_cells; g.wide_slots = h->wide_slots; g.wide_ticks = h->d_wide_ticks;
     std::memcpy(h->h_search, &g, sizeof(g));
     BE_TRY(h, hipMemcpyAsync(h->d_search_in, h->h_search, up, hipMemcpyHostToDevice, s));
     BE_TRY(h, hipEventRecord(h->ev_search, s));
     h->search_pending = true;
     BE_TRY(h, backend::search_paths((const backend::SearchArgs*)h->d_search_in, count, g.lds_cells, s));
+    if (h->d_wide) { // the slots that the first kernel left at E_WINDOW, on the reservation's slabs
+        BE_TRY(h, backend::search_paths_wide((const backend::SearchArgs*)h->d_search_in, h->wide_slots, s));
+        BE_TRY(h, hipEventRecord(h->ev_wide, s));
+        h->wide_pending = true;
+    }
     if (!device_pointers) {
         int* hst = (int*)h->h_stage;
         BE_TRY(h, hipMemcpyAsync(hst, h->d_search_status, sizeof(int) * n, hipMemcpyDeviceToHost, s));
@@ -1488,10 +1505,55 @@ int alore_backend_search_paths(alore_backend_handle h, int count, const double* 
             if (hst[b] == psearch::E_ENDPOINT) return fail(h, ALORE_BE_E_INVALID, "search_paths: an end point is not finite or outside the map");
             if (hst[b] == psearch::E_SAME_CELL) return fail(h, ALORE_BE_E_INVALID, "search_paths: start and goal lie in one cell");
             if (hst[b] == psearch::E_NO_PATH) return fail(h, ALORE_BE_E_INVALID, "search_paths: no path inside the window");
-            if (hst[b] == psearch::E_WINDOW) return fail(h, ALORE_BE_E_UNSUPPORTED, "search_paths: the window has more than 32768 cells");
+            if (hst[b] == psearch::E_WINDOW)
+                return fail(h, ALORE_BE_E_UNSUPPORTED, "search_paths: the window has more than 32768 cells, or more than the reservation");
+            if (hst[b] == psearch::E_RANGE)
+                return fail(h, ALORE_BE_E_UNSUPPORTED, "search_paths: a cost in the window has a component of 32767 or more");
             if (hst[b] == psearch::E_POINTS) return fail(h, ALORE_BE_E_UNSUPPORTED, "search_paths: more than 1024 raw nodes or 31 way-points");
         }
     }
+    return ALORE_BE_OK;
+}
+
+int alore_backend_search_reserve(alore_backend_handle h, int max_cells, int slots)
+{
+    if (!h) return ALORE_BE_E_INVALID;
+    const bool release = max_cells == 0;
+    if (!release && (max_cells <= psearch::MAX_CELLS || max_cells > psearch::WIDE_MAX_CELLS || slots < 1 || slots > 1024 ||
+                     (long long)slots * max_cells * (long long)sizeof(unsigned) > (1ll << 30)))
+        return fail(h, ALORE_BE_E_INVALID, "search_reserve: max_cells in (32768, 1 << 22], slots in [1, 1024], slots * max_cells * 4 <= 1 GiB");
+    BE_TRY(h, hipSetDevice(h->device));
+    if (h->wide_pending) BE_TRY(h, hipEventSynchronize(h->ev_wide)); // the last search has left the slabs
+    h->wide_pending = false;
+    if (h->d_wide) BE_TRY(h, hipFree(h->d_wide));
+    h->d_wide = nullptr;
+    if (h->d_wide_ticks) BE_TRY(h, hipFree(h->d_wide_ticks));
+    h->d_wide_ticks = nullptr;
+    h->wide_cells = h->wide_slots = 0;
+    if (release) return ALORE_BE_OK;
+    if (!h->ev_wide) BE_TRY(h, hipEventCreateWithFlags(&h->ev_wide, hipEventDisableTiming));
+    BE_TRY(h, dalloc(&h->d_wide_ticks, (size_t)h->B * 2));
+    BE_TRY(h, hipMalloc((void**)&h->d_wide, sizeof(unsigned) * (size_t)slots * (size_t)max_cells));
+    h->wide_cells = max_cells;
+    h->wide_slots = slots;
+    return ALORE_BE_OK;
+}
+
+int alore_backend_search_reserved(alore_backend_handle h, int* max_cells, int* slots)
+{
+    if (!h || !max_cells || !slots) return fail(h, ALORE_BE_E_INVALID, "search_reserved: bad argument");
+    *max_cells = h->wide_cells;
+    *slots = h->wide_slots;
+    return ALORE_BE_OK;
+}
+
+int alore_backend_search_wide_ticks(alore_backend_handle h, int count, long long* out)
+{
+    if (!h || count < 1 || count > h->B || !out) return fail(h, ALORE_BE_E_INVALID, "search_wide_ticks: bad argument");
+    if (!h->d_wide_ticks) return fail(h, ALORE_BE_E_INVALID, "search_wide_ticks: no reservation (alore_backend_search_reserve)");
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, hipDeviceSynchronize());
+    BE_TRY(h, hipMemcpy(out, h->d_wide_ticks, sizeof(long long) * 2 * (size_t)count, hipMemcpyDeviceToHost));
     return ALORE_BE_OK;
 }
 

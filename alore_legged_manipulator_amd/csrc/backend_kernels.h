@@ -146,12 +146,21 @@ struct SearchArgs {
     double* xy;                    // [count][31][2]
     int* cost_ab;                  // [count][2]: the unpruned path costs a + b sqrt(2)
     int* status;                   // [count]
-    int* sweeps;                   // [count] sweeps until the field stood still (diagnostic)
+    int* sweeps;                   // [count] sweeps until the field stood still (diagnostic); visits of tiles for a wide slot
+    // the reservation for windows of more than psearch::MAX_CELLS cells (read by search_paths_wide_kernel only); null without one
+    unsigned* wide_slabs;          // [wide_slots][wide_cells] words
+    int wide_cells, wide_slots;
+    long long* wide_ticks;         // [count][2] diagnostic: ticks of the 100 MHz clock a wide slot took, and its walk and pruning of them
 };
 // the kernel reads its arguments from d_args (device memory, filled in stream order before the launch)
 hipError_t search_paths(const SearchArgs* d_args, int count, int lds_cells, hipStream_t s);
 // registers the field's LDS size with the runtime (once per device, not in stream order: call before the first search)
 hipError_t search_configure();
+// path_search_wide.hip: behind search_paths on the same stream, the slots that it left at E_WINDOW and whose window has at most
+// wide_cells cells (arithmetic in path_search_wide.h): `slots` workgroups, workgroup j owns slab j and takes the slots j, j + slots,
+// ... in turn; the field in the slab, relaxed tile by tile in LDS
+hipError_t search_paths_wide(const SearchArgs* d_args, int slots, hipStream_t s);
+hipError_t search_wide_configure();
 
 // task_plan.hip: the visit order of rearrangement missions from path costs on the handle's distance field (arithmetic and contract
 // in task_plan.h): task_costs_kernel, one workgroup per (mission, source point), fills the cost matrices; task_order_kernel, one

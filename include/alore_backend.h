@@ -500,7 +500,16 @@ int alore_backend_get_laser(alore_backend_handle h, int count, double *range_ima
  * stays in a window: the bounding box of the two cells grown by ceil(window_margin / res) cells a side, clipped to the map, at most
  * ALORE_BE_SEARCH_MAX_CELLS cells.  Deviations: an end point outside the map or not finite is refused (the reference clamps), equal
  * end cells are refused (the reference hands on a one-point path).  One workgroup per problem, the field of the window in LDS
- * (csrc/path_search.hip). */
+ * (csrc/path_search.hip).
+ * LARGER WINDOWS are opt-in: after alore_backend_search_reserve(h, max_cells, slots) a slot whose window has more than
+ * ALORE_BE_SEARCH_MAX_CELLS and at most max_cells cells is searched by a second kernel behind the first on the same stream, which
+ * keeps the field in one of the reservation's `slots` slabs in device memory and relaxes it tile by tile in LDS
+ * (csrc/path_search_wide.h, csrc/path_search_wide.hip).  The contract is the same and so is the answer, bit for bit; slots of at
+ * most ALORE_BE_SEARCH_MAX_CELLS cells take the first kernel as before.  One more status exists on that route only,
+ * ALORE_BE_SEARCH_E_RANGE: a cost is the pair (a, b) in 16 bits each, ordered exactly while both stay below 32768, which a window
+ * of 32768 cells guarantees and one of 4 M cells does not; a slot in whose window the goal reaches a cell whose least cost has
+ * a >= 32767 or b >= 32767 (a route of more than 3 km at 0.1 m) fails with it, whatever its own path.  alore_backend_task_plan
+ * takes no part in the reservation and keeps ALORE_BE_TASK_E_WINDOW at ALORE_BE_SEARCH_MAX_CELLS. */
 typedef struct alore_backend_search_params {
     double safe_dis;      /* jps_safe_dis */
     double window_margin; /* metres round the bounding box of start and goal */
@@ -514,9 +523,18 @@ void alore_backend_search_default_params(alore_backend_search_params *p);
 #define ALORE_BE_SEARCH_MASKED 1          /* the mask left the slot out: nothing of it was touched, n_points included */
 #define ALORE_BE_SEARCH_E_ENDPOINT (-1)   /* a coordinate is not finite or outside [lo, hi] of the map */
 #define ALORE_BE_SEARCH_E_SAME_CELL (-2)  /* start and goal lie in one cell */
-#define ALORE_BE_SEARCH_E_WINDOW (-3)     /* the window has more than ALORE_BE_SEARCH_MAX_CELLS cells */
+#define ALORE_BE_SEARCH_E_WINDOW (-3)     /* the window has more than ALORE_BE_SEARCH_MAX_CELLS cells, or more than the reservation */
 #define ALORE_BE_SEARCH_E_NO_PATH (-4)    /* an end cell is not free, or the goal cannot be reached inside the window */
 #define ALORE_BE_SEARCH_E_POINTS (-5)     /* more than 1024 raw nodes, or more than 31 way-points after pruning */
+#define ALORE_BE_SEARCH_E_RANGE (-6)      /* wide route only: a cost in the window has a component of 32767 or more; decided after the
+                                             field, before the walk (so before its E_NO_PATH and E_POINTS) */
+
+/* Reserves device memory for searches on windows of more than ALORE_BE_SEARCH_MAX_CELLS cells: `slots` slabs of max_cells words.
+ * max_cells in (32768, 1 << 22], slots in [1, 1024], slots * max_cells * 4 <= 1 GiB, else ALORE_BE_E_INVALID; a second call
+ * replaces the first (waits for the stream of the last search); max_cells = 0 releases it.  No map is needed yet.  `slots` is
+ * the number of wide slots searched at a time (one workgroup each); a call with more of them takes them in turn. */
+int alore_backend_search_reserve(alore_backend_handle h, int max_cells, int slots);
+int alore_backend_search_reserved(alore_backend_handle h, int *max_cells, int *slots);   /* 0, 0 without one */
 
 /* Searches slots 0..count-1 on the handle's current map (resident, or set by alore_backend_set_map / alore_backend_build_esdf;
  * without one: ALORE_BE_E_INVALID).  x, y of slot b are the two doubles at (char *)start_xy + b * start_stride_bytes, likewise the
@@ -528,7 +546,11 @@ void alore_backend_search_default_params(alore_backend_search_params *p);
  * device_pointers != 0: start_xy, goal_xy and mask are DEVICE memory read in stream order; nothing is allocated, nothing crosses
  * the bus but the argument block and nothing waits (a second call waits for the first one's block to have left the host).
  * device_pointers == 0: they are HOST memory; they are uploaded, the stream is synchronised, and the call returns, for the first
- * slot that failed, ALORE_BE_E_INVALID (end point, same cell, no path) or ALORE_BE_E_UNSUPPORTED (window, points). */
+ * slot that failed, ALORE_BE_E_INVALID (end point, same cell, no path) or ALORE_BE_E_UNSUPPORTED (window, points, range).
+ * With a reservation (alore_backend_search_reserve) both forms enqueue the second kernel too: a slot whose window has more than
+ * ALORE_BE_SEARCH_MAX_CELLS and at most the reserved number of cells gets a searched path or one of the negative statuses above
+ * instead of ALORE_BE_SEARCH_E_WINDOW, a larger window stays ALORE_BE_SEARCH_E_WINDOW; the device-pointer form still allocates
+ * nothing, waits for nothing and moves only the argument block, and the host form's return code is taken after both kernels. */
 int alore_backend_search_paths(alore_backend_handle h, int count, const double *start_xy, int start_stride_bytes, const double *goal_xy,
                                int goal_stride_bytes, const alore_backend_search_params *params, int device_pointers, const int *mask,
                                int mask_stride_bytes, void *stream);
@@ -543,8 +565,12 @@ int alore_backend_search_status(alore_backend_handle h, int count, int *out);
 /* The searched paths copied to HOST arrays (any pointer may be NULL): n_points [count], xy [count][31][2], cost_ab [count][2] (the
  * cost a + b sqrt 2 of the unpruned path; written by slots that succeeded).  Waits for the device. */
 int alore_backend_get_paths(alore_backend_handle h, int count, int *n_points, double *xy, int *cost_ab);
-/* diagnostic: sweeps over the window until the field stood still, per slot of the last search; HOST out[count]; waits */
+/* diagnostic: sweeps over the window until the field stood still, per slot of the last search; for a slot searched on the wide
+ * route the number of visits of tiles instead; HOST out[count]; waits */
 int alore_backend_search_sweeps(alore_backend_handle h, int count, int *out);
+/* diagnostic, with a reservation only: HOST out[count][2], ticks of the device's 100 MHz clock that a slot took on the wide route
+ * and the part of them in its walk and pruning; a slot that did not take the wide route keeps what it had (0 at first); waits */
+int alore_backend_search_wide_ticks(alore_backend_handle h, int count, long long *out);
 
 /* ---- the visit order of rearrangement missions from path costs on the handle's map, on the device --------------------- */
 /* What plan_manager does before any trajectory is planned (plan_manager.hpp:210-250): the grid-path length between the robot, n
