@@ -199,6 +199,7 @@ TASK_GREEDY, TASK_OPTIMAL, TASK_ASSIGNED, TASK_JOINT = 0, 1, 2, 3
 TASK_JOINT_MAX_TASKS = 5
 TASK_OK, TASK_MASKED, TASK_E_ENDPOINT, TASK_E_WINDOW, TASK_E_TASKS, TASK_E_NO_ORDER = 0, 1, -1, -3, -6, -7
 SEARCH_OK, SEARCH_MASKED, SEARCH_E_ENDPOINT, SEARCH_E_SAME_CELL, SEARCH_E_WINDOW, SEARCH_E_NO_PATH, SEARCH_E_POINTS = 0, 1, -1, -2, -3, -4, -5
+TASK_E_RANGE = -8  # wide missions only (task_reserve): a cost field of the mission has a component of 32767 or more
 SEARCH_E_RANGE = -6  # wide route only (search_reserve): a cost in the window has a component of 32767 or more
 SEARCH_MAX_CELLS = 32768
 LASER_OK, LASER_E_POSE, LASER_E_CAPACITY = 0, -1, -2
@@ -293,6 +294,9 @@ def _bind(L):
     L.alore_backend_device_task.argtypes = [C.c_void_p, C.POINTER(TaskViewC)]
     L.alore_backend_get_task.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_int)] * 5 + [DP, DP] + [C.POINTER(C.c_int)] * 2
     L.alore_backend_task_reorder.argtypes = [C.c_void_p, C.c_void_p]
+    L.alore_backend_task_reserve.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.alore_backend_task_reserved.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.alore_backend_task_wide_ticks.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_longlong)]
     L.alore_backend_device_task_assign.argtypes = [C.c_void_p, C.POINTER(TaskAssignViewC)]
     L.alore_backend_get_task_assign.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_int)] * 2
     L.alore_backend_map_paint.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
@@ -1211,6 +1215,29 @@ class BatchedMSPlanner:
     def task_reorder(self, stream=None):
         """diagnostic: the order phase of the last task_plan / task_plan_device launch again, alone, on the matrices in the slab"""
         self._check(self.L.alore_backend_task_reorder(self.h, _stream(stream)))
+
+    def task_reserve(self, max_cells: int, slots: int = 1):
+        """Opt in to missions on windows of more than SEARCH_MAX_CELLS cells: reserves `slots` slabs of max_cells words of device
+        memory for task_plan (its own; search_reserve's stay the search's; max_cells in (32768, 1 << 22], slots in [1, 1024], at
+        most 1 GiB in all).  From then on task_plan and task_plan_device plan a mission whose window has up to max_cells cells
+        instead of giving it TASK_E_WINDOW, the fields of `slots` (mission, source point) pairs at a time; smaller windows go the
+        way they went.  One status is new on that route, TASK_E_RANGE.  A second call replaces the first, max_cells = 0 releases
+        it.  The legs of such a mission need search_reserve if they are to be searched afterwards."""
+        self._check(self.L.alore_backend_task_reserve(self.h, int(max_cells), int(slots)))
+
+    def task_reserved(self) -> tuple:
+        """(max_cells, slots) of the task reservation, (0, 0) without one"""
+        a, b = C.c_int(), C.c_int()
+        self._check(self.L.alore_backend_task_reserved(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def task_wide_ticks(self, count: int | None = None) -> np.ndarray:
+        """diagnostic (task_reserve only): [count][TASK_MAX_LEGS] ticks of the device's 100 MHz clock that the fields of a source
+        point took on the wide route; waits"""
+        n = int(count or getattr(self, "task_count", 0))
+        out = np.zeros((n, TASK_MAX_LEGS), np.int64)
+        self._check(self.L.alore_backend_task_wide_ticks(self.h, n, out.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return out
 
     def device_task_assign(self) -> TaskAssignViewC:
         """the device rows of the assignment that the last TASK_ASSIGNED / TASK_JOINT launch chose (alore_backend_task_assign_view)"""

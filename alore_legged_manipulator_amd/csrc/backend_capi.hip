@@ -92,6 +92,14 @@ struct alore_backend_planner {
     hipEvent_t ev_task = nullptr; // the upload of the previous call has left h_task
     bool task_pending = false;
     int task_last_count = 0, task_last_mode = 0; // of the launch whose argument block lies in d_task_in
+    // alore_backend_task_reserve: task_slots slabs of task_cells words for missions on windows of more than psearch::MAX_CELLS
+    // cells (its own: the search's reservation stays the search's), and the per-source range flags of such missions [B][20]
+    unsigned* d_task_wide = nullptr;
+    int* t_src_range = nullptr;
+    long long* d_task_ticks = nullptr; // [B][20] diagnostic of the wide kernel, with a reservation
+    int task_cells = 0, task_slots = 0;
+    hipEvent_t ev_task_wide = nullptr; // the last task launch that read the slabs has ended
+    bool task_wide_pending = false;
     // alore_backend_laser_*: the sensor (alore_backend_laser_create), its world cloud and the slabs of the scans; the argument
     // block is followed by the staged poses of the host route, pinned and on the device
     bool has_laser = false, has_cloud = false;
@@ -223,12 +231,13 @@ void free_all(alore_backend_handle h)
                     h->d_cost, h->d_err, h->d_ret, h->d_params, h->d_order, h->d_check_in, h->d_check, h->d_build_in, h->d_build_status,
                     h->d_search_in, h->d_path_n, h->d_path_cost, h->d_search_status, h->d_search_sweeps, h->d_path_xy,
                     h->d_task_in, h->t_status, h->t_matrix, h->t_order, h->t_n_order, h->t_total, h->t_fields, h->t_sweeps, h->t_src_fields,
-                    h->t_src_sweeps, h->t_assignment, h->t_assign_total, h->t_leg_start, h->t_leg_goal, h->p_desc, h->p_counters, h->p_host_edits, h->m_slab_mem, h->m_stage, h->m_edits,
+                    h->t_src_sweeps, h->t_src_range, h->d_task_wide, h->d_task_ticks, h->t_assignment, h->t_assign_total, h->t_leg_start, h->t_leg_goal, h->p_desc, h->p_counters, h->p_host_edits, h->m_slab_mem, h->m_stage, h->m_edits,
                     h->g_mem, h->g_stage, h->k_table, h->k_fe, h->k_class_of, h->k_clamped, h->k_stage, h->k_xv, h->k_stats, h->k_params};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_task) (void)hipHostFree(h->h_task);
     if (h->ev_task) (void)hipEventDestroy(h->ev_task);
+    if (h->ev_task_wide) (void)hipEventDestroy(h->ev_task_wide);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->h_check) (void)hipHostFree(h->h_check);
     if (h->h_build) (void)hipHostFree(h->h_build);
@@ -392,7 +401,7 @@ int alore_backend_create(const alore_backend_config* cfg, int device, int max_pi
     if (e == hipSuccess) e = backend::search_wide_configure();
     A(dalloc(&h->t_status, B)); A(dalloc(&h->t_matrix, B * TASK_MATRIX_INTS)); A(dalloc(&h->t_order, B * tplan::MAX_LEGS));
     A(dalloc(&h->t_n_order, B)); A(dalloc(&h->t_total, B * 2)); A(dalloc(&h->t_fields, B)); A(dalloc(&h->t_sweeps, B));
-    A(dalloc(&h->t_src_fields, B * tplan::MAX_LEGS)); A(dalloc(&h->t_src_sweeps, B * tplan::MAX_LEGS));
+    A(dalloc(&h->t_src_fields, B * tplan::MAX_LEGS)); A(dalloc(&h->t_src_sweeps, B * tplan::MAX_LEGS)); A(dalloc(&h->t_src_range, B * tplan::MAX_LEGS));
     A(dalloc(&h->t_leg_start, B * tplan::MAX_LEGS * 2)); A(dalloc(&h->t_leg_goal, B * tplan::MAX_LEGS * 2));
     A(dalloc(&h->t_assignment, B * tplan::MAX_TASKS)); A(dalloc(&h->t_assign_total, B * 2));
     A(dalloc(&h->d_task_in, task_in_bytes(B, tplan::MAX_TASKS)));
@@ -1670,13 +1679,18 @@ int alore_backend_task_plan(alore_backend_handle h, int count, int max_tasks, co
     g.leg_start_xy = h->t_leg_start; g.leg_goal_xy = h->t_leg_goal; g.fields = h->t_fields; g.sweeps = h->t_sweeps;
     g.src_fields = h->t_src_fields; g.src_sweeps = h->t_src_sweeps;
     g.assignment = h->t_assignment; g.assign_total = h->t_assign_total;
+    g.wide_slabs = h->d_task_wide; g.wide_cells = h->task_cells; g.wide_slots = h->task_slots; g.src_range = h->t_src_range; g.src_ticks = h->d_task_ticks;
     std::memcpy(h->h_task, &g, sizeof(g));
     BE_TRY(h, hipMemcpyAsync(h->d_task_in, h->h_task, up, hipMemcpyHostToDevice, s));
     BE_TRY(h, hipEventRecord(h->ev_task, s));
     h->task_pending = true;
-    BE_TRY(h, backend::task_plan((const backend::TaskArgs*)h->d_task_in, count, g.max_tasks, prm.mode, g.lds_cells, s));
+    BE_TRY(h, backend::task_plan((const backend::TaskArgs*)h->d_task_in, count, g.max_tasks, prm.mode, g.lds_cells, h->task_slots, s));
     h->task_last_count = count;
     h->task_last_mode = prm.mode;
+    if (h->d_task_wide) {
+        BE_TRY(h, hipEventRecord(h->ev_task_wide, s));
+        h->task_wide_pending = true;
+    }
     if (!device_pointers) {
         int* hst = (int*)h->h_stage;
         BE_TRY(h, hipMemcpyAsync(hst, h->t_status, sizeof(int) * n, hipMemcpyDeviceToHost, s));
@@ -1685,7 +1699,10 @@ int alore_backend_task_plan(alore_backend_handle h, int count, int max_tasks, co
             if (hst[b] == tplan::E_TASKS) return fail(h, ALORE_BE_E_INVALID, "task_plan: mission failed: a task count is outside 1..max_tasks (joint mode: 1..5), or an assignment is no permutation");
             if (hst[b] == tplan::E_ENDPOINT) return fail(h, ALORE_BE_E_INVALID, "task_plan: mission failed: a point is not finite or outside the map");
             if (hst[b] == tplan::E_NO_ORDER) return fail(h, ALORE_BE_E_INVALID, "task_plan: mission failed: no order has a finite cost");
-            if (hst[b] == tplan::E_WINDOW) return fail(h, ALORE_BE_E_UNSUPPORTED, "task_plan: mission failed: the window has more than 32768 cells");
+            if (hst[b] == tplan::E_WINDOW)
+                return fail(h, ALORE_BE_E_UNSUPPORTED, "task_plan: mission failed: the window has more than 32768 cells, or more than the reservation");
+            if (hst[b] == tplan::E_RANGE)
+                return fail(h, ALORE_BE_E_UNSUPPORTED, "task_plan: mission failed: a cost in the window has a component of 32767 or more");
         }
     }
     return ALORE_BE_OK;
@@ -1696,6 +1713,48 @@ int alore_backend_task_reorder(alore_backend_handle h, void* stream)
     if (!h || h->task_last_count < 1) return fail(h, ALORE_BE_E_INVALID, "task_reorder: no alore_backend_task_plan launch on this handle");
     BE_TRY(h, hipSetDevice(h->device));
     BE_TRY(h, backend::task_order((const backend::TaskArgs*)h->d_task_in, h->task_last_count, h->task_last_mode, (hipStream_t)stream));
+    return ALORE_BE_OK;
+}
+
+int alore_backend_task_reserve(alore_backend_handle h, int max_cells, int slots)
+{
+    if (!h) return ALORE_BE_E_INVALID;
+    const bool release = max_cells == 0;
+    if (!release && (max_cells <= psearch::MAX_CELLS || max_cells > psearch::WIDE_MAX_CELLS || slots < 1 || slots > 1024 ||
+                     (long long)slots * max_cells * (long long)sizeof(unsigned) > (1ll << 30)))
+        return fail(h, ALORE_BE_E_INVALID, "task_reserve: max_cells in (32768, 1 << 22], slots in [1, 1024], slots * max_cells * 4 <= 1 GiB");
+    BE_TRY(h, hipSetDevice(h->device));
+    if (h->task_wide_pending) BE_TRY(h, hipEventSynchronize(h->ev_task_wide)); // the last task launch has left the slabs
+    h->task_wide_pending = false;
+    if (h->d_task_wide) BE_TRY(h, hipFree(h->d_task_wide));
+    h->d_task_wide = nullptr;
+    if (h->d_task_ticks) BE_TRY(h, hipFree(h->d_task_ticks));
+    h->d_task_ticks = nullptr;
+    h->task_cells = h->task_slots = 0;
+    if (release) return ALORE_BE_OK;
+    if (!h->ev_task_wide) BE_TRY(h, hipEventCreateWithFlags(&h->ev_task_wide, hipEventDisableTiming));
+    BE_TRY(h, dalloc(&h->d_task_ticks, (size_t)h->B * tplan::MAX_LEGS));
+    BE_TRY(h, hipMalloc((void**)&h->d_task_wide, sizeof(unsigned) * (size_t)slots * (size_t)max_cells));
+    h->task_cells = max_cells;
+    h->task_slots = slots;
+    return ALORE_BE_OK;
+}
+
+int alore_backend_task_wide_ticks(alore_backend_handle h, int count, long long* out)
+{
+    if (!h || count < 1 || count > h->B || !out) return fail(h, ALORE_BE_E_INVALID, "task_wide_ticks: bad argument");
+    if (!h->d_task_ticks) return fail(h, ALORE_BE_E_INVALID, "task_wide_ticks: no reservation (alore_backend_task_reserve)");
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, hipDeviceSynchronize());
+    BE_TRY(h, hipMemcpy(out, h->d_task_ticks, sizeof(long long) * tplan::MAX_LEGS * (size_t)count, hipMemcpyDeviceToHost));
+    return ALORE_BE_OK;
+}
+
+int alore_backend_task_reserved(alore_backend_handle h, int* max_cells, int* slots)
+{
+    if (!h || !max_cells || !slots) return fail(h, ALORE_BE_E_INVALID, "task_reserved: bad argument");
+    *max_cells = h->task_cells;
+    *slots = h->task_slots;
     return ALORE_BE_OK;
 }
 

@@ -186,10 +186,23 @@ struct TaskArgs {
     int *src_fields, *src_sweeps;  // [count][20] per source point: what task_order_kernel adds up (no atomics)
     int* assignment;               // [count][10], modes ASSIGNED and JOINT: the target of item i
     int* assign_total;             // [count][2], the sum of its carry legs
+    // the reservation for missions whose window has more than lds_cells cells (alore_backend_task_reserve); null without one, and
+    // then nothing below is read
+    unsigned* wide_slabs;          // [wide_slots][wide_cells] words
+    int wide_cells, wide_slots;
+    int* src_range;                // [count][20] per source point of a wide mission: a field of it has a word out of range
+    long long* src_ticks;          // [count][20] diagnostic: ticks of the 100 MHz clock that the fields of such a source took
 };
+// the largest window a launch with these arguments plans: what LDS holds, or the reservation's slab
+__host__ __device__ inline long long task_window_cap(const TaskArgs& a)
+{
+    const long long wide = !a.wide_slabs ? 0 : a.wide_cells < (1 << 22) ? a.wide_cells : (1 << 22);
+    return wide > a.lds_cells ? wide : a.lds_cells;
+}
 // task_assign_order_kernel (mode ASSIGNED) and task_joint_kernel (mode JOINT) stand in for task_order_kernel in a launch of their mode.
 // The kernels read their arguments from d_args (device memory, filled in stream order before the launch)
-hipError_t task_plan(const TaskArgs* d_args, int count, int max_tasks, int mode, int lds_cells, hipStream_t s);
+// wide_slots > 0 (a reservation, whose fields d_args holds): task_costs_wide_kernel, wide_slots workgroups, between the two
+hipError_t task_plan(const TaskArgs* d_args, int count, int max_tasks, int mode, int lds_cells, int wide_slots, hipStream_t s);
 // the order phase alone, on the matrices that lie in the slab: the second launch of task_plan
 hipError_t task_order(const TaskArgs* d_args, int count, int mode, hipStream_t s);
 // registers the LDS sizes with the runtime (once per device, not in stream order: call before the first task_plan)

@@ -17,17 +17,11 @@
 // fit in a CU's LDS; the 91 registers allow one (bounded to 64 the compiler spills, which was not taken).
 #include "backend_kernels.h"
 #include "path_search_wide.h"
+#include "wide_visit.h"
 
 namespace backend {
 
 namespace ps = psearch;
-
-constexpr int WIDE_THREADS = 1024;
-constexpr int WTX = 126, WTY = 126;                   // interior cells of a tile
-constexpr int WS = WTY + 2;                           // row length of the tile array
-constexpr int WIDE_TILE_WORDS = (WTX + 2) * WS;
-constexpr int WIDE_DIRTY_WORDS = ps::dirty_words<WTX, WTY>(ps::WIDE_MAX_CELLS);
-static_assert(WS == 128 && WIDE_TILE_WORDS % WIDE_THREADS == 0, "the load and store loops address the tile array by i >> 7, i & 127");
 
 extern __shared__ __align__(16) unsigned wide_lds[];
 
@@ -74,42 +68,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void search_paths_wide_kernel(const S
             if (t < 0) break;
             ++visits;
             const ps::Tile tt = ps::tile_at<WTX, WTY>(w, tl, t);
-            for (int i = tid; i < WIDE_TILE_WORDS; i += WIDE_THREADS) {
-                const int lx = i >> 7, ly = i & 127;
-                if (lx < tt.tw + 2 && ly < tt.th + 2) tile[i] = ps::slab_word(slab, w, tt.x0 + lx - 1, tt.y0 + ly - 1);
-            }
-            __syncthreads();
-            const int n = tt.tw * tt.th;
-            const int chunk = ((n + WIDE_THREADS - 1) / WIDE_THREADS) | 1;
-            const int lo = min(tid * chunk, n), hi = min(lo + chunk, n);
-            int sweeps = 0;
-            for (;;) {
-                int changed = 0;
-                if (lo < hi) {
-                    if (sweeps & 1) {
-                        int x = (hi - 1) / tt.th, y = (hi - 1) - x * tt.th;
-                        for (int c = hi - 1; c >= lo; --c) {
-                            changed |= (int)ps::relax_tile_cell(tile, WS, x + 1, y + 1);
-                            if (--y < 0) { y = tt.th - 1; --x; }
-                        }
-                    } else {
-                        int x = lo / tt.th, y = lo - x * tt.th;
-                        for (int c = lo; c < hi; ++c) {
-                            changed |= (int)ps::relax_tile_cell(tile, WS, x + 1, y + 1);
-                            if (++y == tt.th) { y = 0; ++x; }
-                        }
-                    }
-                }
-                ++sweeps;
-                if (!__syncthreads_or(changed)) break;
-            }
-            if (sweeps > 1) { // a sweep changed a word
-                for (int i = tid; i < WIDE_TILE_WORDS; i += WIDE_THREADS) {
-                    const int lx = i >> 7, ly = i & 127;
-                    if (lx >= 1 && lx <= tt.tw && ly >= 1 && ly <= tt.th) slab[(tt.x0 + lx - 1) * w.wy + (tt.y0 + ly - 1)] = tile[i];
-                }
-                if (tid == 0) ps::mark_neighbours(dirty, tl, t);
-            }
+            if (wide_visit(slab, w, tt, tile, tid) && tid == 0) ps::mark_neighbours(dirty, tl, t); // a sweep changed a word
             __syncthreads(); // the stores before the next loads, and *next and the tile array are free again
         }
         int range = 0;

@@ -70,6 +70,23 @@
 //            assignment[MAX_TASKS], the target of item i for i < n, entries beyond n untouched, with assign_total[2], the sum of
 //            its carry legs.  Both rows are written by a mission with status OK, and in the ASSIGNED mode by a mission whose
 //            assignment is finite and whose routing is not (E_NO_ORDER); by no other mission, and never in the other two modes.
+//   WIDE     missions on windows beyond LDS (alore_backend_task_reserve; task_plan_wide.h has the serial form, task_costs_wide_kernel
+//            the device's).  check_mission takes the cap on the window as a parameter; the form without it keeps
+//            psearch::MAX_CELLS, and the order of the checks does not change.  A mission whose window has more cells than LDS
+//            holds and at most the cap has its fields in a slab of device memory, relaxed tile by tile by the machinery of
+//            path_search_wide.h as it stands (relax_tile_cell: a word with a component of 32767 or more is never extended); a
+//            field starts with the root's tile and the tiles of the root's eight neighbours dirty (task_plan_wide.h).
+//            Everything above holds unchanged -- matrix, the four orders, tie rules, legs, fields, masked and failed missions,
+//            E_NO_ORDER with its matrix written -- with two differences.  sweeps is the most VISITS OF TILES any field of the
+//            mission needed.  And THE RANGE RULE: E_RANGE -8 (not psearch::E_RANGE's -6, which is E_TASKS here) if any field the
+//            mission computes has a reached word with a >= 32767 or b >= 32767.  A field is ROOTED AT THE CELL OF THE LOWER
+//            INDEX: source k with safe_kj for the targets j > k, one field per distinct safe_kj in order of first appearance,
+//            computed whether or not a target shares the source's cell.  The flag is a property of the map, the window, the
+//            safe distance and the root (path_search_wide.h), so an oracle decides it from its own fields if it roots them the
+//            same way.  E_RANGE is decided after the matrix and before any ordering, so before E_NO_ORDER, in all four modes:
+//            status, n_order = 0, fields and sweeps are written, the matrix rows of the mission are unspecified, order, total,
+//            legs and the assignment rows untouched.  The exactness of sums holds as stated: without the flag every component
+//            of every entry is below 32767, twenty legs stay below 2^41 in the squared comparison.
 // DEVIATIONS FROM THE REFERENCE
 //   the window: the reference searches the whole map;  an end point outside the map is refused, the reference clamps it;  the tie
 //   rules of the optimal, assigned and joint modes;  the assigned and joint modes themselves: the reference has the pieces
@@ -88,6 +105,7 @@ namespace tplan {
 
 constexpr int MAX_TASKS = 10, P_MAX = 1 + 2 * MAX_TASKS, MAX_LEGS = 2 * MAX_TASKS;
 constexpr int OK = 0, MASKED = 1, E_ENDPOINT = -1, E_WINDOW = -3, E_TASKS = -6, E_NO_ORDER = -7;
+constexpr int E_RANGE = -8; // wide missions only: a field of the mission has a reached word with a component of 32767 or more
 constexpr int GREEDY = 0, OPTIMAL = 1, ASSIGNED = 2, JOINT = 3;
 constexpr int STATES = (1 << MAX_TASKS) * MAX_TASKS; // togo[S * MAX_TASKS + last]: 80 KiB
 constexpr int REST_STATES = 1 << MAX_TASKS;          // rest[T]: 8 KiB
@@ -130,8 +148,9 @@ struct Mission {
 // the most tasks a mission may have in a launch for rows of max_tasks: what the joint mode hands check_mission as max_tasks, so
 // that n > JOINT_MAX_TASKS is E_TASKS there by the check of n that every mode has
 PS_HD int task_limit(int mode, int max_tasks) { return (mode == JOINT && max_tasks > JOINT_MAX_TASKS) ? JOINT_MAX_TASKS : max_tasks; }
-// the checks of a mission, in the order tasks, end point, window; pts: the mission's row of points
-PS_HD Mission check_mission(const psearch::Grid& g, int n, int max_tasks, const double* pts, const int* assign, int mode, double window_margin)
+// the checks of a mission, in the order tasks, end point, window; pts: the mission's row of points; max_cells: the cap on the window
+PS_HD Mission check_mission(const psearch::Grid& g, int n, int max_tasks, const double* pts, const int* assign, int mode, double window_margin,
+                            long long max_cells)
 {
     Mission m{};
     m.status = E_TASKS;
@@ -163,8 +182,13 @@ PS_HD Mission check_mission(const psearch::Grid& g, int n, int max_tasks, const 
     const int x0 = xa < 0 ? 0 : (int)xa, x1 = xb > g.nx - 1 ? g.nx - 1 : (int)xb;
     const int y0 = ya < 0 ? 0 : (int)ya, y1 = yb > g.ny - 1 ? g.ny - 1 : (int)yb;
     m.x0 = x0; m.y0 = y0; m.wx = x1 - x0 + 1; m.wy = y1 - y0 + 1;
-    m.status = ((long long)m.wx * m.wy > psearch::MAX_CELLS) ? E_WINDOW : OK;
+    m.status = ((long long)m.wx * m.wy > max_cells) ? E_WINDOW : OK;
     return m;
+}
+// the cap of a window that lies in LDS
+PS_HD Mission check_mission(const psearch::Grid& g, int n, int max_tasks, const double* pts, const int* assign, int mode, double window_margin)
+{
+    return check_mission(g, n, max_tasks, pts, assign, mode, window_margin, (long long)psearch::MAX_CELLS);
 }
 
 // the cell of point p in window coordinates, x * wy + y, and the map's distance there (a checked mission: the point is inside)
@@ -474,18 +498,24 @@ inline int route_one(const int* mat, int n, const int* assign, Cost* togo, const
         }
     return optimal_order(mat, n, assign, togo, o.order, o.n_order, o.total);
 }
-inline int plan_one(const psearch::Grid& g, int n, int max_tasks, const double* pts, const int* assign, const Params& p, unsigned* words,
-                    Cost* togo, const Out& o)
+// the order of a mission whose matrix is filled, modes GREEDY and OPTIMAL
+inline int order_given(int n, const double* pts, const int* assign, const Params& p, Cost* togo, const Out& o)
 {
-    const Mission m = check_mission(g, n, max_tasks, pts, assign, p.mode, p.window_margin);
-    if (m.status != OK) { *o.n_order = 0; return m.status; }
-    fill_matrix(g, m, pts, p, words, o);
     int status = OK;
     if (p.mode == OPTIMAL) status = route_one(o.matrix, n, assign, togo, o);
     else greedy_order(o.matrix, n, o.order, o.n_order, o.total);
     if (status == OK) write_legs(pts, n, o.order, *o.n_order, o.leg_start_xy, o.leg_goal_xy);
     return status;
 }
+inline int plan_one(const psearch::Grid& g, int n, int max_tasks, const double* pts, const int* assign, const Params& p, unsigned* words,
+                    Cost* togo, const Out& o)
+{
+    const Mission m = check_mission(g, n, max_tasks, pts, assign, p.mode, p.window_margin);
+    if (m.status != OK) { *o.n_order = 0; return m.status; }
+    fill_matrix(g, m, pts, p, words, o);
+    return order_given(n, pts, assign, p, togo, o);
+}
+inline int order_chosen(int n, const double* pts, const Params& p, Cost* table, const Out& o, int* assignment, int* assign_total);
 // the modes that choose the assignment (p.mode ASSIGNED or JOINT).  table[]: ASSIGNED_STATES pairs, togo then rest (ASSIGNED), or
 // JOINT_STATES pairs (JOINT).  assignment[MAX_TASKS] and assign_total[2] are written as the contract says
 inline int plan_one_assigned(const psearch::Grid& g, int n, int max_tasks, const double* pts, const Params& p, unsigned* words, Cost* table,
@@ -494,6 +524,11 @@ inline int plan_one_assigned(const psearch::Grid& g, int n, int max_tasks, const
     const Mission m = check_mission(g, n, task_limit(p.mode, max_tasks), pts, nullptr, p.mode, p.window_margin);
     if (m.status != OK) { *o.n_order = 0; return m.status; }
     fill_matrix(g, m, pts, p, words, o);
+    return order_chosen(n, pts, p, table, o, assignment, assign_total);
+}
+// the order of a mission whose matrix is filled, modes ASSIGNED and JOINT
+inline int order_chosen(int n, const double* pts, const Params& p, Cost* table, const Out& o, int* assignment, int* assign_total)
+{
     int status;
     if (p.mode == JOINT) {
         for (int level = n; level >= 1; --level)

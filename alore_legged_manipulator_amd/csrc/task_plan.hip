@@ -26,7 +26,8 @@
 // directly indexed, no ranking) level by level in the number of tasks done; 43.6 KiB.  A launch in the greedy or optimal mode
 // enqueues what it always did.
 #include "backend_kernels.h"
-#include "task_plan.h"
+#include "task_plan_wide.h"
+#include "wide_visit.h"
 
 namespace backend {
 
@@ -155,15 +156,126 @@ __global__ __launch_bounds__(COST_THREADS) void task_costs_kernel(const TaskArgs
     }
 }
 
+// ---- missions on windows beyond LDS (alore_backend_task_reserve) ----------------------------------------------------------------
+// task_costs_wide_kernel: `wide_slots` workgroups of 1024 threads between task_costs_kernel and the order kernel on the same stream,
+// on a handle with a task reservation only.  Workgroup j owns slab j and takes the work items i = m (2 max_tasks) + k, mission m
+// and source point k, for i = j, j + slots, ...: the sources of one mission spread over the workgroups.  A mission whose status
+// task_costs_kernel did not leave at E_WINDOW is passed over at the cost of one load.  For the others every thread repeats the
+// mission's checks with the reservation's cap (uniform); an item is worked on if the mission is OK under that cap, its window has
+// more than lds_cells cells (task_costs_kernel left it at E_WINDOW) and k < P - 1, and skipped otherwise.  Per distinct safe_kj in
+// order of first appearance: every word of the window is initialised in the slab (a slab that served another field leaks nothing),
+// the field is relaxed tile by tile exactly as search_paths_wide_kernel does it -- wide_visit.h is the visit both run; thread 0
+// keeps the dirty bits in LDS and picks the next tile -- the window is scanned for words out of range, and the threads j <= tid < P
+// with that safe_kj read their word from the slab and write the entries (k, tid) and (tid, k).  The diagonal as task_costs_kernel
+// writes it.  src_fields, src_sweeps (the most visits of tiles) and src_range go to the [count][20] arrays that the order kernel
+// reads, the time of the source's fields to src_ticks (diagnostic).  No atomics; a slab has one owner, no workgroup waits for another or reads what another wrote.
+// LDS: (126 + 2)^2 words of tile, the dirty bits of the largest window (4164 bytes), the next tile, 512 bytes of tables: 69 KiB.
+constexpr int WIDE_TABLE_AT = ((WIDE_TILE_WORDS + WIDE_DIRTY_WORDS + 1) * (int)sizeof(unsigned) + 15) & ~15;
+constexpr int COST_WIDE_LDS_BYTES = WIDE_TABLE_AT + TABLE_BYTES;
+
+__global__ __launch_bounds__(WIDE_THREADS) void task_costs_wide_kernel(const TaskArgs* __restrict__ gp)
+{
+    const TaskArgs& a = *gp;
+    const int tid = threadIdx.x;
+    unsigned* tile = (unsigned*)task_lds;
+    unsigned* dirty = tile + WIDE_TILE_WORDS;
+    int* next = (int*)(dirty + WIDE_DIRTY_WORDS);
+    double* safe = (double*)(task_lds + WIDE_TABLE_AT);
+    int* cell = (int*)(task_lds + WIDE_TABLE_AT + 256);
+    unsigned* slab = a.wide_slabs + (size_t)blockIdx.x * a.wide_cells;
+    const long long cap = task_window_cap(a);
+    const ps::Grid g = ps::make_grid(a.map.dist, a.map.nx, a.map.ny, a.map.x_lo, a.map.y_lo, a.map.x_hi, a.map.y_hi, a.map.res);
+    const int sources = 2 * a.max_tasks, items = a.count * sources;
+    for (int i = blockIdx.x; i < items; i += a.wide_slots) {
+        const int m = i / sources, k = i - m * sources;
+        if (a.status[m] != tp::E_WINDOW) continue; // what task_costs_kernel left: the same in every thread, as every branch up to the first barrier
+        const MissionIn in = mission_in(a, m);
+        if (in.masked) continue;
+        const tp::Mission ms = tp::check_mission(g, in.n, a.max_tasks, in.pts, in.assign, a.mode, a.window_margin, cap);
+        const int cells = ms.wx * ms.wy, P = ms.P;
+        if (ms.status != tp::OK || cells <= a.lds_cells || k >= P - 1) continue;
+        int* mat = a.matrix + (size_t)m * MATRIX_INTS;
+        if (tid < P) {
+            double dj, dk;
+            cell[tid] = tp::point_cell(g, ms, in.pts, tid, &dj);
+            (void)tp::point_cell(g, ms, in.pts, k, &dk);
+            safe[tid] = tp::pair_safe(a.safe_dis, dk, dj); // used for tid > k only
+        }
+        if (tid == 0) {
+            tp::put_entry(mat, k, k, tp::Cost{0, 0});
+            if (k == P - 2) tp::put_entry(mat, P - 1, P - 1, tp::Cost{0, 0});
+        }
+        __syncthreads();
+        const long long t_begin = wall_clock64();
+        const int cell_k = cell[k];
+        int fields = 0, most = 0, range = 0;
+        for (int j = k + 1; j < P; ++j) {
+            const double s = safe[j];
+            bool first = true;
+            for (int e = k + 1; e < j; ++e) first = first && !(safe[e] == s);
+            if (!first) continue; // uniform
+            const ps::Window w = tp::field_window(ms, cell_k, s);
+            for (int c = tid; c < cells; c += WIDE_THREADS) {
+                const int x = c / w.wy;
+                slab[c] = ps::first_word(g, w, x, c - x * w.wy);
+            }
+            const ps::Tiling tl = ps::make_tiling<WTX, WTY>(w);
+            const int n_tiles = tl.ntx * tl.nty;
+            for (int e = tid; e < (n_tiles + 31) / 32; e += WIDE_THREADS) dirty[e] = 0u;
+            __syncthreads();
+            ps::Cursor cu = ps::cursor_begin();
+            int visits = 0;
+            if (tid == 0) tp::dirty_begin<WTX, WTY>(dirty, tl, w); // the root's tile and those of its neighbours
+            for (;;) {
+                if (tid == 0) *next = ps::next_visit(dirty, n_tiles, cu);
+                __syncthreads();
+                const int t = *next;
+                if (t < 0) break;
+                ++visits;
+                if (wide_visit(slab, w, ps::tile_at<WTX, WTY>(w, tl, t), tile, tid) && tid == 0) ps::mark_neighbours(dirty, tl, t);
+                __syncthreads(); // the stores before the next loads, and *next and the tile array are free again
+            }
+            int out = 0;
+            for (int c = tid; c < cells; c += WIDE_THREADS) out |= (int)ps::out_of_range(slab[c]);
+            range |= __syncthreads_or(out);
+            ++fields;
+            most = max(most, visits);
+            if (tid >= j && tid < P && safe[tid] == s) {
+                const tp::Cost c = tp::read_cost(slab, cell_k, cell[tid]);
+                tp::put_entry(mat, k, tid, c);
+                tp::put_entry(mat, tid, k, c);
+            }
+            __syncthreads(); // the words are read out before the next field overwrites them
+        }
+        if (tid == 0) {
+            a.src_fields[(size_t)m * tp::MAX_LEGS + k] = fields;
+            a.src_sweeps[(size_t)m * tp::MAX_LEGS + k] = most;
+            a.src_range[(size_t)m * tp::MAX_LEGS + k] = range;
+            a.src_ticks[(size_t)m * tp::MAX_LEGS + k] = wall_clock64() - t_begin;
+        }
+        __syncthreads(); // the tables are read out before the next item overwrites them
+    }
+}
+
 // ---- what the three order kernels share --------------------------------------------------------------------------------------
-// the mission of an order kernel's workgroup; false where task_costs_kernel wrote the status and there is nothing to order
+// the mission of an order kernel's workgroup; false where the cost kernels wrote the status and there is nothing to order.  A
+// mission on a window beyond LDS (it took task_costs_wide_kernel; task_costs_kernel left its status at E_WINDOW) has its per-source
+// range flags read here, by every thread alike: one set, and thread 0 publishes E_RANGE -- status, n_order = 0, the diagnostics --
+// and nothing is ordered.  The flags of no other mission are read
+__device__ inline void publish(const TaskArgs& a, int m, const double* pts, int n, int P, int status, const int* order, int n_order, const int* total);
 __device__ inline bool order_mission(const TaskArgs& a, int m, MissionIn* in, tp::Mission* ms)
 {
     *in = mission_in(a, m);
     if (in->masked) return false;
     const ps::Grid g = ps::make_grid(a.map.dist, a.map.nx, a.map.ny, a.map.x_lo, a.map.y_lo, a.map.x_hi, a.map.y_hi, a.map.res);
-    *ms = tp::check_mission(g, in->n, a.max_tasks, in->pts, in->assign, a.mode, a.window_margin);
-    return ms->status == tp::OK && ms->wx * ms->wy <= a.lds_cells;
+    *ms = tp::check_mission(g, in->n, a.max_tasks, in->pts, in->assign, a.mode, a.window_margin, task_window_cap(a));
+    if (ms->status != tp::OK) return false;
+    if (ms->wx * ms->wy <= a.lds_cells) return true;
+    int range = 0;
+    for (int k = 0; k < ms->P - 1; ++k) range |= a.src_range[(size_t)m * tp::MAX_LEGS + k];
+    if (!range) return true;
+    if (threadIdx.x == 0) publish(a, m, in->pts, in->n, ms->P, tp::E_RANGE, nullptr, 0, nullptr);
+    return false;
 }
 // the matrix of the mission to LDS; the barrier behind it is the caller's
 __device__ inline void load_matrix(const TaskArgs& a, int m, int P, int* mat, int tid)
@@ -304,6 +416,8 @@ hipError_t task_configure()
 {
     hipError_t e = hipFuncSetAttribute((const void*)task_costs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cost_lds_bytes(ps::MAX_CELLS));
     if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute((const void*)task_costs_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, COST_WIDE_LDS_BYTES);
+    if (e != hipSuccess) return e;
     e = hipFuncSetAttribute((const void*)task_order_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, OPTIMAL_LDS_BYTES);
     if (e != hipSuccess) return e;
     e = hipFuncSetAttribute((const void*)task_assign_order_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ASSIGNED_LDS_BYTES);
@@ -311,11 +425,15 @@ hipError_t task_configure()
     return hipFuncSetAttribute((const void*)task_joint_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, JOINT_LDS_BYTES);
 }
 
-hipError_t task_plan(const TaskArgs* d_args, int count, int max_tasks, int mode, int lds_cells, hipStream_t s)
+hipError_t task_plan(const TaskArgs* d_args, int count, int max_tasks, int mode, int lds_cells, int wide_slots, hipStream_t s)
 {
     void* args[] = {&d_args};
     hipError_t e = hipLaunchKernel((const void*)task_costs_kernel, dim3(count * 2 * max_tasks), dim3(COST_THREADS), args, cost_lds_bytes(lds_cells), s);
     if (e != hipSuccess) return e;
+    if (wide_slots > 0) { // a reservation: the missions that the first kernel left at E_WINDOW, on its slabs
+        e = hipLaunchKernel((const void*)task_costs_wide_kernel, dim3(wide_slots), dim3(WIDE_THREADS), args, COST_WIDE_LDS_BYTES, s);
+        if (e != hipSuccess) return e;
+    }
     return task_order(d_args, count, mode, s);
 }
 

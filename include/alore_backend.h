@@ -509,7 +509,10 @@ int alore_backend_get_laser(alore_backend_handle h, int count, double *range_ima
  * ALORE_BE_SEARCH_E_RANGE: a cost is the pair (a, b) in 16 bits each, ordered exactly while both stay below 32768, which a window
  * of 32768 cells guarantees and one of 4 M cells does not; a slot in whose window the goal reaches a cell whose least cost has
  * a >= 32767 or b >= 32767 (a route of more than 3 km at 0.1 m) fails with it, whatever its own path.  alore_backend_task_plan
- * takes no part in the reservation and keeps ALORE_BE_TASK_E_WINDOW at ALORE_BE_SEARCH_MAX_CELLS. */
+ * takes no part in the reservation and keeps ALORE_BE_TASK_E_WINDOW at ALORE_BE_SEARCH_MAX_CELLS.
+ * alore_backend_task_plan has a reservation of its own, alore_backend_task_reserve (below): with it a mission whose window has more
+ * than ALORE_BE_SEARCH_MAX_CELLS cells has its cost fields on that reservation's slabs, by the same tiles.  The legs of such a
+ * mission are searched afterwards only on a handle that also has a search reservation large enough for them. */
 typedef struct alore_backend_search_params {
     double safe_dis;      /* jps_safe_dis */
     double window_margin; /* metres round the bounding box of start and goal */
@@ -608,10 +611,13 @@ int alore_backend_search_wide_ticks(alore_backend_handle h, int count, long long
 #define ALORE_BE_TASK_OK 0
 #define ALORE_BE_TASK_MASKED 1          /* the mask left the mission out: only its status was written */
 #define ALORE_BE_TASK_E_ENDPOINT (-1)   /* a point of the mission is not finite or outside [lo, hi] of the map */
-#define ALORE_BE_TASK_E_WINDOW (-3)     /* the mission's window has more than ALORE_BE_SEARCH_MAX_CELLS cells */
+#define ALORE_BE_TASK_E_WINDOW (-3)     /* the mission's window has more than ALORE_BE_SEARCH_MAX_CELLS cells, or more than the reservation */
 #define ALORE_BE_TASK_E_TASKS (-6)      /* n outside 1..max_tasks, (optimal mode) an assignment that is no permutation, (joint mode) n > 5 */
 #define ALORE_BE_TASK_E_NO_ORDER (-7)   /* optimal and joint mode: no order has a finite cost; assigned mode: no assignment has a finite
                                            sum of carry legs, or the one chosen has no finite order (the matrix is written) */
+#define ALORE_BE_TASK_E_RANGE (-8)      /* wide missions only (alore_backend_task_reserve): a cost field of the mission has a reached
+                                           cell whose cost has a component of 32767 or more; decided after the matrix and before
+                                           any ordering, so before ALORE_BE_TASK_E_NO_ORDER (-6 is ALORE_BE_TASK_E_TASKS here) */
 typedef struct alore_backend_task_params {
     double safe_dis;      /* jps_safe_dis */
     double window_margin; /* metres round the bounding box of the mission's points */
@@ -628,10 +634,23 @@ void alore_backend_task_default_params(alore_backend_task_params *p);
  * diagnostics are).  device_pointers != 0: n_tasks, points, assignment and mask are DEVICE memory read in stream order; nothing
  * crosses the bus but the argument block and nothing waits.  device_pointers == 0: they are HOST memory; they are uploaded, the
  * stream is synchronised, and the call returns, for the first mission that failed, ALORE_BE_E_INVALID (tasks, end point, no order)
- * or ALORE_BE_E_UNSUPPORTED (window); the error text of such a return begins with "task_plan: mission failed", every other error means
+ * or ALORE_BE_E_UNSUPPORTED (window, range); the error text of such a return begins with "task_plan: mission failed", every other error means
  * that nothing was launched and the slab is as it was.
  * Successive calls on one handle must be ordered on the device, on one stream or by events: the argument block on the device is the
- * handle's, and a call overwrites it while the kernels of an earlier call on an unordered stream may still read it. */
+ * handle's, and a call overwrites it while the kernels of an earlier call on an unordered stream may still read it.
+ * MISSIONS ON LARGER WINDOWS are opt-in: after alore_backend_task_reserve(h, max_cells, slots) a mission whose window has more than
+ * ALORE_BE_SEARCH_MAX_CELLS and at most max_cells cells is planned like any other, a larger one stays ALORE_BE_TASK_E_WINDOW.  A
+ * third kernel (csrc/task_plan.hip: task_costs_wide_kernel, `slots` workgroups) runs between the two and computes the fields of such
+ * missions in the reservation's slabs, tile by tile as the wide search does (csrc/path_search_wide.h); the matrix, the orders of
+ * all four modes, the tie rules, legs, `fields`, masked and failed missions are as above, bit for bit what the contract says.
+ * `sweeps` of such a mission is the most visits of tiles any of its fields needed.  One status exists on that route only,
+ * ALORE_BE_TASK_E_RANGE: a field is rooted at the cell of the LOWER-indexed point of a pair (source k, for the targets j > k, one
+ * field per distinct safe distance); if any field of the mission reaches a cell whose least cost has a >= 32767 or b >= 32767 the
+ * mission fails with it after the matrix and before any ordering, in every mode: status, n_order = 0, fields and sweeps are
+ * written, its matrix rows are unspecified, order, total, legs and the assignment rows untouched.  Without that status every
+ * entry has both components below 32767, so sums of twenty legs stay exact as stated above.  Missions of at most
+ * ALORE_BE_SEARCH_MAX_CELLS cells take the first kernel as before and keep their bits.  The device-pointer form still allocates
+ * nothing, waits for nothing and moves only the argument block; the host form's return code is taken after all kernels. */
 int alore_backend_task_plan(alore_backend_handle h, int count, int max_tasks, const int *n_tasks, const double *points,
                             int point_row_stride_bytes, const int *assignment_or_null, const alore_backend_task_params *params,
                             int device_pointers, const int *mask, int mask_stride_bytes, void *stream);
@@ -639,6 +658,16 @@ int alore_backend_task_plan(alore_backend_handle h, int count, int max_tasks, co
  * lie in the slab, with that call's arguments (for device_pointers != 0 its inputs must still be as they were); it writes what that
  * call wrote.  Nothing waits.  What tools/task_assign.py times the order kernels with. */
 int alore_backend_task_reorder(alore_backend_handle h, void *stream);
+/* Reserves device memory for missions on windows of more than ALORE_BE_SEARCH_MAX_CELLS cells: `slots` slabs of max_cells words,
+ * this call's own (alore_backend_search_reserve's slabs stay the search's).  max_cells in (32768, 1 << 22], slots in [1, 1024],
+ * slots * max_cells * 4 <= 1 GiB, else ALORE_BE_E_INVALID; a second call replaces the first (waits for the stream of the last
+ * alore_backend_task_plan); max_cells = 0 releases it.  No map is needed yet.  `slots` is the number of (mission, source point)
+ * pairs whose fields are computed at a time (one workgroup each); a call with more of them takes them in turn. */
+int alore_backend_task_reserve(alore_backend_handle h, int max_cells, int slots);
+int alore_backend_task_reserved(alore_backend_handle h, int *max_cells, int *slots);   /* 0, 0 without one */
+/* diagnostic, with a task reservation only: HOST out[count][ALORE_BE_TASK_MAX_LEGS], per mission and source point the ticks of the
+ * device's 100 MHz clock that its fields took on the wide route; a source that did not take it keeps what it had (0 at first); waits */
+int alore_backend_task_wide_ticks(alore_backend_handle h, int count, long long *out);
 /* The handle's device slab of the missions [max_problems].  Leg l of every mission goes into alore_backend_search_paths
  * (device_pointers = 1) as it lies: start_xy = leg_start_xy + 2 l, goal_xy = leg_goal_xy + 2 l, both strides
  * ALORE_BE_TASK_MAX_LEGS * 16 bytes.  Rows of order and of the legs beyond n_order are left untouched. */
