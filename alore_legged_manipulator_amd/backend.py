@@ -254,6 +254,7 @@ def _bind(L):
                                           C.c_void_p]
     L.alore_backend_device_build_status.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.alore_backend_build_status.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.alore_backend_launch_order.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.alore_backend_get_problems.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), DP, DP, DP, DP, DP, DP, DP, C.POINTER(C.c_int)]
     L.alore_backend_predicted_state_device.argtypes = [C.c_void_p, C.c_int, C.c_double] + [C.c_void_p] * 8
     L.alore_backend_plan_masked.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
@@ -462,7 +463,8 @@ def _mask(mask, stride):
 
 
 class BatchedMSPlanner:
-    """MSPlanner for a batch.  ``max_pieces``: the longest trajectory (pieces) the handle accepts (<= 32)."""
+    """MSPlanner for a batch.  ``max_pieces``: the longest trajectory (pieces) the handle accepts (<= 64: the handle
+    takes the 16-, 32- or 64-piece build of the optimiser, ``self.P``; 64 pieces are a route of about 50 m at the default front end)."""
 
     def __init__(self, max_problems: int, max_pieces: int = 16, config: BackendConfig | None = None, device: int = 0):
         self.L = _lib.load()
@@ -472,7 +474,7 @@ class BatchedMSPlanner:
         rc = self.L.alore_backend_create(C.byref(self.cfg), device, max_pieces, max_problems, C.byref(self.h))
         if rc != 0:
             raise BackendError(f"alore_backend_create failed ({rc}): no GPU, or unsupported configuration; there is no CPU path")
-        self.P = 16 if max_pieces <= 16 else 32
+        self.P = 16 if max_pieces <= 16 else 32 if max_pieces <= 32 else 64
         self.B = max_problems
         self.count = 0
         self._keep = None
@@ -947,6 +949,13 @@ class BatchedMSPlanner:
         n = int(count or self.count)
         out = np.zeros(n, np.int32)
         self._check(self.L.alore_backend_build_status(self.h, n, out.ctypes.data_as(C.POINTER(C.c_int))))
+        return out
+
+    def launch_order(self, count: int | None = None) -> np.ndarray:
+        """the launch order of the last set_problems / set_paths[_device]: most pieces first, stable in the slot index (waits)"""
+        n = int(count or self.count)
+        out = np.zeros(n, np.int32)
+        self._check(self.L.alore_backend_launch_order(self.h, n, out.ctypes.data_as(C.POINTER(C.c_int))))
         return out
 
     def device_build_status(self) -> int:

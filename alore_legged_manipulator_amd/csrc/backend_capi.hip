@@ -352,7 +352,7 @@ int alore_backend_create(const alore_backend_config* cfg, int device, int max_pi
     *out = nullptr;
     static_assert(bclass::MEM_MAX == backend::MEM_MAX, "backend_classes.h checks mem_size against the history the kernel has");
     if (bclass::invalid_field(*cfg)) return ALORE_BE_E_UNSUPPORTED;
-    if (max_pieces > 32) return ALORE_BE_E_UNSUPPORTED;
+    if (max_pieces > 64) return ALORE_BE_E_UNSUPPORTED;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ALORE_BE_E_NO_DEVICE;
     if (device < 0 || device >= ndev) return ALORE_BE_E_INVALID;
@@ -361,7 +361,7 @@ int alore_backend_create(const alore_backend_config* cfg, int device, int max_pi
     if (!h) return ALORE_BE_E_NOMEM;
     h->cfg = *cfg;
     h->device = device;
-    h->P = max_pieces <= 16 ? 16 : 32; // two kernel instantiations: piece capacity 16 or 32
+    h->P = max_pieces <= 16 ? 16 : max_pieces <= 32 ? 32 : 64; // three kernel instantiations: piece capacity 16, 32 or 64
     h->B = max_problems;
     const size_t B = (size_t)max_problems, P = (size_t)h->P, ns = 3 * P;
     hipError_t e = hipSuccess;
@@ -373,7 +373,7 @@ int alore_backend_create(const alore_backend_config* cfg, int device, int max_pi
     A(dalloc(&h->r_ok, B)); A(dalloc(&h->r_status, B));
     A(dalloc(&h->d_hist, B * backend::MEM_MAX * 2 * ns));
     A(dalloc(&h->d_gram, B * (size_t)backend::GRAM_DOUBLES));
-    A(dalloc(&h->d_pcr, B * (size_t)backend::WS_DOUBLES));
+    A(dalloc(&h->d_pcr, B * (size_t)backend::ws_doubles(h->P)));
     if (std::getenv("ALORE_BE_STAMPS")) A(dalloc(&h->d_stamps, (size_t)64));
     A(dalloc(&h->d_x, B * ns)); A(dalloc(&h->d_g, B * ns)); A(dalloc(&h->d_lam, B * 2)); A(dalloc(&h->d_rho, B * 2));
     A(dalloc(&h->d_cost, B)); A(dalloc(&h->d_err, B * 2)); A(dalloc(&h->d_ret, B * 3)); A(dalloc(&h->d_params, 1)); A(dalloc(&h->d_order, B));
@@ -677,7 +677,7 @@ int alore_backend_set_paths(alore_backend_handle h, int count, const alore_backe
     BE_TRY(h, hipMemcpyAsync(h->d_build_in, h->h_build, up, hipMemcpyHostToDevice, s));
     BE_TRY(h, hipEventRecord(h->ev_build, s));
     h->build_pending = true;
-    BE_TRY(h, backend::build_problems((const backend::BuildArgs*)h->d_build_in, count, s));
+    BE_TRY(h, backend::build_problems((const backend::BuildArgs*)h->d_build_in, count, h->P, s));
     h->count = count;
     if (!device_pointers) {
         int* hst = (int*)h->h_stage;
@@ -704,6 +704,16 @@ int alore_backend_build_status(alore_backend_handle h, int count, int* out)
     BE_TRY(h, hipSetDevice(h->device));
     BE_TRY(h, hipDeviceSynchronize());
     BE_TRY(h, hipMemcpy(out, h->d_build_status, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost));
+    return ALORE_BE_OK;
+}
+
+int alore_backend_launch_order(alore_backend_handle h, int count, int* out)
+{
+    if (!h || count < 1 || count > h->B || !out) return fail(h, ALORE_BE_E_INVALID, "launch_order: bad argument");
+    if (count != h->count) return fail(h, ALORE_BE_E_INVALID, "launch_order: the order covers the slots of the last set_problems / set_paths, all of them");
+    BE_TRY(h, hipSetDevice(h->device));
+    BE_TRY(h, hipDeviceSynchronize());
+    BE_TRY(h, hipMemcpy(out, h->d_order, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost));
     return ALORE_BE_OK;
 }
 

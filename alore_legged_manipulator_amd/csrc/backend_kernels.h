@@ -14,11 +14,20 @@ using Status = alore_backend_status;
 constexpr int MEM_MAX = 256; // L-BFGS history slots per problem (global_planning3ms.yaml: mem_size 256)
 // per problem, next to the history: for every aligned chunk of 8 slots the 8 x 8 block G[k][l] = s_k . y_l (k < l; the rest stays
 // zero) row by row, its transpose, then y's and 1 / y's per slot (backend_kernels.hip: two_loop_gram)
-constexpr int PCR_DOUBLES = 5 * 32 * 8 + 32 * 4; // per problem: [step][knot][alpha, gamma (2 x 2 each)], then [knot][D^-1]
-// ... followed in the same per-problem workspace by two node arrays of an evaluation that are written and read once or twice and so need
-// no LDS: the order-2 node terms of the even nodes [32 * 9][2] and the duration-gradient terms per node [32 * 17]
-constexpr int WS_EB = PCR_DOUBLES, WS_NODET = WS_EB + 32 * 9 * 2, WS_CS = WS_NODET + 32 * 17, WS_DOUBLES = WS_CS + 2 * 32 * 17; // ... and cos / sin of the heading per node [node][2]
 constexpr int GRAM_G = 0, GRAM_GT = (MEM_MAX / 8) * 64, GRAM_YS = 2 * GRAM_GT, GRAM_RYS = GRAM_YS + MEM_MAX, GRAM_DOUBLES = GRAM_RYS + MEM_MAX;
+// The per-problem workspace of an evaluation is sized by the build's capacity P (16, 32 or 64 pieces): the 16 and 32 builds share
+// the layout for 32 knots and 5 elimination steps, the 64 build has 64 knots and 6 steps
+constexpr int ws_knots(int P) { return P <= 32 ? 32 : 64; }
+constexpr int ws_steps(int P) { return P <= 32 ? 5 : 6; }
+constexpr int pcr_doubles(int P) { return ws_steps(P) * ws_knots(P) * 8 + ws_knots(P) * 4; } // per problem: [step][knot][alpha, gamma (2 x 2 each)], then [knot][D^-1]
+// ... followed in the same per-problem workspace by two node arrays of an evaluation that are written and read once or twice and so need
+// no LDS: the order-2 node terms of the even nodes [knots * 9][2] and the duration-gradient terms per node [knots * 17]
+constexpr int ws_eb(int P) { return pcr_doubles(P); }
+constexpr int ws_nodet(int P) { return ws_eb(P) + ws_knots(P) * 9 * 2; }
+constexpr int ws_cs(int P) { return ws_nodet(P) + ws_knots(P) * 17; }
+constexpr int ws_doubles(int P) { return ws_cs(P) + 2 * ws_knots(P) * 17; } // ... and cos / sin of the heading per node [node][2]
+static_assert(ws_doubles(16) == 3616 && ws_doubles(32) == 3616 && ws_eb(32) == 1408 && ws_nodet(32) == 1984 && ws_cs(32) == 2528,
+              "the workspace of the 16 and 32 builds keeps its layout");
 
 enum Mode { MODE_PLAN = 0, MODE_EVAL = 1, MODE_LBFGS = 2 };
 
@@ -58,7 +67,7 @@ struct Params {
     ResultStore res;
     double* hist; // [B][MEM_MAX][2][3P]
     double* gram; // [B][GRAM_DOUBLES], zero-initialised once (the lower triangles are never written)
-    double* pcr;  // [B][WS_DOUBLES] per-problem workspace of an evaluation: elimination factors of the knot system of the current evaluation (spline solve -> adjoint solve)
+    double* pcr;  // [B][ws_doubles(P)] per-problem workspace of an evaluation: elimination factors of the knot system of the current evaluation (spline solve -> adjoint solve)
     int count, mode;
     // MODE_EVAL / MODE_LBFGS
     int stage, max_iter;
@@ -129,7 +138,8 @@ struct BuildArgs {
     const int* class_of; // [B]
 };
 // both kernels read their arguments from d_args (device memory, filled in stream order before the launch)
-hipError_t build_problems(const BuildArgs* d_args, int count, hipStream_t s);
+// (P: the handle's piece capacity, BuildArgs::P -- it selects the shape of launch_order_kernel)
+hipError_t build_problems(const BuildArgs* d_args, int count, int P, hipStream_t s);
 
 // path_search.hip: way-point paths by grid search on the handle's distance field (arithmetic in path_search.h): one workgroup per
 // problem, the cost-to-goal field of the search window in LDS, then the walk and the pruning of removeCornerPts

@@ -340,12 +340,14 @@ __device__ __forceinline__ void pcr_replay(double (&r)[4], const double (&fac)[8
 // rhs / solution: y[d][lane][0..1] in LDS for d = 0, 1 (the caller's layout); all 64 lanes must call.  REPLAY = false
 // factorises (and leaves the factors of the lane's knot in F / D: registers of the caller -- 4.6 KB of LDS until round 5, which
 // cost a workgroup per CU), REPLAY = true solves with the factors of the last factorising call.
-struct PcrFactors { double F[5][8], D[4]; };
+// (five elimination steps for up to 31 knots: the 16 and 32 builds; a sixth, of stride 32, for the 63 knots of the 64 build)
+template <int P>
+struct PcrFactors { double F[ws_steps(P)][8], D[4]; };
 template <int P, bool REPLAY>
-__device__ __forceinline__ void knot_pcr(LDSQ Lds<P>& L, int M, const LDSQ double* T, LDSQ double (*y0)[2], LDSQ double (*y1)[2], PcrFactors& pf)
+__device__ __forceinline__ void knot_pcr(LDSQ Lds<P>& L, int M, const LDSQ double* T, LDSQ double (*y0)[2], LDSQ double (*y1)[2], PcrFactors<P>& pf)
 {
     constexpr bool DPP = P <= 16; // all knots (<= 15) in one DPP row
-    constexpr int PL = P <= 16 ? 16 : 32;
+    constexpr int PL = P <= 16 ? 16 : P <= 32 ? 32 : 64;
     const int e = threadIdx.x, nk = M - 1;
     const bool act = e < nk;
     (void)PL; // idle lanes (e >= nk) compute zero factors of their own (no neighbour on either side) and never use D
@@ -357,6 +359,7 @@ __device__ __forceinline__ void knot_pcr(LDSQ Lds<P>& L, int M, const LDSQ doubl
         if (4 < nk) pcr_replay<4, DPP>(r, pf.F[2]);
         if (8 < nk) pcr_replay<8, DPP>(r, pf.F[3]);
         if constexpr (P > 16) { if (16 < nk) pcr_replay<16, false>(r, pf.F[4]); }
+        if constexpr (P > 32) { if (32 < nk) pcr_replay<32, false>(r, pf.F[5]); }
         if (act) {
             const B2 di{pf.D[0], pf.D[1], pf.D[2], pf.D[3]};
             y0[e][0] = di.a * r[0] + di.b * r[1]; y0[e][1] = di.c * r[0] + di.d * r[1];
@@ -379,6 +382,7 @@ __device__ __forceinline__ void knot_pcr(LDSQ Lds<P>& L, int M, const LDSQ doubl
     if (4 < nk) pcr_step<4, DPP>(q, act, e, nk, pf.F[2]);
     if (8 < nk) pcr_step<8, DPP>(q, act, e, nk, pf.F[3]);
     if constexpr (P > 16) { if (16 < nk) pcr_step<16, false>(q, act, e, nk, pf.F[4]); }
+    if constexpr (P > 32) { if (32 < nk) pcr_step<32, false>(q, act, e, nk, pf.F[5]); }
     if (act) {
         const B2 di = inv2(q.Dk);
         pf.D[0] = di.a; pf.D[1] = di.b; pf.D[2] = di.c; pf.D[3] = di.d;
@@ -454,13 +458,14 @@ __device__ __attribute__((noinline)) double eval_cost(const Params* gp_in, unsig
     // the lane's elimination factors leave through global memory (4.6 KB per problem, read back once for the adjoint solve below:
     // kept in LDS they cost a workgroup per CU, kept in registers across the passes in between a wavefront per SIMD, and
     // eliminating twice costs 9 % more instructions per plan)
-    constexpr int PCR_PL = P <= 16 ? 16 : 32, PCR_ST = P <= 16 ? 4 : 5;
-    GLBQ double* pcr_ws = (GLBQ double*)uni_ptr(prm.pcr) + (size_t)uni(e.prob) * WS_DOUBLES;
-    GLBQ double* eb_ws = pcr_ws + WS_EB;       // [even node][2]
-    GLBQ double* nt_ws = pcr_ws + WS_NODET;    // [node]
-    GLBQ double* cs_ws = pcr_ws + WS_CS;       // [node][cos, sin]
+    constexpr int PCR_PL = P <= 16 ? 16 : P <= 32 ? 32 : 64, PCR_ST = P <= 16 ? 4 : P <= 32 ? 5 : 6;
+    static_assert(PCR_PL <= ws_knots(P) && PCR_ST <= ws_steps(P) && P <= ws_knots(P), "the per-problem workspace holds the build's factors and nodes");
+    GLBQ double* pcr_ws = (GLBQ double*)uni_ptr(prm.pcr) + (size_t)uni(e.prob) * ws_doubles(P);
+    GLBQ double* eb_ws = pcr_ws + ws_eb(P);    // [even node][2]
+    GLBQ double* nt_ws = pcr_ws + ws_nodet(P); // [node]
+    GLBQ double* cs_ws = pcr_ws + ws_cs(P);    // [node][cos, sin]
     {
-        PcrFactors pcr;
+        PcrFactors<P> pcr;
         knot_pcr<P, false>(L, M, L.T, L.y[0], L.y[1], pcr);
         if (lane < PCR_PL) {
 #pragma unroll
@@ -765,9 +770,9 @@ __device__ __attribute__((noinline)) double eval_cost(const Params* gp_in, unsig
     __syncthreads();
     BE_STAMP(15)
     { // K is symmetric: the same system, replayed with the factors of the spline solve (read back from the problem's workspace)
-        PcrFactors pcr;
+        PcrFactors<P> pcr;
 #pragma unroll
-        for (int st = 0; st < 5; ++st)
+        for (int st = 0; st < ws_steps(P); ++st)
 #pragma unroll
             for (int k = 0; k < 8; ++k) pcr.F[st][k] = 0.0;
 #pragma unroll
@@ -1384,8 +1389,9 @@ __device__ void load_problem(const Params& prm, unsigned lbase, int b)
 // final_collision, the body -- reads `prm.cfg` through its pointer as before, at constant offsets and by scalar loads, and holds no
 // class index and no second pointer.  CLASSES = false, the instantiation a handle without a table launches, has no such move: it
 // is the kernel of before, instruction for instruction; the noinline functions are shared by both.
+// The 64-piece build (Lds<64>, 78 KB: two workgroups per CU, at most one wavefront per SIMD) has the whole register file of its SIMD.
 template <int P, bool CLASSES>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void backend_kernel(const Params* __restrict__ gp0)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P > 32 ? 1 : 2, P > 32 ? 1 : 2))) void backend_kernel(const Params* __restrict__ gp0)
 {
     if (gp0->stamps && blockIdx.x == 0 && threadIdx.x == 0) gp0->stamps[63] = (long long)__builtin_readcyclecounter();
     const unsigned lbase = lds_base_of_kernel();
@@ -1543,9 +1549,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 static_assert(16 * NS >= MEM_MAX, "alpha[] shares the bytes of fx[]");
 static_assert(sizeof(Lds<16>) <= 20480, "Lds<16> must leave room for eight workgroups per CU (tools/micro/lds_fit.hip: 8 x 20480 B fit, 7 up to 23040, 6 up to 26880, 5 up to 31744)");
 
+// two workgroups of the 64-piece build share a CU's 160 KB
+static_assert(sizeof(Lds<64>) <= 80 * 1024, "Lds<64> must leave room for two workgroups per CU");
+
 size_t lds_bytes(int P)
 {
-    return P <= 16 ? sizeof(Lds<16>) : sizeof(Lds<32>);
+    return P <= 16 ? sizeof(Lds<16>) : P <= 32 ? sizeof(Lds<32>) : sizeof(Lds<64>);
 }
 
 // block k of class_params <- the launch's block with the config of class k; safe_dis / time_weight of alore_backend_eval / _lbfgs
@@ -1564,15 +1573,17 @@ __global__ void class_params_kernel(const Params* __restrict__ gp)
 hipError_t launch(const Params& p, const Params* d_params, int P, hipStream_t s)
 {
     const bool classes = p.class_params != nullptr;
-    const void* fn = classes ? (P <= 16 ? (const void*)backend_kernel<16, true> : (const void*)backend_kernel<32, true>)
-                             : (P <= 16 ? (const void*)backend_kernel<16, false> : (const void*)backend_kernel<32, false>);
+    const int build = P <= 16 ? 0 : P <= 32 ? 1 : 2; // the kernel's piece capacity: 16, 32 or 64
+    static const void* const fns[2][3] = {{(const void*)backend_kernel<16, false>, (const void*)backend_kernel<32, false>, (const void*)backend_kernel<64, false>},
+                                          {(const void*)backend_kernel<16, true>, (const void*)backend_kernel<32, true>, (const void*)backend_kernel<64, true>}};
+    const void* fn = fns[classes ? 1 : 0][build];
     const size_t lds = lds_bytes(P);
-    static size_t configured[16][4] = {{0}};
+    static size_t configured[16][6] = {{0}};
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     dev &= 15;
-    const int v = (P <= 16 ? 0 : 1) + (classes ? 2 : 0);
+    const int v = build + (classes ? 3 : 0);
     if (lds > configured[dev][v]) {
         e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;

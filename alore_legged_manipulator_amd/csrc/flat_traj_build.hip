@@ -9,11 +9,12 @@
 // Nothing of a slot is written before the path is known to build; a slot that the mask leaves out is not touched at all.
 //
 // launch_order_kernel: d_order = the slots by piece count, most pieces first, stable in the slot index -- the order of the
-// std::stable_sort in alore_backend_set_problems -- by a counting sort in one workgroup: every thread owns a contiguous run of
-// slots, counts its pieces into its own row of an LDS histogram, a prefix per bucket over the threads (slot order) and over the
-// buckets (descending) gives every thread its first position per bucket.
+// std::stable_sort in alore_backend_set_problems -- by a counting sort in one workgroup (arithmetic and shapes in launch_order.h):
+// every thread owns a contiguous run of slots, counts its pieces into its own row of an LDS histogram, a prefix per bucket over the
+// threads (slot order) and over the buckets (descending) gives every thread its first position per bucket.
 #include "backend_kernels.h"
 #include "flat_traj_build.h"
+#include "launch_order.h"
 
 namespace backend {
 namespace {
@@ -179,51 +180,35 @@ __global__ __launch_bounds__(64) void build_problems_kernel(const BuildArgs* __r
     }
 }
 
-constexpr int ORDER_THREADS = 256, ORDER_BUCKETS = 33; // piece counts 0 .. 32
-
-__global__ __launch_bounds__(ORDER_THREADS) void launch_order_kernel(const BuildArgs* __restrict__ gp)
+// the shapes are those of launch_order.h: 256 threads and 33 buckets for the 16- and 32-piece builds, 128 and 65 for the 64-piece build
+template <int BUCKETS, int THREADS>
+__global__ __launch_bounds__(THREADS) void launch_order_kernel(const BuildArgs* __restrict__ gp)
 {
-    __shared__ int hist[ORDER_THREADS][ORDER_BUCKETS]; // [thread][pieces] -> first position of that thread's slots with that many pieces
-    __shared__ int total[ORDER_BUCKETS];
+    namespace lo = launch_order;
+    __shared__ int hist[THREADS][BUCKETS]; // [thread][pieces] -> first position of that thread's slots with that many pieces
+    __shared__ int total[BUCKETS];
     const int count = gp->count, tid = threadIdx.x;
     const int* __restrict__ Mg = gp->M;
     int* __restrict__ order = gp->order;
-    const int per = (count + ORDER_THREADS - 1) / ORDER_THREADS;
-    const int lo = min(tid * per, count), hi = min(lo + per, count);
-    for (int m = 0; m < ORDER_BUCKETS; ++m) hist[tid][m] = 0;
-    for (int s = lo; s < hi; ++s) hist[tid][min(max(Mg[s], 0), ORDER_BUCKETS - 1)] += 1;
+    int first, last;
+    lo::run_of(tid, count, THREADS, &first, &last);
+    lo::count_run<BUCKETS>(Mg, first, last, hist[tid]);
     __syncthreads();
-    if (tid < ORDER_BUCKETS) { // exclusive prefix over the threads, i.e. in slot order
-        int acc = 0;
-        for (int q = 0; q < ORDER_THREADS; ++q) {
-            const int c = hist[q][tid];
-            hist[q][tid] = acc;
-            acc += c;
-        }
-        total[tid] = acc;
-    }
+    if (tid < BUCKETS) total[tid] = lo::prefix_threads<BUCKETS>(hist, THREADS, tid);
     __syncthreads();
-    if (tid == 0) { // first position of every bucket: most pieces first
-        int acc = 0;
-        for (int m = ORDER_BUCKETS - 1; m >= 0; --m) {
-            const int c = total[m];
-            total[m] = acc;
-            acc += c;
-        }
-    }
+    if (tid == 0) lo::prefix_buckets<BUCKETS>(total);
     __syncthreads();
-    for (int s = lo; s < hi; ++s) {
-        const int m = min(max(Mg[s], 0), ORDER_BUCKETS - 1);
-        order[total[m] + hist[tid][m]++] = s;
-    }
+    lo::scatter_run<BUCKETS>(Mg, first, last, hist[tid], total, order);
 }
 
-hipError_t build_problems(const BuildArgs* d_args, int count, hipStream_t s)
+hipError_t build_problems(const BuildArgs* d_args, int count, int P, hipStream_t s)
 {
     void* args[] = {&d_args};
     hipError_t e = hipLaunchKernel((const void*)build_problems_kernel, dim3(count), dim3(64), args, 0, s);
     if (e != hipSuccess) return e;
-    e = hipLaunchKernel((const void*)launch_order_kernel, dim3(1), dim3(ORDER_THREADS), args, 0, s);
+    namespace lo = launch_order;
+    if (P <= 32) e = hipLaunchKernel((const void*)launch_order_kernel<lo::buckets_of(32), lo::threads_of(32)>, dim3(1), dim3(lo::threads_of(32)), args, 0, s);
+    else e = hipLaunchKernel((const void*)launch_order_kernel<lo::buckets_of(64), lo::threads_of(64)>, dim3(1), dim3(lo::threads_of(64)), args, 0, s);
     if (e != hipSuccess) return e;
     return hipGetLastError();
 }

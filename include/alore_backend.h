@@ -28,7 +28,7 @@ extern "C" {
 #define ALORE_BE_E_NO_DEVICE (-2)
 #define ALORE_BE_E_HIP (-3)
 #define ALORE_BE_E_NOMEM (-4)
-#define ALORE_BE_E_UNSUPPORTED (-5) /* more pieces than the handle was created for */
+#define ALORE_BE_E_UNSUPPORTED (-5) /* more pieces than the handle was created for, or than any handle takes (64) */
 
 typedef struct alore_backend_planner *alore_backend_handle;
 
@@ -89,6 +89,13 @@ typedef struct alore_backend_status {
 } alore_backend_status;
 
 void alore_backend_default_config(alore_backend_config *c);
+/* max_pieces: the longest trajectory a slot holds, 1 .. 64; the handle rounds it up to the piece capacity P of one of the three
+ * builds of the optimiser -- 16, 32 or 64 (alore_backend_slots: max_pieces) -- and every slab below is sized by P.  64 pieces are
+ * a route of about 50 m at the default front-end parameters.  More than 64: ALORE_BE_E_UNSUPPORTED.
+ * Device memory per problem slot is dominated by the L-BFGS history [256][2][3 P] doubles: 192 KiB at P = 16, 384 KiB at 32 and
+ * 768 KiB at 64; with the cross products (36 KiB), the evaluation workspace (28.25 KiB at P <= 32, 60.5 KiB at 64) and the problem
+ * and result slabs that is about 260, 455 and 880 KiB per slot.  A handle that cannot be allocated fails with ALORE_BE_E_NOMEM and
+ * leaves nothing allocated. */
 int alore_backend_create(const alore_backend_config *cfg, int device, int max_pieces, int max_problems,
                          alore_backend_handle *out);
 int alore_backend_destroy(alore_backend_handle h);
@@ -249,8 +256,12 @@ int alore_backend_set_paths(alore_backend_handle h, int count, const alore_backe
 int alore_backend_device_build_status(alore_backend_handle h, const int **out);
 /* the same copied to HOST memory out[count]; waits for the device */
 int alore_backend_build_status(alore_backend_handle h, int count, int *out);
+/* the launch order that alore_backend_set_problems / alore_backend_set_paths left on the device, copied to HOST memory out[count]
+ * (count = the slots of that call): workgroup w of alore_backend_plan works on slot out[w] -- most pieces first, stable in the slot
+ * index; waits for the device */
+int alore_backend_launch_order(alore_backend_handle h, int count, int *out);
 /* The problem slots as they lie on the device, copied to HOST arrays (any pointer may be NULL; P = max_pieces as rounded by the
- * handle, 16 or 32): n_pieces [count], inner [count][(P-1)*2] (yaw, s), init_T [count], positions [count][P*2] (way-point xy,
+ * handle, 16, 32 or 64): n_pieces [count], inner [count][(P-1)*2] (yaw, s), init_T [count], positions [count][P*2] (way-point xy,
  * then final xy), head / tail [count][6] ([yaw | s][p v a]), start_xytheta [count][3], final_xy [count][2], if_cut [count].
  * Waits for the device. */
 int alore_backend_get_problems(alore_backend_handle h, int count, int *n_pieces, double *inner, double *init_T, double *positions,
