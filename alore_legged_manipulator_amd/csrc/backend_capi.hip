@@ -9,6 +9,7 @@
 
 #include "backend_classes.h"
 #include "backend_kernels.h"
+#include "esdf_window.h"
 #include "flat_traj_build.h"
 #include "fleet_manager.h"
 #include "laser_scan_launch.h"
@@ -454,9 +455,12 @@ int alore_backend_build_esdf(alore_backend_handle h, const unsigned char* grid, 
         BE_TRY(h, backend::esdf_fill_max(h->d_map, n, nullptr));
         h->map = backend::MapView{h->d_map, nx, ny, x_lo, y_lo, x_lo + nx * res, y_lo + ny * res, res};
     }
+    // the window can end one cell past the map (esdf_window.h): esdf_rows then reads up to cell n + ny.  Cells past the grid are
+    // unknown (0), as in the resident map, not whatever follows the allocation
     unsigned char* d_grid = nullptr;
-    BE_TRY(h, hipMalloc((void**)&d_grid, n));
-    hipError_t e = hipMemcpy(d_grid, grid, n, hipMemcpyHostToDevice);
+    BE_TRY(h, hipMalloc((void**)&d_grid, n + (size_t)ny + 1));
+    hipError_t e = hipMemset(d_grid + n, 0, (size_t)ny + 1);
+    if (e == hipSuccess) e = hipMemcpy(d_grid, grid, n, hipMemcpyHostToDevice);
     int empty = 0;
     if (e == hipSuccess) e = backend::esdf_update(d_grid, nx, ny, res, x_lo, y_lo, odom_x, odom_y, detection_range, h->d_map, nullptr, &empty);
     (void)hipFree(d_grid);

@@ -264,7 +264,7 @@ struct EsdfWorkspace {
     size_t cells;                // capacity: (X + 1) (Y + 1) of the largest window
     int lines;                   // capacity: max(X, Y) + 1
 };
-void esdf_workspace_size(int GLX, int GLY, double res, double range, size_t* cells, int* lines);
+// esdf_workspace_size(GLX, GLY, res, range, &cells, &lines): esdf_window.h, with the window's arithmetic
 hipError_t esdf_enqueue(const unsigned char* d_grid, int GLX, int GLY, double res, double x_lo, double y_lo, double odom_x, double odom_y,
                         double range, double* d_dist, const EsdfWorkspace& w, hipStream_t s, int* empty_window);
 

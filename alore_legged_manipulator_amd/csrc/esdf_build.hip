@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "backend_kernels.h"
+#include "esdf_window.h"
 
 namespace backend {
 
@@ -121,29 +122,18 @@ hipError_t esdf_fill_max(double* p, size_t n, hipStream_t s)
     return hipGetLastError();
 }
 
-// the largest window of a map of GLX x GLY cells at this detection range: (X + 1) <= xc, (Y + 1) <= yc
-void esdf_workspace_size(int GLX, int GLY, double res, double range, size_t* cells, int* lines)
-{
-    const double span = ceil(2.0 * range / res) + 3.0;
-    const int xc = span < GLX + 1 ? (int)span : GLX + 1, yc = span < GLY + 1 ? (int)span : GLY + 1;
-    *cells = (size_t)xc * yc;
-    *lines = xc > yc ? xc : yc;
-}
-
-// d_grid: device copy of the state grid; d_dist: the map the optimiser reads (updated in the window).  Enqueues the five kernels
-// on `s` with the caller's workspace (tmp, pos, neg: w.cells doubles; v: w.lines (w.lines + 2) ints; z: w.lines (w.lines + 3)
-// doubles) and returns: nothing is allocated and nothing waits.  A window that the workspace does not hold is refused.
+// d_grid: device copy of the state grid, followed by GLY + 1 zero cells (esdf_window.h); d_dist: the map the optimiser reads (updated
+// in the window).  Enqueues the five kernels on `s` with the caller's workspace (tmp, pos, neg: w.cells doubles; v: w.lines
+// (w.lines + 2) ints; z: w.lines (w.lines + 3) doubles) and returns: nothing is allocated and nothing waits.  A window that the
+// workspace does not hold is refused.
 hipError_t esdf_enqueue(const unsigned char* d_grid, int GLX, int GLY, double res, double x_lo, double y_lo, double odom_x, double odom_y,
                         double range, double* d_dist, const EsdfWorkspace& w, hipStream_t s, int* empty_window)
 {
-    const double inv = 1.0 / res, gx = GLX * res, gy = GLY * res;
-    const int min_x = (int)floor(fmax(0.0, odom_x - range - x_lo) * inv), min_y = (int)floor(fmax(0.0, odom_y - range - y_lo) * inv);
-    const int max_x = (int)ceil(fmin(gx, odom_x + range - x_lo) * inv) - 1, max_y = (int)ceil(fmin(gy, odom_y + range - y_lo) * inv) - 1;
-    const int X = max_x - min_x, Y = max_y - min_y;
-    *empty_window = (X < 1 || Y < 1) ? 1 : 0;
+    const EsdfWindow win = esdf_window(GLX, GLY, res, x_lo, y_lo, odom_x, odom_y, range);
+    const int min_x = win.min_x, min_y = win.min_y, X = win.X, Y = win.Y, D = win.D;
+    *empty_window = win.empty;
     if (*empty_window) return hipSuccess;
-    const size_t total = (size_t)(X + 1) * (Y + 1);
-    const int D = (X > Y ? X : Y) + 1;
+    const size_t total = win.total;
     if (total > w.cells || D > w.lines) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(w.pos, 0, sizeof(double) * total, s);
     if (e == hipSuccess) e = hipMemsetAsync(w.neg, 0, sizeof(double) * total, s);
@@ -161,14 +151,11 @@ hipError_t esdf_enqueue(const unsigned char* d_grid, int GLX, int GLY, double re
 hipError_t esdf_update(const unsigned char* d_grid, int GLX, int GLY, double res, double x_lo, double y_lo, double odom_x, double odom_y,
                        double range, double* d_dist, hipStream_t s, int* empty_window)
 {
-    const double inv = 1.0 / res, gx = GLX * res, gy = GLY * res;
-    const int min_x = (int)floor(fmax(0.0, odom_x - range - x_lo) * inv), min_y = (int)floor(fmax(0.0, odom_y - range - y_lo) * inv);
-    const int max_x = (int)ceil(fmin(gx, odom_x + range - x_lo) * inv) - 1, max_y = (int)ceil(fmin(gy, odom_y + range - y_lo) * inv) - 1;
-    const int X = max_x - min_x, Y = max_y - min_y;
-    *empty_window = (X < 1 || Y < 1) ? 1 : 0;
+    const EsdfWindow win = esdf_window(GLX, GLY, res, x_lo, y_lo, odom_x, odom_y, range);
+    *empty_window = win.empty;
     if (*empty_window) return hipSuccess;
-    const size_t total = (size_t)(X + 1) * (Y + 1);
-    const int D = (X > Y ? X : Y) + 1, lines = D;
+    const size_t total = win.total;
+    const int D = win.D, lines = D;
     EsdfWorkspace w{};
     w.cells = total;
     w.lines = lines;

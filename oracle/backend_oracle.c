@@ -856,7 +856,10 @@ int be_update_esdf2d(const unsigned char *grid, int GLX, int GLY, double res, do
         double *dst = pass == 0 ? pos : neg;
         for (x = 0; x <= X; x++) {
             for (y = 0; y <= Y; y++) {
-                const int st = grid[(size_t)(x + min_x) * GLY + (y + min_y)];
+                /* the window can end one cell past the map where ceil((n res) (1 / res)) rounds up: the reference reads past its
+                 * buffer there; here a cell past the end of the [GLX][GLY] grid is unknown (0) and no memory is touched */
+                const size_t cell = (size_t)(x + min_x) * GLY + (y + min_y);
+                const int st = cell < (size_t)GLX * GLY ? grid[cell] : 0;
                 const int seed = pass == 0 ? (st == 2) : (st == 1 || st == 0);
                 line_in[y] = seed ? 0.0 : DBL_MAX;
             }
